@@ -14,6 +14,10 @@ Prints ONE JSON line on rank 0, including
                  HIP events on the launch stream) against the 8 TB/s peak; `valu` = the second ceiling: the instructions
                  the kernels execute (ISA census x PMC count) priced at the issue cycles tools/ubench_valu.hip measured,
                  over the SIMD cycles available at the shader clock measured DURING the timed region
+A plain run stops there.  With --full (1 GPU unless noted) the line also carries what takes runs of its own:
+  peak_measured  (in roofline) the device's read / copy bandwidth on 8-GiB buffers, and the kernel's fraction of it
+  h2d_inclusive_Gbps  the same scan fed from page-locked host memory
+  c5_count_reduce  (N > 1) C5's syncmer count reduced across the ranks
   other_configs  (1 GPU) one pass each over the other BASELINE.json configurations at their stated sizes:
                  C2 canonical 31-mer + hash64 over 10 Gbp, C4 super-k-mers k=31 m=15 over 50 Gbp of 10-kbp reads,
                  C5 syncmers k=31 s=11 over 50 Gbp of 10-kbp reads — Gbp/s, kernel ms, roofline fraction
@@ -222,6 +226,12 @@ def main():
                          "the card drawing 1,370 instead of 1,310 W (profiles/r04_ab_summary.txt, DESIGN.md section 6.3); below 2.5 M reads the launches show")
     ap.add_argument("--lanes", type=int, default=2, choices=(1, 2),
                     help="execution lanes of the context: 2 = the record pass of one range runs beside the hashing pass of the next")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline does not need: the HBM probe, the upload-inclusive figure, the CPU baseline, the other "
+                         "configurations, the next rows (1 GPU) and C5's count reduction (N > 1); the --no-* switches below trim it")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last step computed as float64 .npy files under DIR (rank 0): every range's "
+                         "count and XOR digests, and a seeded sample of the records of the two ranges still held in the output buffers")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-other-configs", action="store_true")
     ap.add_argument("--no-next-rows", action="store_true")
@@ -360,6 +370,8 @@ def main():
     for k in range(args.steps - 1):
         for a, b in zip(all_res[k * len(ranges):(k + 1) * len(ranges)], step_res):
             assert (a.count, a.xor_hash, a.xor_pos, a.xor_value) == (b.count, b.xor_hash, b.xor_pos, b.xor_value), "steps disagree"
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, np, torch, ranges, step_res, outs)
 
     t_max = elapsed
     total_count = count
@@ -390,7 +402,8 @@ def main():
         k = torch.tensor([kernel_ms], dtype=torch.float64, device=coll_dev)
         dist.all_reduce(k, op=dist.ReduceOp.MAX)
         kernel_ms = float(k.item())
-        c5_reduce = c5_count_reduce(ctx, torch, dist, rank, world, coll_dev)
+        if args.full:
+            c5_reduce = c5_count_reduce(ctx, torch, dist, rank, world, coll_dev)
 
     out = None
     if rank == 0:
@@ -471,7 +484,7 @@ def main():
             out["roofline"]["hbm_actual"] = hbm_actual
         if power is not None:
             out["power"] = power
-        if n_gpus == 1:
+        if n_gpus == 1 and args.full:
             try:
                 rd, cp = ctx.probe_hbm(8 << 30, 5)
                 out["roofline"]["peak_measured"] = {"read_GBps": round(rd, 1), "copy_GBps": round(cp, 1),
@@ -483,14 +496,14 @@ def main():
             out["count_allreduce_ms"] = round(allreduce_ms, 3)
         if c5_reduce is not None:
             out["c5_count_reduce"] = c5_reduce
-        if n_gpus == 1 and not args.no_cpu_baseline:
+        if n_gpus == 1 and args.full and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(np, ctx, batch, n_bases)
-        if n_gpus == 1 and not args.no_h2d:
+        if n_gpus == 1 and args.full and not args.no_h2d:
             try:
                 out["h2d_inclusive_Gbps"] = h2d_inclusive(np, torch, biolib_amd, dev, batch, cap)
             except Exception as e:  # the companion figure must not lose the bench line
                 out["h2d_inclusive_Gbps"] = {"error": repr(e)[:300]}
-    if n_gpus == 1 and not args.no_other_configs:
+    if n_gpus == 1 and args.full and not args.no_other_configs:
         batch.close()
         del outs
         torch.cuda.empty_cache()
@@ -503,6 +516,43 @@ def main():
         dist.barrier()
         dist.destroy_process_group()
     return out
+
+
+DUMP_SAMPLE = 1 << 18  # records sampled per dumped range: 2 ranges x 2^18 x (3 fields x 16 B + 8 B of index) = 29 MB
+
+
+def dump_outputs(path, np, torch, ranges, step_res, outs):
+    """--dump-outputs: what a caller of the timed path holds after its last step, for comparing two builds output by output.  Per
+    range of that step, the Result the scan filled: `range_count` and the XOR digests of its values, positions and hashes.  The
+    record arrays of the last two ranges are still in the double buffers: `last_*` and `second_last_*` hold a sample of their
+    records at sorted indices drawn from a fixed seed (`*_index`).  64-bit words are stored as (n, 2) float64 rows of their high
+    and low 32 bits, both exact in float64."""
+    os.makedirs(path, exist_ok=True)
+
+    def halves(words):
+        u = np.asarray(words, dtype=np.uint64)
+        return np.stack([(u >> np.uint64(32)).astype(np.float64), (u & np.uint64(0xFFFFFFFF)).astype(np.float64)], axis=-1)
+
+    def save(name, a):
+        np.save(os.path.join(path, name + ".npy"), np.asarray(a, dtype=np.float64))
+
+    save("range_first", [a for a, _ in ranges])
+    save("range_bases", [n for _, n in ranges])
+    save("range_count", [int(r.count) for r in step_res])
+    for field in ("xor_value", "xor_pos", "xor_hash"):
+        save("range_" + field, halves([int(getattr(r, field)) for r in step_res]).reshape(-1, 2))
+    for tag, i in (("last", len(ranges) - 1), ("second_last", len(ranges) - 2)):
+        if i < 0:
+            continue
+        count = int(step_res[i].count)
+        if count <= DUMP_SAMPLE:
+            idx = np.arange(count, dtype=np.int64)
+        else:
+            idx = np.unique(np.random.default_rng(SEED + i).integers(0, count, size=DUMP_SAMPLE))
+        sel = torch.from_numpy(idx.astype(np.int64)).to(outs[i & 1][0].device)
+        save(f"{tag}_index", idx)
+        for name, t in zip(("values", "positions", "hashes"), outs[i & 1]):
+            save(f"{tag}_{name}", halves(t.index_select(0, sel).cpu().numpy().view(np.uint64)).reshape(-1, 2))
 
 
 def h2d_inclusive(np, torch, biolib_amd, dev, batch, cap):

@@ -110,3 +110,35 @@ def test_power_sampler_reports_the_busiest_card(tmp_path):
     assert out["card"] == "card8" and out["power_W"] == {"median": 1270, "p90": 1270, "max": 1270} and out["power_cap_W"] == 1400
     assert out["sensor_clock_MHz"]["median"] == 2080 and out["samples"] >= 3
     assert bench.PowerSampler(str(tmp_path / "nothing_here")).start().finish() is None
+
+
+def test_dump_outputs_keeps_every_bit_and_the_size_bound(tmp_path):
+    """--dump-outputs: 64-bit words survive as exact (high, low) float64 halves; a range with more records than the sample holds is
+    sampled at a fixed seed, one with fewer is written whole; three fields of two sampled ranges stay far below 64 MB"""
+    import numpy as np
+    import torch
+
+    from biolib_amd.capi import Result
+
+    ranges = [(0, 750), (750, 750), (1500, 300)]
+    outs = [tuple(torch.randint(-2**62, 2**62, (bench.DUMP_SAMPLE * 4,), dtype=torch.int64) for _ in range(3)) for _ in range(2)]
+    step_res = []
+    for count in (5, bench.DUMP_SAMPLE * 3, 42):
+        r = Result()
+        r.count, r.xor_value, r.xor_hash, r.xor_pos = count, 2**64 - 1, 12345, 2**63
+        step_res.append(r)
+    bench.dump_outputs(str(tmp_path / "a"), np, torch, ranges, step_res, outs)
+    bench.dump_outputs(str(tmp_path / "b"), np, torch, ranges, step_res, outs)
+    files = sorted(os.listdir(tmp_path / "a"))
+    assert files == sorted(os.listdir(tmp_path / "b")) and len(files) == 14
+    load = lambda d, name: np.load(tmp_path / d / (name + ".npy"))
+    for f in files:
+        assert load("a", f[:-4]).dtype == np.float64 and np.array_equal(load("a", f[:-4]), load("b", f[:-4]))
+    assert sum(os.path.getsize(tmp_path / "a" / f) for f in files) < 64 << 20
+    assert load("a", "range_count").tolist() == [5, bench.DUMP_SAMPLE * 3, 42]
+    assert load("a", "range_xor_value").tolist() == [[2**32 - 1, 2**32 - 1]] * 3 and load("a", "range_xor_pos")[0].tolist() == [2**31, 0]
+    words = lambda a: (a[:, 0].astype(np.uint64) << np.uint64(32)) | a[:, 1].astype(np.uint64)
+    assert np.array_equal(load("a", "last_index"), np.arange(42)) and np.array_equal(words(load("a", "last_values")), outs[0][0][:42].numpy().view(np.uint64))
+    idx = load("a", "second_last_index").astype(np.int64)
+    assert 0.8 * bench.DUMP_SAMPLE < idx.size <= bench.DUMP_SAMPLE and np.all(np.diff(idx) > 0)
+    assert np.array_equal(words(load("a", "second_last_hashes")), outs[1][2].numpy().view(np.uint64)[idx])

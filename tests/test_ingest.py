@@ -1,6 +1,7 @@
 """FASTA/FASTQ ingest: the library's reader against what the reference's own reader
 (tests/kseq.h) returned for the fixture files (tests/golden/ingest/expected.json, generator
 make_ingest_golden.py), and — on the GPU — file -> batches -> scans against the oracle on the parsed sequences."""
+import hashlib
 import json
 import os
 import struct
@@ -13,6 +14,12 @@ import oracle_lib as O
 HERE = os.path.dirname(os.path.abspath(__file__))
 ING = os.path.join(HERE, "golden", "ingest")
 EXPECTED = json.load(open(os.path.join(ING, "expected.json")))
+
+
+def ref_verdicts(key):
+    """what the reference returned on the inputs of a test below that compares against it (generator make_ref_golden.py)"""
+    with open(os.path.join(HERE, "golden", "ref_verdicts.json")) as f:
+        return json.load(f)[key]
 
 
 @pytest.mark.parametrize("fn", sorted(EXPECTED))
@@ -153,7 +160,25 @@ def _ref_read(path):
     return [bytes(bases[int(offs[i]):int(offs[i + 1])]) for i in range(n)]
 
 
-@pytest.mark.skipif(not O.have_ref(), reason="oracle/_ref not built")
+def reads_verdict(seqs):
+    """a reader's result as recorded in tests/golden/ref_verdicts.json: None for an error, else the sequence lengths and a digest of the bases"""
+    if seqs is None:
+        return None
+    return {"lens": [len(x) for x in seqs], "sha": hashlib.sha256(b"".join(seqs)).hexdigest()[:32]}
+
+
+def _reference_verdict(recorded, i, path, text):
+    """what the reference reader returns for case i: recorded (make_ref_golden.py) and, where oracle/_ref is built, read live as well,
+    which must agree with the record"""
+    live = reads_verdict(_ref_read(path)) if O.have_ref() else None
+    if i < len(recorded):
+        assert recorded[i]["text"] == hashlib.sha256(text).hexdigest()[:16], ("the fuzz generator no longer makes the recorded case", i)
+        assert not O.have_ref() or live == recorded[i]["ref"], (i, text)
+        return recorded[i]["ref"]
+    assert O.have_ref(), "cases beyond the recorded ones (BL_FUZZ_ROUNDS > 1) need oracle/_ref"
+    return live
+
+
 def test_fuzz_host_reader_vs_reference_reader(tmp_path):
     """600 mutated FASTA/FASTQ texts: the library's host reader returns exactly what the reference's kseq returns,
     and fails exactly where it fails"""
@@ -163,45 +188,52 @@ def test_fuzz_host_reader_vs_reference_reader(tmp_path):
     for i, text in enumerate(cases(11, 600)):
         path = tmp_path / "f.txt"
         path.write_bytes(text)
-        exp = _ref_read(path)
+        exp = _reference_verdict(ref_verdicts("reader_fuzz_host"), i, path, text)
         try:
             got = [s for _, s in biolib_amd.Reader(path).records()]
         except biolib_amd.BiolibError:
             got = None
-        assert got == exp, (i, text)
+        assert reads_verdict(got) == exp, (i, text)
 
 
-@pytest.mark.skipif(not O.have_ref(), reason="oracle/_ref not built")
-def test_padded_gzip_files_read_like_the_reference_reader(tmp_path):
-    """block / tape padding behind the last gzip member (zeros, arbitrary bytes): the reference's reader (kseq over gzread)
-    returns the records and no error, and so does the library's — plain gzip through both decoders, and BGZF"""
+def padded_gzip_files():
+    """(reads, {name: file}): the same 400 reads as plain gzip (one member, two members) and BGZF, each with nothing, zeros,
+    arbitrary bytes or a lone gzip magic byte behind the last member"""
     import gzip
-
-    import biolib_amd
 
     rng = np.random.default_rng(5)
     reads = [bytes(rng.choice(np.frombuffer(b"ACGT", np.uint8), 150)) for _ in range(400)]
     text = b"".join(b"@r%d\n" % i + s + b"\n+\n" + b"I" * 150 + b"\n" for i, s in enumerate(reads))
     files = {"one.fq.gz": gzip.compress(text), "two.fq.gz": gzip.compress(text[: len(text) // 2 // 304 * 304]) + gzip.compress(text[len(text) // 2 // 304 * 304:]),
              "b.fq.gz": _bgzf(text, 9000)}
-    for name, packed in files.items():
-        for j, tail in enumerate((b"", b"\0" * 512, b"garbage!", b"\x1f")):
-            path = tmp_path / ("%d_%s" % (j, name))
-            path.write_bytes(packed + tail)
-            exp = _ref_read(path)
-            assert exp == reads, (name, j)
-            for env in ({"BL_PGZIP": "1", "BL_PGZIP_PART": "4096"}, {"BL_PGZIP": "0"}):
-                os.environ.update(env)
-                try:
-                    got = [s for _, s in biolib_amd.Reader(path, threads=4).records()]
-                finally:
-                    for k in env:
-                        os.environ.pop(k, None)
-                assert got == exp, (name, j, env)
+    return reads, {"%d_%s" % (j, name): packed + tail for name, packed in files.items() for j, tail in enumerate((b"", b"\0" * 512, b"garbage!", b"\x1f"))}
+
+
+def test_padded_gzip_files_read_like_the_reference_reader(tmp_path):
+    """block / tape padding behind the last gzip member (zeros, arbitrary bytes): the reference's reader (kseq over gzread)
+    returns the records and no error, and so does the library's — plain gzip through both decoders, and BGZF"""
+    import biolib_amd
+
+    reads, files = padded_gzip_files()
+    recorded = ref_verdicts("reader_padded_gzip")
+    assert sorted(files) == sorted(recorded)
+    for name, data in files.items():
+        path = tmp_path / name
+        path.write_bytes(data)
+        exp = recorded[name]
+        assert not O.have_ref() or reads_verdict(_ref_read(path)) == exp, name
+        assert exp == reads_verdict(reads), name
+        for env in ({"BL_PGZIP": "1", "BL_PGZIP_PART": "4096"}, {"BL_PGZIP": "0"}):
+            os.environ.update(env)
+            try:
+                got = [s for _, s in biolib_amd.Reader(path, threads=4).records()]
+            finally:
+                for k in env:
+                    os.environ.pop(k, None)
+            assert got == reads, (name, env)
 
 
 @pytest.mark.gpu
-@pytest.mark.skipif(not O.have_ref(), reason="oracle/_ref not built")
 def test_fuzz_device_parser_vs_reference_reader(tmp_path):
     """the device-side parser either refuses a text or returns exactly the reference reader's sequences — never a
     silent mis-parse, never a fault"""
@@ -210,22 +242,23 @@ def test_fuzz_device_parser_vs_reference_reader(tmp_path):
 
     ctx = biolib_amd.Context(0)
     accepted = 0
-    rounds = int(os.environ.get("BL_FUZZ_ROUNDS", "1"))  # more seeds for an exploratory run
+    rounds = int(os.environ.get("BL_FUZZ_ROUNDS", "1"))  # more seeds for an exploratory run (beyond the recorded ones: needs oracle/_ref)
     texts = [t for r in range(rounds) for t in cases(12 + r, 400)]
     for i, text in enumerate(texts):
         path = tmp_path / "f.txt"
         path.write_bytes(text)
-        exp = _ref_read(path)
+        exp = _reference_verdict(ref_verdicts("reader_fuzz_device"), i, path, text)
         try:
             b = ctx.from_text(text)
         except biolib_amd.BiolibError:
             continue
         accepted += 1
         assert exp is not None, (i, text)
-        assert b.n_seqs == len(exp) and bytes(b.download()) == b"".join(exp), (i, text)
+        parsed = bytes(b.download())
+        offs = np.concatenate([[0], np.cumsum(exp["lens"])]).astype(np.uint64)
+        assert b.n_seqs == len(exp["lens"]) and reads_verdict([parsed[int(a):int(z)] for a, z in zip(offs[:-1], offs[1:])]) == exp, (i, text)
         # sequence boundaries: every base is its own unit, windows of 2 never cross a boundary
-        seq_all = np.frombuffer(b"".join(exp), np.uint8)
-        offs = np.concatenate([[0], np.cumsum([len(s) for s in exp])]).astype(np.uint64)
+        seq_all = np.frombuffer(parsed, np.uint8)
         if len(seq_all):
             v, p, h = O.minimizers(seq_all, offs, 1, 2, 0, False, brute=False)
             got = b.minimizers(1, 2)

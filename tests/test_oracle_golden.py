@@ -2,6 +2,10 @@
 reference produced (tests/golden/, generator make_golden.py) and, when the reference
 library was built in this container, live against the reference itself.
 CPU-only: runs under -m "not gpu"."""
+import hashlib
+import json
+import os
+
 import numpy as np
 import pytest
 
@@ -152,14 +156,13 @@ def test_one_mib_digests(golden_kats):
         c4["count"], c4["xor_minimizer"], c4["xor_hash"], c4["sum_size"], c4["xor_first_pos"])
 
 
-@pytest.mark.skipif(not O.have_ref(), reason="oracle/_ref not built (needs /root/reference; build container only)")
-def test_live_against_reference_library():
-    R = O.ref()
+def library_record(ref=None):
+    """key -> what the oracle (or, given `ref`, the reference library) returns on the inputs of the comparison below: digests of
+    hash64 over random keys and of kmer_view's items, syncmer counts"""
     L = O.oracle()
     rng = np.random.default_rng(1)
-    for v in rng.integers(0, 2**63, 2000, dtype=np.uint64):
-        for s in (0, 42, 2**40 + 5):
-            assert L.blo_hash64_u64(int(v), s) == R.ref_hash64_u64(int(v), s)
+    hash64 = ref.ref_hash64_u64 if ref else L.blo_hash64_u64
+    rec = {"hash64": _digest([int(hash64(int(v), s)) for v in rng.integers(0, 2**63, 2000, dtype=np.uint64) for s in (0, 42, 2**40 + 5)])}
     for seed in range(6):
         n = 3000 + 17 * seed
         s = O.synth(100 + seed, n)
@@ -169,12 +172,30 @@ def test_live_against_reference_library():
         for k in (1, 2, 3, 8, 16, 21, 31, 32):
             for canon in (0, 1):
                 for complete in (0, 1):
-                    assert O.kmer_items(s, k, canon, complete) == O.kmer_items(s, k, canon, complete, lib=R)
+                    rec[f"kmer_items/{seed}/{k}/{canon}/{complete}"] = _digest(O.kmer_items(s, k, canon, complete, lib=ref))
         one = np.array([0, n], np.uint64)
         for (k, m, a, b) in ((31, 11, 0, 20), (21, 8, 0, 13), (9, 9, 0, 0), (15, 4, 3, 7)):
             for canon in (0, 1):
-                got = O.syncmers(s, one, k, m, a, b, canon, drop_last=True, positions=False)[0]
-                assert got == R.ref_syncmer_count(O._ptr(s), n, k, m, a, b, canon)
+                key = f"syncmers/{seed}/{k}/{m}/{a}/{b}/{canon}"
+                if ref:
+                    rec[key] = int(ref.ref_syncmer_count(O._ptr(s), n, k, m, a, b, canon))
+                else:
+                    rec[key] = int(O.syncmers(s, one, k, m, a, b, canon, drop_last=True, positions=False)[0])
+    return rec
+
+
+def _digest(items):
+    return hashlib.sha256(json.dumps(items, separators=(",", ":")).encode()).hexdigest()[:32]
+
+
+def test_live_against_reference_library():
+    """the oracle against what the reference library returned on the same inputs (tests/golden/ref_verdicts.json, generator
+    make_ref_golden.py) and, where oracle/_ref is built, against the library itself"""
+    with open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "ref_verdicts.json")) as f:
+        recorded = json.load(f)["reference_library"]
+    assert library_record() == recorded
+    if O.have_ref():
+        assert library_record(O.ref()) == recorded
 
 
 def test_closed_form_hash_equals_the_general_murmur3():

@@ -8,7 +8,7 @@ timeout -k 10 600 python -m pytest tests/test_gpu_parity.py tests/test_gpu_edges
 tail -2 $OUT/tests.log
 for v in HEAD closed_exact HEAD closed_exact; do
   if [ $v = HEAD ]; then unset BIOLIB_AMD_LIB; else export BIOLIB_AMD_LIB=$ROOT/biolib_amd/lib/ab/$v.so; fi
-  timeout -k 10 300 python bench.py --no-cpu-baseline --no-next-rows --no-h2d --steps 3 > $OUT/bench_$v.json 2> $OUT/bench_$v.err || { tail -5 $OUT/bench_$v.err; exit 1; }
+  timeout -k 10 300 python bench.py --full --no-cpu-baseline --no-next-rows --no-h2d --steps 3 > $OUT/bench_$v.json 2> $OUT/bench_$v.err || { tail -5 $OUT/bench_$v.err; exit 1; }
   python - <<PY
 import json
 d = json.loads(open("$OUT/bench_$v.json").read().strip().splitlines()[-1])
