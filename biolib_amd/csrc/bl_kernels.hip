@@ -227,7 +227,7 @@ __device__ __forceinline__ void count_tile(const ScanParams& p, TileShared<MODE,
 // Pass 1 of one tile in the read-tiled layout (fixed-length short reads, bl_scan_frl.hpp): same outputs as count_tile.
 // APPROX: the windows are decided on murmur64_top (bl_scan_core.hpp), 7 instructions per hash cheaper than the hash; a tile in which
 // some lane could not tell two keys apart is listed for scan_redo_frl_kernel, which runs this function without the flag.
-template <int MODE, int W, int NS, int LIM_LAST, bool GENERIC, bool APPROX = false>
+template <int MODE, int W, int NS, int LIM_LAST, bool GENERIC, bool APPROX = false, int U = 0>
 __device__ __forceinline__ void count_tile_frl(const ScanParams& p, TileShared<MODE, W>& sh, uint32_t tile, int tid)
 {
     const int64_t q0 = tile_q0(p, tile);
@@ -241,7 +241,7 @@ __device__ __forceinline__ void count_tile_frl(const ScanParams& p, TileShared<M
 
     ThreadState st;
     bool tie = false;
-    phase_hash_frl<MODE, W, NS, GENERIC, APPROX>(p, sh, tid, q0, tile, st);
+    phase_hash_frl<MODE, W, NS, GENERIC, APPROX, U>(p, sh, tid, q0, tile, st);
     phase_window_frl_a<MODE, W, NS, LIM_LAST, APPROX>(p, sh, tid, st, nullptr, &tie);
     if (APPROX && BL_COLD(wave_any(tie)) && (tid & 63) == 0) sh.redo = 1;
     const uint32_t packed = phase_window_frl_b<MODE, W, NS>(p, tid, st, nullptr);
@@ -267,7 +267,10 @@ __device__ __forceinline__ void count_tile_frl(const ScanParams& p, TileShared<M
 // footprint is the 2 KB of codes and its residency is set by launch_scan_emit's padding alone (it used to stage up to
 // three 8 KB lists per tile, which, beside a hashing kernel that needs 12 KB per workgroup, decided who got the CU).
 // LOOPED: called from scan_emit_kernel's tile loop (one barrier per tile whatever the tile holds; scheduling fences that hold the registers down)
-template <int MODE, bool LOOPED = false>
+// C3: the C3 shape (emit_c3): `codes` holds two strands, the tile's codes from codes[1] on and their reverse complement from
+// codes[C3_RC + 1] on (unit31_canonical), each behind one dword it may read and mask away.
+constexpr int C3_RC = NCHUNK + 4;
+template <int MODE, bool LOOPED = false, bool C3 = false>
 __device__ __forceinline__ void emit_tile(const ScanParams& p, uint32_t* codes, uint32_t tile, int tid, Digest& dg)
 {
     // one memory round trip for the common case: every load of the tile — counts, offsets, codes, the first 2 * TPB list entries
@@ -297,7 +300,17 @@ __device__ __forceinline__ void emit_tile(const ScanParams& p, uint32_t* codes, 
         return;
     }
     const uint64_t base_s = base & 0xffffffffull, base_e = base >> 32;
-    if (MODE != MODE_SYNCMER) {  // (syncmers: no codes, no barrier — a record is its list entry's position)
+    if (C3) {  // both strands, once per tile (the reverse complement of a chunk is 5 instructions; of a record, by pair-reversal, 13)
+        if (tid < needed) {
+            codes[1 + tid] = c0;
+            codes[C3_RC + needed - tid] = revcomp16(c0);
+        }
+        if (TPB + tid < needed) {
+            codes[1 + TPB + tid] = c1;
+            codes[C3_RC + needed - TPB - tid] = revcomp16(c1);
+        }
+        __syncthreads();
+    } else if (MODE != MODE_SYNCMER) {  // (syncmers: no codes, no barrier — a record is its list entry's position)
         if (tid < needed) codes[tid] = c0;
         if (TPB + tid < needed) codes[TPB + tid] = c1;
         __syncthreads();
@@ -306,7 +319,7 @@ __device__ __forceinline__ void emit_tile(const ScanParams& p, uint32_t* codes, 
     TileLists L{codes, la, lj, MODE == MODE_SUPERKMER ? p.slots_e + slot : nullptr, MODE == MODE_SUPERKMER ? p.slots_e + slot + p.stride : nullptr};
     const uint32_t d = (uint32_t)(base_s - base_e);  // 0 or 1 (see end_position)
     auto one = [&](uint32_t r, uint32_t ent, uint32_t ent_j) {
-        const Record rec = emit_prepare<MODE, LOOPED>(p, codes, q0, ent, ent_j, dg);
+        const Record rec = C3 ? emit_prepare_c3<LOOPED>(p, codes + 1, codes + C3_RC + 1, needed, q0, ent, dg) : emit_prepare<MODE, LOOPED>(p, codes, q0, ent, ent_j, dg);
         if (fits) emit_store<MODE, false>(p, rec, base_s + r);
         else emit_store<MODE, true>(p, rec, base_s + r);
         if (MODE == MODE_SUPERKMER && (p.out_size || p.out_records) && (fits || base_s + r < p.capacity)) {
@@ -405,7 +418,7 @@ __global__ __launch_bounds__(TPB, (W <= 11 ? BL_FRL_WAVES : 4)) void scan_count_
     const ScanParams p = frl_params<MODE, W, NS, U, L, C>(pin);
     constexpr int LIM_LAST = frl_lim_last<W, NS, U, L>();
     static_assert(L == 0 || (LIM_LAST >= 1 && LIM_LAST <= NS), "read-tiled geometry: the last lane of a read must own 1..NS windows");
-    if (blockIdx.x < g.count) count_tile_frl<MODE, W, NS, LIM_LAST, U == 0, APPROX>(p, sh, g.first + blockIdx.x, threadIdx.x);
+    if (blockIdx.x < g.count) count_tile_frl<MODE, W, NS, LIM_LAST, U == 0, APPROX, U>(p, sh, g.first + blockIdx.x, threadIdx.x);
 }
 
 // The tiles an APPROX pass 1 listed, counted again on the hashes themselves (same outputs, written over what pass 1 left for them);
@@ -417,7 +430,7 @@ __global__ __launch_bounds__(TPB, (W <= 11 ? 5 : 4)) void scan_redo_frl_kernel(c
     const ScanParams p = frl_params<MODE, W, NS, U, L, C>(pin);
     const unsigned long long n = *p.redo_count;
     for (unsigned long long i = blockIdx.x; i < n; i += gridDim.x) {
-        count_tile_frl<MODE, W, NS, frl_lim_last<W, NS, U, L>(), U == 0>(p, sh, p.redo_list[i], threadIdx.x);
+        count_tile_frl<MODE, W, NS, frl_lim_last<W, NS, U, L>(), U == 0, false, U>(p, sh, p.redo_list[i], threadIdx.x);
         __syncthreads();  // the lists in LDS have been spilled before the next tile overwrites them
     }
 }
@@ -437,11 +450,15 @@ __global__ __launch_bounds__(TPB, (W <= 11 ? 5 : 4)) void scan_redo_frl_kernel(c
 template <int MODE>
 constexpr int emit_tiles() { return MODE == MODE_MINIMIZER ? BL_EMIT_TILES : 1; }
 
+// C3 (minimizers of canonical 31-mers, read-tiled): each code buffer holds the reverse-complemented strand too (emit_tile).
+template <int MODE, int U, int C, int FRL>
+constexpr bool emit_c3() { return MODE == MODE_MINIMIZER && U == 31 && C == 1 && FRL == 1; }
 template <int MODE, int U = 0, int C = -1, int FRL = -1>
 __global__ __launch_bounds__(TPB) void scan_emit_kernel(const ScanParams pin, GroupRange g)
 {
     constexpr int K = emit_tiles<MODE>();
-    __shared__ uint32_t codes[K > 1 ? 2 : 1][NCHUNK];
+    constexpr bool C3 = emit_c3<MODE, U, C, FRL>();
+    __shared__ uint32_t codes[K > 1 ? 2 : 1][C3 ? 2 * C3_RC : NCHUNK];
     const int tid = threadIdx.x;
     ScanParams p = pin;
     if (U != 0) p.unit = U;
@@ -456,7 +473,7 @@ __global__ __launch_bounds__(TPB) void scan_emit_kernel(const ScanParams pin, Gr
 #pragma unroll 1
         for (uint32_t k = 0; k < (uint32_t)K && t0 + k < g.count; ++k) {
             Digest d1{0, 0, 0};
-            emit_tile<MODE, true>(p, codes[k & 1], g.first + t0 + k, tid, d1);
+            emit_tile<MODE, true, C3>(p, codes[k & 1], g.first + t0 + k, tid, d1);
             acc[0][tid] ^= (uint32_t)d1.xv; acc[1][tid] ^= (uint32_t)(d1.xv >> 32);
             acc[2][tid] ^= (uint32_t)d1.xh; acc[3][tid] ^= (uint32_t)(d1.xh >> 32);
             acc[4][tid] ^= (uint32_t)d1.xp; acc[5][tid] ^= (uint32_t)(d1.xp >> 32);
@@ -466,7 +483,7 @@ __global__ __launch_bounds__(TPB) void scan_emit_kernel(const ScanParams pin, Gr
         dg.xp = ((unsigned long long)acc[5][tid] << 32) | acc[4][tid];
     } else {
         if (blockIdx.x >= g.count) return;
-        emit_tile<MODE, false>(p, codes[0], g.first + blockIdx.x, tid, dg);
+        emit_tile<MODE, false, C3>(p, codes[0], g.first + blockIdx.x, tid, dg);
     }
 
     // digest: wave reduce (DPP xor-scan), then one set of atomics per WAVE into a shard line.  Measured alternatives: an LDS stage
@@ -825,8 +842,9 @@ static void launch_emit_mode(const ScanParams& p, GroupRange g, hipStream_t stre
     const uint32_t have = (uint32_t)(((K > 1 ? 2 : 1) * NCHUNK + (K > 1 ? 6 * TPB : 0)) * sizeof(uint32_t));  // the kernel's static LDS: code buffers, digest words
     const uint32_t pad = lds_per_wg > have ? lds_per_wg - have : 0;
     const dim3 grid((g.count + K - 1) / K), block(TPB);
-    if (MODE == MODE_MINIMIZER && p.frl && p.unit == 31 && p.canonical) {  // BASELINE C3
-        hipLaunchKernelGGL((scan_emit_kernel<MODE_MINIMIZER, 31, 1, 1>), grid, block, pad, stream, p, g);
+    if (MODE == MODE_MINIMIZER && p.frl && p.unit == 31 && p.canonical) {  // BASELINE C3: code buffers of two strands (emit_c3)
+        const uint32_t have_c3 = (uint32_t)(((K > 1 ? 2 : 1) * 2 * C3_RC + (K > 1 ? 6 * TPB : 0)) * sizeof(uint32_t));
+        hipLaunchKernelGGL((scan_emit_kernel<MODE_MINIMIZER, 31, 1, 1>), grid, block, lds_per_wg > have_c3 ? lds_per_wg - have_c3 : 0, stream, p, g);
         return;
     }
     hipLaunchKernelGGL((scan_emit_kernel<MODE>), grid, block, pad, stream, p, g);

@@ -309,7 +309,11 @@ BL_DEV uint32_t murmur64_top(uint64_t key, uint32_t seed)
     const uint32_t a1 = (uint32_t)h1, b1 = (uint32_t)(h1 >> 32), a2 = (uint32_t)h2, b2 = (uint32_t)(h2 >> 32);
     const uint32_t cross = (uint32_t)mad_lo(b2, clo, mad_lo(a2, chi, mad_lo(b1, clo, mad_lo0<PLUS_ONE>(a1, chi))));
 #if defined(__HIP_DEVICE_COMPILE__) && !defined(BL_CPU_EMU)
-    return __umulhi(a1, clo) + __umulhi(a2, clo) + cross;
+    // the sum as one opaque v_add3_u32: left visible, the compiler may fold `hi(a * c) + x` into a v_mad_u64_u32 with the 64-bit addend
+    // {0, x} — one v_mov more per product for the same result (it did, in the read-tiled kernel once the running maximum was gone)
+    uint32_t top;
+    asm("v_add3_u32 %0, %1, %2, %3" : "=v"(top) : "v"(__umulhi(a1, clo)), "v"(__umulhi(a2, clo)), "v"(cross));
+    return top;
 #else
     return (uint32_t)(((uint64_t)a1 * clo) >> 32) + (uint32_t)(((uint64_t)a2 * clo) >> 32) + cross;
 #endif

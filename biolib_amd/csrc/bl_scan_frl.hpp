@@ -64,9 +64,36 @@ BL_DEV void phase_load_frl(const ScanParams& p, TileShared<MODE, W>& sh, int tid
 // ------------------------------------------------------------------------------------------------
 // Phase 2: which read and which units this lane owns; roll and hash them.
 // GENERIC: run-time unit length (see phase_hash: those kernels hash with the compiler's own multiply)
-// APPROX: st.h[s] holds murmur64_top in its high dword (low dword 0) and st.hmax the largest of them: the window phase works on
-// those and reports what it cannot decide (lane_window_argmin_frl)
-template <int MODE, int W, int NS, bool GENERIC = false, bool APPROX = false>
+// APPROX: st.h[s] holds murmur64_top<true> (S + 1) in its high dword (low dword 0): the window phase works on those and reports what it
+// cannot decide (lane_window_argmin_frl)
+
+// The 64 bits of codes that END at base e (0 <= e < 48) of the 48 bases a0:a1:a2 (first base in the top pair of a0): bases e - 31 .. e,
+// the last one in the low pair.  Bases before 0 read as zeros.  Ending rather than starting at a base keeps every shift of v_alignbit_b32
+// inside 0..30 (a 64-bit window that starts on a word boundary would need a shift of 32, which the instruction takes modulo 32).
+BL_DEV uint64_t bases_ending_at(uint32_t a0, uint32_t a1, uint32_t a2, int e)
+{
+    const int q = e >> 4, sh = 30 - 2 * (e & 15);
+    const uint32_t w[3] = {a0, a1, a2};
+    const uint32_t lo = sh == 0 ? w[q] : (q == 0 ? w[0] >> sh : funnel_shr(w[q - 1], w[q], sh));
+    const uint32_t hi = q == 0 ? 0u : (sh == 0 ? w[q - 1] : (q == 1 ? w[0] >> sh : funnel_shr(w[q - 2], w[q - 1], sh)));
+    return ((uint64_t)hi << 32) | lo;
+}
+
+// Units of length U (16 < U <= 32, a compile-time constant) by direct extraction: unit s is the U bases that end at base s + U - 1 of
+// the lane's 48, its reverse complement the U bases that end at base 47 - s of their reverse complement (three revcomp16 per lane, for
+// NS units): two v_alignbit_b32 and a mask per strand, where the rolling registers (Roller) cost 8 instructions per unit.
+template <int U>
+BL_DEV void units_direct(uint32_t a0, uint32_t a1, uint32_t a2, uint32_t r0, uint32_t r1, uint32_t r2, int s, uint64_t& fw, uint64_t& rv)
+{
+    static_assert(U > 16 && U <= 32, "direct extraction: 16 < U <= 32");
+    constexpr uint64_t M = U == 32 ? ~0ull : (1ull << (2 * U)) - 1;
+    fw = bases_ending_at(a0, a1, a2, s + U - 1) & M;
+    rv = bases_ending_at(r0, r1, r2, 47 - s) & M;
+}
+
+// U: the unit length where the kernel fixes it (0: from p.unit).  31 (the C3 shape) with NS <= 17 takes the units by direct
+// extraction (units_direct); every other length keeps the rolling registers.  In the CPU emulation U is 0 and p.unit decides.
+template <int MODE, int W, int NS, bool GENERIC = false, bool APPROX = false, int U = 0>
 BL_DEV void phase_hash_frl(const ScanParams& p, TileShared<MODE, W>& sh, int tid, int64_t q0, uint32_t tile, ThreadState& st)
 {
     const int wv = wave_index(tid), lane = tid & 63;
@@ -85,23 +112,28 @@ BL_DEV void phase_hash_frl(const ScanParams& p, TileShared<MODE, W>& sh, int tid
     const uint32_t a0 = (uint32_t)(((((uint64_t)c0 << 32) | c1) << sh2) >> 32);
     const uint32_t a1 = (uint32_t)(((((uint64_t)c1 << 32) | c2) << sh2) >> 32);
     const uint32_t a2 = (uint32_t)(((((uint64_t)c2 << 32) | c3) << sh2) >> 32);
+    constexpr bool DIRECT_OK = !GENERIC && (U == 0 || U == 31) && NS + 31 - 1 <= 47;
+    if (DIRECT_OK && (U == 31 || p.unit == 31)) {
+        const uint32_t r0 = revcomp16(a2), r1 = revcomp16(a1), r2 = revcomp16(a0);
+        BL_UNROLL
+        for (int s = 0; s < NS; ++s) {
+            uint64_t fw, rv;
+            units_direct<31>(a0, a1, a2, r0, r1, r2, s, fw, rv);
+            const uint64_t v = (p.canonical && rv < fw) ? rv : fw;  // minimizer_view.hpp:236-238
+            st.h[s] = APPROX ? (uint64_t)murmur64_top<true>(v, p.seed) << 32 : murmur64(v, p.seed);
+        }
+        return;
+    }
     Roller rr;
     roller_start(rr, a0, a1, a2, p.unit);
-    uint32_t hmax = 0;
     BL_UNROLL
     for (int s = 0; s < NS; ++s) {
         roller_step(rr, s);
         const uint64_t fw = roller_fwd(rr), rv = roller_rc(rr);
         const uint64_t v = (p.canonical && rv < fw) ? rv : fw;  // minimizer_view.hpp:236-238
-        if (APPROX) {
-            const uint32_t top = murmur64_top(v, p.seed);
-            hmax = top > hmax ? top : hmax;
-            st.h[s] = (uint64_t)top << 32;
-        } else {
-            st.h[s] = GENERIC ? murmur64_plain(v, p.seed) : murmur64(v, p.seed);
-        }
+        if (APPROX) st.h[s] = (uint64_t)murmur64_top<true>(v, p.seed) << 32;
+        else st.h[s] = GENERIC ? murmur64_plain(v, p.seed) : murmur64(v, p.seed);
     }
-    st.hmax = hmax;
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -112,12 +144,21 @@ BL_DEV uint32_t dpp_next32(uint32_t v) { return (uint32_t)__builtin_amdgcn_updat
 // the same as a rotation: lane 63 reads lane 0 (wave_rol:1)
 BL_DEV uint32_t dpp_next32_rot(uint32_t v) { return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x134, 0xf, 0xf, true); }
 BL_DEV uint32_t dpp_prev32(uint32_t v) { return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x138, 0xf, 0xf, true); }  // wave_shr:1
+// dpp_next32_rot(v) + k as ONE v_add_u32_dpp (the builtin and an add compile to v_mov_b32_dpp + v_add_u32).  A DPP operand written by the
+// VALU instruction just before needs two wait states, and the assembler does not look inside the asm: hence the s_nop.
+BL_DEV uint32_t dpp_next32_rot_add(uint32_t v, uint32_t k)
+{
+    uint32_t d;
+    asm("s_nop 1\n\tv_add_u32_dpp %0, %1, %2 wave_rol:1 row_mask:0xf bank_mask:0xf" : "=v"(d) : "v"(v), "v"(k));
+    return d;
+}
 #endif
 
 // Window argmins of a lane that owns NS elements: the W - 1 halo elements come from the following lanes, NS per hop.
 // a[i] = raw packed key (element index in its low 6 bits) or, after the exact branch, the plain element index.
-// APPROX (keys from murmur64_top): no exact form in here; *tie is set when a lane that owns windows met two keys less than two
-// prefixes apart, or holds a key whose prefix could wrap, and the caller has the whole tile decided again (scan_redo_frl_kernel)
+// APPROX (keys from murmur64_top<true>): no exact form in here; *tie is set when a lane that owns windows met two keys less than two
+// prefixes apart, or one of its windows has its minimum at prefix 0 (a key that may have wrapped), and the caller has the whole tile
+// decided again (scan_redo_frl_kernel)
 template <int NS, int W, bool APPROX = false>
 BL_DEV void lane_window_argmin_frl(const ThreadState* all, int tid, const ThreadState& st, bool owns, uint32_t* a, bool* tie = nullptr)
 {
@@ -128,7 +169,11 @@ BL_DEV void lane_window_argmin_frl(const ThreadState* all, int tid, const Thread
 #if defined(__HIP_DEVICE_COMPILE__) && !defined(BL_CPU_EMU)
     (void)all;
     (void)tid;
-    {
+    if constexpr (APPROX && NE <= NS) {  // one hop: the halo is the next lane's first W - 1 keys, their tags moved on by NS in the same instruction
+        const uint32_t ns = (uint32_t)NS;
+        BL_UNROLL
+        for (int x = 0; x < NE; ++x) key[NS + x] = dpp_next32_rot_add(key[x], ns);
+    } else {
         uint32_t cur[NS];
         BL_UNROLL
         for (int x = 0; x < NS; ++x) cur[x] = key[x];
@@ -158,8 +203,18 @@ BL_DEV void lane_window_argmin_frl(const ThreadState* all, int tid, const Thread
 #endif
     const uint32_t dmin = window_argmin_packed<NS, W, true, true, APPROX>(key, a);
     if (APPROX) {
-        // (a lane's keys: its own NS elements and the W - 1 that follow; the lanes those belong to test their own hmax)
-        if (owns && (dmin < 128u || st.hmax >= 0xffffffc0u)) *tie = true;
+        // The keys hold S' = murmur64_top<true> = S + 1, and the hash's high dword T is S' or S' - 1.  Without a wrap, prefixes two or more
+        // apart order keys like their hashes (dmin, above).  The one value that can wrap is S' = 0 (T = 0xffffffff): such a key looks like
+        // the smallest there is while its hash is the largest.  It can only mislead a window it is the minimum of: a window that holds a
+        // key of prefix 0 has a minimum of prefix 0 (nothing packs below it), be it that key or another one.  So a tile is decided again
+        // when some window a lane owns has its minimum at prefix 0, and every window that holds a wrapped key is among those.  One
+        // v_min3_u32 finds the smallest minimum of the lane's windows: windows 0, W, 2W, ... and NS - 1 cover all of its keys.  (With
+        // murmur64_top itself the value that can wrap is the LARGEST, which may sit in any window: that took a running maximum of every
+        // hash, 15 v_max_u32 per lane.)
+        uint32_t amin = a[NS - 1];
+        BL_UNROLL
+        for (int s = 0; s < NS - 1; s += W) amin = a[s] < amin ? a[s] : amin;
+        if (owns && (dmin < 128u || amin < 64u)) *tie = true;
         return;
     }
     if (BL_COLD(wave_any(owns && dmin < 64u))) {  // a prefix tie somewhere in the wave: the exact 64-bit form

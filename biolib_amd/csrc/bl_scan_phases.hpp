@@ -1262,6 +1262,41 @@ BL_DEV Record emit_prepare(const ScanParams& p, const uint32_t* codes, int64_t q
     return rec;
 }
 
+// The canonical 31-mer at tile-relative base `pos` from the tile's codes AND their reverse complement, both staged in LDS by pass 2
+// (scan_emit_kernel's C3 form): cf[c] = chunk c, cr[c] = revcomp16(chunk nc - 1 - c), so base i of cr is the complement of base
+// 16 nc - 1 - i of cf.  Each strand is the 64 bits that END at its last base — two v_alignbit_b32 over three dwords, whose shift
+// (30 - 2 * (e & 15), taken modulo 32 by the instruction) never needs to be 32 — and a mask of the top pair; one 64-bit compare and
+// two selects pick the canonical one.  extract_unit builds the reverse complement of every record by pair-reversal instead.
+// cf[-1] and cr[-1] must be readable: a unit that ends in chunk 1 takes (and masks away) up to two bits of the dword in front.
+// FENCED: the forward strand is complete before the reverse one is read (pass 2's looped form lives on 28 registers)
+template <bool FENCED = false>
+BL_DEV uint64_t unit31_canonical(const uint32_t* cf, const uint32_t* cr, int nc, int pos)
+{
+    const int qf = (pos + 30) >> 4, qr = nc - 1 - (pos >> 4);  // the dword holding the strand's last base
+    const int shf = 2 - 2 * pos, shr = 2 * pos;                // = 30 - 2 * (last base & 15), modulo 32
+    const uint32_t flo = funnel_shr(cf[qf - 1], cf[qf], shf & 31), fhi = funnel_shr(cf[qf - 2], cf[qf - 1], shf & 31) & 0x3fffffffu;
+    if (FENCED) BL_SCHED_FENCE();
+    const uint32_t rlo = funnel_shr(cr[qr - 1], cr[qr], shr & 31), rhi = funnel_shr(cr[qr - 2], cr[qr - 1], shr & 31) & 0x3fffffffu;
+    const uint64_t fw = ((uint64_t)fhi << 32) | flo, rv = ((uint64_t)rhi << 32) | rlo;
+    return rv < fw ? rv : fw;  // numeric min, kmer_view.hpp:196
+}
+
+// 5a for the C3 shape (minimizers, 31-mers, canonical, read-tiled): the unit from both staged strands (unit31_canonical)
+template <bool FENCED = false>
+BL_DEV Record emit_prepare_c3(const ScanParams& p, const uint32_t* cf, const uint32_t* cr, int nc, int64_t q0, uint32_t ent, Digest& dg)
+{
+    Record rec{0, 0, 0, 0, 0};
+    rec.pos = (uint64_t)(q0 + (int)ent);
+    dg.xp ^= rec.pos + (uint64_t)p.pos_base;
+    rec.v = unit31_canonical<FENCED>(cf, cr, nc, (int)ent);
+    if (FENCED) BL_SCHED_FENCE();
+    rec.h = murmur64(rec.v, p.seed);
+    if (FENCED) BL_SCHED_FENCE();
+    dg.xv ^= rec.v;
+    dg.xh ^= rec.h;
+    return rec;
+}
+
 // 5b: coalesced stores (thread r writes record r).  Records are written once and not read again by
 // the scan: non-temporal stores keep them from displacing the tile data in L2.
 template <typename T>
