@@ -56,7 +56,7 @@ struct __attribute__((packed)) Unaligned8 {
 __device__ __forceinline__ unsigned long long codes8(const unsigned char* __restrict__ bases, unsigned long long at, unsigned long long n_bases)
 {
     unsigned long long w = 0;
-    if (at + 8 <= n_bases) {
+    if (n_bases >= 8 && at <= n_bases - 8) {  // (not `at + 8 <= n_bases`: a wrapped `at` must not pass)
         w = reinterpret_cast<const Unaligned8*>(bases + at)->v;
     } else {  // the last bytes of the batch (a borrowed buffer has nothing behind them that may be read)
         for (int i = 0; i < 8; ++i)
@@ -78,11 +78,13 @@ __global__ __launch_bounds__(256) void pack_kernel(const unsigned char* __restri
     const unsigned long long g = (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (g >= n) return;
     // the scan reported origin + the position inside the batch (bl_batch_set_origin); a position in front of the origin wraps to a
-    // huge value and takes the "beyond the batch" exit below
+    // huge value and takes the "beyond the batch" exit below.  Neither guard adds to p: p + nb would wrap back into the batch for
+    // a position 1..nb bases in front of the origin
     const unsigned long long p = first_pos[g] - origin;
     const int size = sizes[g];
     int nb = size + k - 1;
-    if (p + (unsigned long long)nb > n_bases) nb = p < n_bases ? (int)(n_bases - p) : 0;  // never read past the batch (a caller error; the record is then short)
+    if (p >= n_bases) nb = 0;  // nothing of the batch: an empty record (base bits zero)
+    else if ((unsigned long long)nb > n_bases - p) nb = (int)(n_bases - p);  // never read past the batch (a caller error; the record is then short)
     unsigned long long hi = 0, lo = 0;
 #pragma unroll
     for (int j = 0; j < 4; ++j)

@@ -290,7 +290,11 @@ int bl_count_allreduce(bl_ctx* const* ctxs, int n_gpu, uint64_t* counters, int n
  *   size + k - 1 bases (2 bits each, first base most significant), d_records[2g+1] = bases 32.. in bits 63..10, mm_pos in
  *   bits 9..5 (d_mm_pos is REQUIRED: bl_count_super_kmers finds a record's minimizer through it), size - 1 in bits 4..0.
  *   Needs 2k - m <= 59.  d_first_pos holds what the scan of THIS batch reported: positions in the caller's whole when the batch
- *   has an origin (bl_batch_set_origin); a position in front of the origin or beyond the batch packs an empty record.
+ *   has an origin (bl_batch_set_origin).  A position outside the batch — in front of the origin (by any distance: the difference
+ *   is never added to), or at or behind origin + n_bases — packs an EMPTY record: all base bits zero (d_records[2g] == 0 and
+ *   bits 63..10 of d_records[2g+1] == 0), while mm_pos and size - 1 in bits 9..0 are kept as given.  A group that starts inside
+ *   the batch and runs over its end packs the bases up to the end; those behind it are code 0, bits 9..0 again as given (the
+ *   record still claims `size` k-mers).  Neither case reads a byte in front of or behind the batch's n_bases bases.
  * bl_partition_records: reorder 16-byte records into `parts` (<= 64) contiguous buckets by d_hashes[g] % parts (the
  *   minimizer hash the scan returned = the owner rank); counts[b] (host) = records in bucket b.
  * bl_expand_super_kmers: records -> their k-mers (canonical with BL_FLAG_CANONICAL), group after group;

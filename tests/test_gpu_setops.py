@@ -7,6 +7,7 @@ import numpy as np
 import pytest
 
 import oracle_lib as O
+from superkmer_model import pack as _np_pack
 
 pytestmark = pytest.mark.gpu
 HERE = os.path.dirname(os.path.abspath(__file__))
@@ -177,25 +178,6 @@ def _sorted_counts(u, c):
     c = c.cpu().numpy().astype(np.int64)
     order = np.argsort(u, kind="stable")
     return u[order], c[order]
-
-
-def _np_pack(seq, fp, sz, k, mp=None):
-    """numpy restatement of the 16-byte packed super-k-mer record"""
-    code = np.zeros(256, np.uint64)
-    for ch, c in zip(b"ACGTUacgtu", (0, 1, 2, 3, 3, 0, 1, 2, 3, 3)):
-        code[ch] = c
-    out = np.zeros((len(fp), 2), np.uint64)
-    for g, (p, s) in enumerate(zip(fp.tolist(), sz.tolist())):
-        nb = s + k - 1
-        c = code[seq[p:p + nb]]
-        hi = 0
-        for i in range(min(nb, 32)):
-            hi |= int(c[i]) << (62 - 2 * i)
-        lo = (s - 1) | ((int(mp[g]) if mp is not None else 0) << 5)
-        for i in range(32, nb):
-            lo |= int(c[i]) << (62 - 2 * (i - 32))
-        out[g] = (hi, lo)
-    return out
 
 
 @pytest.mark.parametrize("k,m,canon", [(31, 15, True), (31, 15, False), (32, 5, True), (21, 11, True), (5, 5, True), (16, 1, False)])
