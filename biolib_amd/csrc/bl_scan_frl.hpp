@@ -196,7 +196,7 @@ BL_DEV void lane_window_argmin_frl(const ThreadState* all, int tid, const Thread
         const int lane = tid & 63;
         for (int x = 0; x < NE; ++x) {
             const int nb = lane + 1 + x / NS;
-            const uint32_t hi = nb < 64 ? (uint32_t)(all[tid + 1 + x / NS].h[x % NS] >> 32) : (0x03fffff0u - 2u * (uint32_t)x) << 6;  // pads, two prefixes apart
+            const uint32_t hi = nb < 64 ? (uint32_t)(all[tid + 1 + x / NS].h[x % NS] >> 32) : (0x03fffff0u - 4u * (uint32_t)x) << 6;  // pads, four prefixes apart: no tie among themselves, on hashes (< 64) or on murmur64_top (< 128, tags included)
             key[NS + x] = packed_key(hi, NS + x, true);
         }
     }

@@ -407,6 +407,21 @@ void emu_top_check(const uint64_t* keys, uint64_t n, uint32_t seed, uint64_t* ba
         if (t - s == 1u) ++*below;
     }
 }
+// the same for murmur64_top<true> (S + 1): how many are neither T nor T + 1 (must be 0), how many are T + 1
+void emu_top_check_plus_one(const uint64_t* keys, uint64_t n, uint32_t seed, uint64_t* bad, uint64_t* above)
+{
+    *bad = *above = 0;
+    for (uint64_t i = 0; i < n; ++i) {
+        const uint32_t t = (uint32_t)(murmur64(keys[i], seed) >> 32), s = murmur64_top<true>(keys[i], seed);
+        if (s - t > 1u) ++*bad;
+        if (s - t == 1u) ++*above;
+    }
+}
+// the dwords themselves, for tests/hash_top_model.py
+void emu_top_values(const uint64_t* keys, uint64_t n, uint32_t seed, int plus_one, uint32_t* out)
+{
+    for (uint64_t i = 0; i < n; ++i) out[i] = plus_one ? murmur64_top<true>(keys[i], seed) : murmur64_top<false>(keys[i], seed);
+}
 int emu_frl_scans() { return g_frl_scans; }
 int emu_frl_redone() { return g_frl_redone; }
 int emu_closed_redone() { return g_closed_redone; }
