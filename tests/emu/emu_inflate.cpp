@@ -78,7 +78,7 @@ int failures = 0;
 void expect(bool ok, const char* what, size_t id)
 {
     if (!ok) {
-        std::printf("FAIL %s (case %zu)\n", what, id);
+        if (failures < 100) std::printf("FAIL %s (case %zu)\n", what, id);  // (a broken decoder fails everywhere: the counts say the rest)
         ++failures;
     }
 }
@@ -155,8 +155,66 @@ static std::vector<uint8_t> read_file(const char* path)
     return v;
 }
 
+// emu_inflate --corpus FILE [FIRST STEP]: the hand-built streams of tests/inflate_corpus.py (a file written by its write_corpus_file:
+// "BLINFLC1", then per record six little-endian dwords — bytes of data, stated text size, 1 = designed sound, expected status or 0,
+// bytes of text, class — the data and the text).  Every record FIRST, FIRST + STEP, ... runs at the destination misalignments 0..15;
+// its status, its text and the bytes around its text are checked, and the design's verdict against zlib's.
+static int run_corpus(const char* path, size_t first, size_t step)
+{
+    const auto file = read_file(path);
+    if (file.size() < 8 || std::memcmp(file.data(), "BLINFLC1", 8) != 0) {
+        std::printf("emu_inflate: %s is no corpus file\n", path);
+        return 2;
+    }
+    size_t at = 8, id = 0, run = 0, n_sound = 0, n_unsound = 0;
+    size_t class_records[16] = {0}, class_failed[16] = {0};
+    while (at < file.size()) {
+        if (file.size() - at < 24) return 2;
+        uint32_t h[6];
+        std::memcpy(h, file.data() + at, 24);
+        at += 24;
+        const uint32_t n_data = h[0], isize = h[1], sound = h[2], want_status = h[3], n_text = h[4];
+        if (file.size() - at < (size_t)n_data + n_text || isize > 65536 || (sound && n_text != isize)) return 2;
+        if (id % step == first) {
+            const int failures_before = failures;
+            const std::vector<uint8_t> packed(file.begin() + at, file.begin() + at + n_data), text(file.begin() + at + n_data, file.begin() + at + n_data + n_text);
+            std::vector<uint8_t> ztext;
+            const bool zok = zlib_inflate(packed, isize, ztext);
+            expect(zok == (sound != 0), "zlib's verdict is not the design's", id);
+            if (zok && sound) expect(ztext == text, "zlib's text is not the model's", id);
+            for (unsigned misalign = 0; misalign < 16; ++misalign) {
+                const Result r = ours(packed, isize, misalign);
+                expect(!r.wrote_outside, "wrote outside the member's text", id);
+                if (sound) {
+                    expect(r.status == bl_inflate::OK, "sound stream refused", id);
+                    expect(r.text == text, "text differs", id);
+                } else {
+                    expect(r.status != bl_inflate::OK, "unsound stream accepted", id);
+                    if (want_status) expect(r.status == want_status, "refused with another status than the cause's", id);
+                }
+            }
+            ++run;
+            ++(sound ? n_sound : n_unsound);
+            ++class_records[h[5] & 15u];
+            class_failed[h[5] & 15u] += failures > failures_before;
+        }
+        at += (size_t)n_data + n_text;
+        ++id;
+    }
+    for (int c = 0; c < 16; ++c)
+        if (class_records[c]) std::printf("emu_inflate: class %d: %zu records, %zu failed\n", c, class_records[c], class_failed[c]);
+    std::printf("emu_inflate: corpus records %zu of %zu (%zu sound, %zu unsound) at 16 misalignments, %d failures\n", run, id, n_sound, n_unsound, failures);
+    if (failures == 0) std::printf("emu_inflate: OK\n");
+    return failures ? 1 : 0;
+}
+
 int main(int argc, char** argv)
 {
+    if ((argc == 3 || argc == 5) && std::string(argv[1]) == "--corpus") {
+        const size_t first = argc == 5 ? std::strtoul(argv[3], nullptr, 10) : 0, step = argc == 5 ? std::strtoul(argv[4], nullptr, 10) : 1;
+        if (step == 0 || first >= step) return 2;
+        return run_corpus(argv[2], first, step);
+    }
     // emu_inflate --check RAW_DEFLATE_FILE TEXT_FILE: streams from encoders other than zlib (tests/test_inflate.py feeds it what GNU
     // gzip wrote); the text is at most 64 KiB, as in a BGZF member
     if (argc == 4 && std::string(argv[1]) == "--check") {
