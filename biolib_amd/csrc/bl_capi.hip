@@ -15,6 +15,7 @@
 
 #include "../../include/biolib_amd.h"
 #include "bl_launch.hpp"
+#include "bl_kmers128_launch.hpp"
 
 namespace {
 
@@ -888,6 +889,110 @@ int bl_scan_kmers(bl_ctx* c, const bl_batch* b, uint64_t first, uint64_t n, uint
     if (rc != BL_OK) return rc;
     return end_scan(c, /*add_mask: count, sum*/ (1u << 0) | (1u << 3), result, false, 0, flags);
 }
+
+// ---- 128-bit k-mers (k <= 64): bl_kmers128.hip
+
+static int prepare_kmers128(bl_ctx* c, const bl_batch* b, uint64_t first, uint64_t n, uint32_t k, uint64_t seed, uint32_t flags, const uint64_t* d_values,
+                            bl::Kmer128Params& p, bl_result* result, bool& empty)
+{
+    empty = false;
+    if (!c || !b || b->ctx != c) return fail(BL_ERR_INVALID, "ctx/batch is NULL or the batch belongs to another context");
+    if (k < 1 || k > bl::MAX_UNIT128) return fail(BL_ERR_INVALID, "k must be in [1, 64] (KmerType = __uint128_t)");
+    if (reinterpret_cast<uintptr_t>(d_values) % 16 != 0) return fail(BL_ERR_INVALID, "d_values must be 16-byte aligned (one __uint128_t per record)");
+    uint64_t end;
+    int rc = check_range(b, first, n, end);
+    if (rc != BL_OK) return rc;
+    if (end <= first) {
+        empty = true;
+        return zero_result(c, result, flags);
+    }
+    rc = ensure_start_bits(c, b);
+    if (rc != BL_OK) return rc;
+    p.bases = b->bases;
+    p.n_bases = (int64_t)b->n_bases;
+    p.start_bits = b->start_bits;
+    p.pos_base = (int64_t)b->origin;
+    bl::plan_kmers128((int64_t)first, (int64_t)end, p);
+    p.unit = (int32_t)k;
+    p.seed = (uint32_t)seed;  // hash.hpp:16,50: the seed is truncated to 32 bits
+    p.canonical = (flags & BL_FLAG_CANONICAL) ? 1 : 0;
+    p.drop_last = (flags & BL_FLAG_DROP_LAST) ? 1 : 0;
+    return BL_OK;
+}
+
+int bl_scan_kmers128(bl_ctx* c, const bl_batch* b, uint64_t first, uint64_t n, uint32_t k, uint64_t seed, uint32_t flags,
+                     uint64_t* d_values, uint64_t* d_hashes, uint8_t* d_valid, bl_result* result)
+{
+    bl::Kmer128Params p{};
+    bool empty;
+    int rc = prepare_kmers128(c, b, first, n, k, seed, flags, d_values, p, result, empty);
+    if (rc != BL_OK || empty) return rc;
+    p.out_value = d_values;
+    p.out_hash = d_hashes;
+    p.out_valid = d_valid;
+    rc = begin_scan(c);
+    if (rc != BL_OK) return rc;
+    p.shards = c->shards();
+    rc = kernel_event(c, true);
+    if (rc != BL_OK) return rc;
+    hipError_t e = bl::launch_kmers128(p, c->stream);
+    if (e != hipSuccess) return fail(BL_ERR_HIP, std::string("kmer128_kernel: ") + hipGetErrorString(e));
+    rc = kernel_event(c, false);
+    if (rc != BL_OK) return rc;
+    return end_scan(c, /*add_mask: count, sum*/ (1u << 0) | (1u << 3), result, false, 0, flags);
+}
+
+int bl_scan_hash_sample128(bl_ctx* c, const bl_batch* b, uint64_t first, uint64_t n, uint32_t k, uint64_t seed, uint64_t threshold, uint32_t flags,
+                           uint64_t* d_values, uint64_t* d_positions, uint64_t* d_hashes, uint64_t capacity, bl_result* result)
+{
+    bl::Kmer128Params p{};
+    bool empty;
+    int rc = prepare_kmers128(c, b, first, n, k, seed, flags, d_values, p, result, empty);
+    if (rc != BL_OK || empty) return rc;
+    const bool wants = d_values || d_positions || d_hashes;
+    p.hash_below = threshold;
+    p.rec_value = d_values;
+    p.rec_pos = d_positions;
+    p.rec_hash = d_hashes;
+    p.capacity = wants ? capacity : 0;
+    rc = begin_scan(c);
+    if (rc != BL_OK) return rc;
+    // scratch: tile counts + local prefixes + scan-block totals / prefixes, and one u16 record mask per lane of every tile
+    const size_t nt = (size_t)p.n_tiles, nb = (nt + bl::SCAN_BLK - 1) / bl::SCAN_BLK;
+    rc = grow(c, reinterpret_cast<void**>(&c->cur->tile_buf), &c->cur->tile_buf_bytes, (2 * nt + 2 * nb + 8) * sizeof(unsigned long long));
+    if (rc != BL_OK) return rc;
+    rc = grow(c, reinterpret_cast<void**>(&c->cur->slot_buf), &c->cur->slot_buf_bytes, nt * bl::TPB * sizeof(uint16_t));
+    if (rc != BL_OK) return rc;
+    unsigned long long* tb = reinterpret_cast<unsigned long long*>(c->cur->tile_buf);
+    p.tile_counts = tb;
+    p.tile_base = tb + nt;
+    unsigned long long* block_tot = tb + 2 * nt;
+    p.block_base = block_tot + nb;
+    p.lane_masks = c->cur->slot_buf;
+    p.shards = c->shards();
+    rc = kernel_event(c, true);
+    if (rc != BL_OK) return rc;
+    hipError_t e = bl::launch_kmers128_count(p, c->stream);
+    if (e != hipSuccess) return fail(BL_ERR_HIP, std::string("kmer128_count_kernel: ") + hipGetErrorString(e));
+    rc = kernel_event(c, false);
+    if (rc != BL_OK) return rc;
+    // the prefix scan of the window scans: it reads these four fields, and adds the total to the digest's count
+    bl::ScanParams sp{};
+    sp.tile_counts = p.tile_counts;
+    sp.tile_base = p.tile_base;
+    sp.block_base = p.block_base;
+    sp.shards = p.shards;
+    unsigned long long* carry = reinterpret_cast<unsigned long long*>(c->cur->ws);  // header word, zeroed by begin_scan
+    e = bl::launch_tile_scan(sp, bl::GroupRange{0, (uint32_t)p.n_tiles}, block_tot, carry, c->stream);
+    if (e != hipSuccess) return fail(BL_ERR_HIP, std::string("tile_scan: ") + hipGetErrorString(e));
+    if (wants) {
+        e = bl::launch_kmers128_emit(p, c->stream);
+        if (e != hipSuccess) return fail(BL_ERR_HIP, std::string("kmer128_emit_kernel: ") + hipGetErrorString(e));
+    }
+    return end_scan(c, 1u << 0, result, wants, capacity, flags);
+}
+
+uint64_t bl_hash64_u128(uint64_t lo, uint64_t hi, uint64_t seed) { return bl::murmur64_u128(lo, hi, (uint32_t)seed); }
 
 static int scan_windows(int mode, bl_ctx* c, const bl_batch* b, uint64_t first, uint64_t n, uint32_t unit, uint32_t w, uint64_t seed,
                         uint32_t flags, bl::ScanParams& p, uint64_t capacity, bl_result* result)

@@ -17,6 +17,12 @@ def hash64(value, seed=0):
     return int(capi.lib().bl_hash64_u64(int(value) & (2**64 - 1), int(seed) & (2**64 - 1)))
 
 
+def hash64_u128(lo, hi, seed=0):
+    """hash::hash64::hash<__uint128_t>(hi << 64 | lo, seed): the hash of the 128-bit k-mer scans (16 key bytes), bit-exact, on the host."""
+    m = 2**64 - 1
+    return int(capi.lib().bl_hash64_u128(int(lo) & m, int(hi) & m, int(seed) & m))
+
+
 def _flags(canonical=False, drop_last=False, sync=False):
     return (FLAG_CANONICAL if canonical else 0) | (FLAG_DROP_LAST if drop_last else 0) | (FLAG_SYNC if sync else 0)
 
@@ -409,6 +415,20 @@ class Batch:
                                             capacity, C.byref(result)))
         return result
 
+    def kmers128_raw(self, k, seed, flags, first=0, n=0, values=None, hashes=None, valid=None, result=None):
+        """bl_scan_kmers128 (k <= 64): `values` holds two words per position, low then high"""
+        result = result if result is not None else Result()
+        self.ctx._hold(result, flags)
+        check(self._lib.bl_scan_kmers128(self.ctx._h, self._h, first, n, k, seed, flags, _ptr(values), _ptr(hashes), _ptr(valid), C.byref(result)))
+        return result
+
+    def hash_sample128_raw(self, k, seed, threshold, flags, first=0, n=0, values=None, positions=None, hashes=None, capacity=0, result=None):
+        result = result if result is not None else Result()
+        self.ctx._hold(result, flags)
+        check(self._lib.bl_scan_hash_sample128(self.ctx._h, self._h, first, n, k, seed, threshold, flags, _ptr(values), _ptr(positions), _ptr(hashes),
+                                               capacity, C.byref(result)))
+        return result
+
     def super_kmers_raw(self, k, m, seed, flags, first=0, n=0, minimizers=None, first_pos=None, mm_pos=None, sizes=None, hashes=None,
                         capacity=0, result=None):
         result = result if result is not None else Result()
@@ -440,6 +460,51 @@ class Batch:
         if arrays:
             out.update(values=_host_u64(v, span), hashes=_host_u64(h, span), valid=ok[:span].cpu().numpy().copy())
         return out
+
+    def kmers128(self, k, seed=0, canonical=False, drop_last=False, first=0, n=0, arrays=True):
+        """k-mers up to k = 64 (kmer_view<__uint128_t>): values has shape (n, 2), uint64 — column 0 the low word, column 1 the high word;
+        hashes are hash64_u128(lo, hi, seed).  xor_value / aux: XOR of the low / high words."""
+        import torch
+
+        span = self._span(first, n)
+        c = self.ctx
+        v = torch.empty((max(span, 1), 2), dtype=torch.int64, device=c.torch_device) if arrays else None
+        h = c.empty_u64(span) if arrays else None
+        ok = c.empty_u8(span) if arrays else None
+        r = self.kmers128_raw(k, seed, _flags(canonical, drop_last, True), first, n, v, h, ok)
+        out = r.as_dict()
+        out["sum_hash"] = out.pop("xor_pos")
+        if arrays:
+            out.update(values=v[:span].cpu().numpy().view(np.uint64).copy(), hashes=_host_u64(h, span), valid=ok[:span].cpu().numpy().copy())
+        return out
+
+    def hash_sample128(self, k, seed=0, threshold=2**64 - 1, canonical=False, drop_last=False, first=0, n=0, capacity=None, device=False):
+        """k-mers up to k = 64 with hash64_u128(value, seed) < threshold, in position order; values has shape (count, 2) as in kmers128.
+        Run again with the count the scan reports when `capacity` (default: the expected number of records) was too small.
+        device=True keeps the hash tensor on the GPU (keys for sort_unique / jaccard)."""
+        import torch
+
+        span = self._span(first, n)
+        guess = capacity if capacity is not None else int(span * min(1.0, (threshold + 1) / 2**64) * 1.1) + 4096
+        c = self.ctx
+
+        def run(cap):
+            v = torch.empty((cap, 2), dtype=torch.int64, device=c.torch_device)
+            p, h = c.empty_u64(cap), c.empty_u64(cap)
+            r = Result()
+            try:
+                self.hash_sample128_raw(k, seed, threshold, _flags(canonical, drop_last, True), first, n, v, p, h, cap, r)
+            finally:
+                self._last_count = r.count
+            cnt = int(r.count)
+            out = r.as_dict()
+            if device:
+                out.update(hashes_device=h, n=cnt)
+            else:
+                out.update(values=v[:cnt].cpu().numpy().view(np.uint64).copy(), positions=_host_u64(p, cnt), hashes=_host_u64(h, cnt))
+            return out
+
+        return self._with_capacity(guess, run)
 
     def _with_capacity(self, guess, run):
         cap = max(int(guess), 64)

@@ -7,6 +7,9 @@
  *
  *   bl_scan_kmers        wrapper::kmer_view<uint64_t,It>                  include/kmer_view.hpp:25-83 and 162-234
  *                        + hash::hash64::hash(value, seed)                include/hash.hpp:50-59
+ *   bl_scan_kmers128     wrapper::kmer_view<__uint128_t,It>               the same template on the reference's 128-bit KmerType, k <= 64
+ *                        + hash::hash64::hash<__uint128_t>(value, seed)   include/hash.hpp:55-59 (16 key bytes)
+ *   bl_scan_hash_sample128  sampler::hash_sampler over that view          include/hash_sampler.hpp:73-78,136-141
  *   bl_scan_minimizers   wrapper::minimizer_view<K,M,hash64,It>           include/minimizer_view.hpp:14-98 (intended semantics)
  *                        sampler::minimizer_sampler<It,Hash>              include/minimizer_sampler.hpp:12-70
  *   bl_scan_super_kmers  wrapper::super_kmer_view<K,M,hash64>             include/super_kmer_view.hpp:11-58, 121-135
@@ -14,6 +17,7 @@
  *   bl_scan_syncmers     sampler::syncmer_sampler<It,minimizer_position_extractor>
  *                                                                         include/syncmer_sampler.hpp:9-137, include/kmer_view.hpp:250-283
  *   bl_hash64_u64        hash::hash64::hash<uint64_t>                     include/hash.hpp:55-59 (host-side convenience, bit-exact)
+ *   bl_hash64_u128       hash::hash64::hash<__uint128_t>                  the same for a 16-byte value
  *
  * Conventions
  *   - Plain C: opaque handles, plain pointers and sizes.  Never throws; every call returns a status
@@ -68,7 +72,7 @@ typedef struct bl_result {
     uint64_t xor_value;  /* XOR of the 2-bit packed values of all records */
     uint64_t xor_hash;   /* XOR of their 64-bit hashes */
     uint64_t xor_pos;    /* XOR of their global positions (k-mer scan: wrapping SUM of hashes instead) */
-    uint64_t aux;        /* super-k-mers: number of group ends seen (== count when consistent) */
+    uint64_t aux;        /* super-k-mers: number of group ends seen (== count when consistent); 128-bit k-mer scans: XOR of the high words */
     int32_t status;      /* BL_OK or BL_ERR_CAPACITY */
     int32_t redone;      /* diagnostic: tiles whose pass 1 could not decide a window on what it looks at (an approximation of the hash's
                           * high dword, or high dwords alone) and were counted a second time on the hashes themselves; the records are the
@@ -143,6 +147,25 @@ int bl_batch_download(bl_batch* batch, uint64_t first, uint64_t n, char* out);
 int bl_scan_kmers(bl_ctx* ctx, const bl_batch* batch, uint64_t first, uint64_t n, uint32_t k, uint64_t seed, uint32_t flags,
                   uint64_t* d_values, uint64_t* d_hashes, uint8_t* d_valid, bl_result* result);
 
+/* k-mers up to k = 64: wrapper::kmer_view<__uint128_t,It> (the reference templates kmer_view on KmerType; its super-k-mer driver
+ * uses typedef __uint128_t kmer_t) with hash::hash64::hash<__uint128_t>.  Arrays and result as bl_scan_kmers, except:
+ *   d_values[2*(p-first)], d_values[2*(p-first)+1]  the k-mer as a 128-bit integer, LOW word first, then the HIGH word — the
+ *                      little-endian object representation of __uint128_t, so d_values is a valid __uint128_t[n]; it must be
+ *                      16-byte aligned (BL_ERR_INVALID otherwise).  First base in the most significant occupied pair.
+ *   d_hashes[p-first]  hash64(value, seed) = first word of MurmurHash3_x64_128 over those 16 BYTES, whatever k is (sizeof(KmerType)
+ *                      in the reference's template), seed truncated to 32 bits.  For k <= 32 the value equals bl_scan_kmers' with a
+ *                      high word of 0, but the hash DIFFERS from bl_scan_kmers' hash of 8 bytes — as in the reference, where the
+ *                      hash depends on KmerType.
+ *   canonical          numeric minimum of the two 128-bit values, the reverse complement taken in 2k bits.  (The reference's own
+ *                      reverse-strand update shifts a 64-bit operand by up to 126 bits, kmer_view.hpp:195,223: undefined for
+ *                      k >= 33.  This is the intended meaning, its formulas evaluated in KmerType)
+ * result: count, xor_value := XOR of the low words, aux := XOR of the high words, xor_hash, xor_pos := wrapping sum of hashes.
+ * 1 <= k <= 64 (bl_scan_kmers keeps its own limit of 32).
+ * NOT covered for k > 32: 128-bit keys in bl_sort_unique_u64 / bl_jaccard_sorted_u64 / bl_partition_u64 and the spill formats (the
+ * 64-bit HASHES of the records are keys those calls take), biolib_amd::read_pool, syncmers, and the super-k-mer records / counter. */
+int bl_scan_kmers128(bl_ctx* ctx, const bl_batch* batch, uint64_t first, uint64_t n, uint32_t k, uint64_t seed, uint32_t flags,
+                     uint64_t* d_values /* 2 per position: lo, hi */, uint64_t* d_hashes, uint8_t* d_valid, bl_result* result);
+
 /* minimizers (C3): hashed unit = (canonical) `unit`-mer, window = w consecutive units inside one
  * sequence and one break-free run, leftmost minimum hash; one record each time the minimizer
  * occurrence changes (or a run begins):
@@ -159,6 +182,14 @@ int bl_scan_minimizers(bl_ctx* ctx, const bl_batch* batch, uint64_t first, uint6
 int bl_scan_hash_sample(bl_ctx* ctx, const bl_batch* batch, uint64_t first, uint64_t n, uint32_t k, uint64_t seed, uint64_t threshold,
                         uint32_t flags, uint64_t* d_values, uint64_t* d_positions, uint64_t* d_hashes, uint64_t capacity,
                         bl_result* result);
+
+/* The same sampler over kmer_view<__uint128_t> (1 <= k <= 64): the k-mers of bl_scan_kmers128 whose 16-byte hash is below `threshold`,
+ * position-ordered.  d_values holds two words per record (low, high; 16-byte aligned), d_positions and d_hashes one.  Nothing is
+ * written at or beyond `capacity`; the result always carries the full count (BL_ERR_CAPACITY when it exceeds capacity).
+ * result: count, xor_value := XOR of the low words, aux := XOR of the high words, xor_hash, xor_pos := XOR of the positions. */
+int bl_scan_hash_sample128(bl_ctx* ctx, const bl_batch* batch, uint64_t first, uint64_t n, uint32_t k, uint64_t seed, uint64_t threshold,
+                           uint32_t flags, uint64_t* d_values /* 2 per record */, uint64_t* d_positions, uint64_t* d_hashes,
+                           uint64_t capacity, bl_result* result);
 
 /* super-k-mers (C4): maximal groups of consecutive k-mers sharing one minimizer occurrence
  * (m-mer, w = k - m + 1):
@@ -395,6 +426,8 @@ int bl_copy_to_device(bl_ctx* ctx, void* d_dst, const void* src, uint64_t bytes)
 
 /* ---- host-side scalar helper (bit-exact with the device hash) ------------------------------------- */
 uint64_t bl_hash64_u64(uint64_t value, uint64_t seed);
+/* hash::hash64::hash<__uint128_t>(value, seed), value = hi << 64 | lo: the 16 bytes hashed are lo's then hi's */
+uint64_t bl_hash64_u128(uint64_t lo, uint64_t hi, uint64_t seed);
 
 #ifdef __cplusplus
 }

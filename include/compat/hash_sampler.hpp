@@ -26,6 +26,9 @@ class hash_sampler
     template <typename It, typename = void> struct has_view : std::false_type {};
     template <typename It> struct has_view<It, std::void_t<decltype(std::declval<It const&>().view()), decltype(std::declval<It const&>().chars_consumed())>> : std::true_type {};
     static constexpr bool gpu_path = has_view<Iterator>::value and std::is_same<HashFunctionFamily, hash::hash64>::value;
+    template <typename It, typename = void> struct wide_view : std::false_type {};
+    template <typename It> struct wide_view<It, std::void_t<decltype(It::wide_kmers)>> : std::integral_constant<bool, It::wide_kmers> {};
+    static_assert(not (gpu_path and wide_view<Iterator>::value), "hash_sampler over a kmer_view of 128-bit k-mers is not provided: call bl_scan_hash_sample128");
     using hash_type = typename HashFunctionFamily::hash_type;
 
     public:

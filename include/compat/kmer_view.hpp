@@ -9,14 +9,18 @@
 // over the result — null items for breaks, position / id bookkeeping, and quirk Q1 (`it != cend()` stops
 // before the last k-mer, which stays readable as *it; kmer_view.hpp:57,172-202).  Inputs on which the
 // reference reads out of bounds (length < k, break followed by fewer than k bases at the end; Q2)
-// terminate cleanly instead.  KmerType must fit 64 bits and k <= 32 (the reference's own limit for
-// uint64_t, kmer_view.hpp:195).
+// terminate cleanly instead.  KmerType of up to 8 bytes: k <= 32 (the reference's own limit for uint64_t,
+// kmer_view.hpp:195), through bl_scan_kmers.  KmerType = __uint128_t: k <= 64, through bl_scan_kmers128 — values in 128 bits,
+// canonical = numeric minimum with the reverse complement taken in 2k bits (the reference's reverse-strand update is undefined
+// there for k >= 33).  Not covered for 128-bit k-mers: read_pool lookups (every view scans itself), and
+// hash::minimizer_position_extractor below.
 // Views built on memory handed out by a biolib_amd::read_pool (read_pool.hpp) do not go to the GPU one by one: they
 // index into the single scan of the pool's current batch.
 #ifndef BIOLIB_AMD_COMPAT_KMER_VIEW_HPP
 #define BIOLIB_AMD_COMPAT_KMER_VIEW_HPP
 
 #include <cassert>
+#include <cstring>
 #include <limits>
 #include <optional>
 #include <string>
@@ -40,13 +44,19 @@ template <typename KmerType, class Iterator>
 class kmer_view
 {
     static_assert(std::is_same<typename Iterator::value_type, char>::value, "kmer_view iterates over char");
-    static_assert(sizeof(KmerType) <= 8, "the GPU path packs k-mers in 64 bits (k <= 32)");
+    static_assert(sizeof(KmerType) <= 16, "the GPU path packs k-mers in 64 bits (k <= 32) or 128 bits (k <= 64)");
+    static constexpr bool wide = sizeof(KmerType) > 8;
 
+    public:
+        // what a position's k-mer is stored as: one word, or the 128-bit integer bl_scan_kmers128 writes (low word first)
+        using stored_type = typename std::conditional<wide, unsigned __int128, uint64_t>::type;
+
+    private:
     struct materialised {
         std::string own_chars;             // host copy of [start, stop) (empty for pooled views)
-        std::vector<uint64_t> own_values;  // per position: packed (canonical) k-mer, 0 where none starts
+        std::vector<stored_type> own_values;  // per position: packed (canonical) k-mer, 0 where none starts
         char const* chars = nullptr;       // what the iterators read: the copies above, or a read_pool's arena and its batch scan
-        uint64_t const* values = nullptr;
+        stored_type const* values = nullptr;
         std::size_t n = 0;
     };
 
@@ -92,6 +102,8 @@ class kmer_view
                     return std::numeric_limits<KmerType>::max();
                 }
 
+                // the samplers' GPU paths work on 64-bit k-mers: they refuse a view of 128-bit ones at compile time
+                static constexpr bool wide_kmers = wide;
                 // position of the underlying char iterator, for samplers that run the GPU path themselves
                 kmer_view const* view() const noexcept {return parent_view;}
                 std::size_t chars_consumed() const noexcept {return consumed;}
@@ -126,7 +138,8 @@ class kmer_view
 
         kmer_view(Iterator start, Iterator stop, uint8_t k, bool canonical = false) : itr_start(start), itr_stop(stop), klen(k), canon(canonical)
         {
-            if (k == 0 or k > 32) throw std::runtime_error("[k-mer view] k must be in [1, 32] for 64-bit k-mers");
+            if (not wide and (k == 0 or k > 32)) throw std::runtime_error("[k-mer view] k must be in [1, 32] for 64-bit k-mers");
+            if (wide and (k == 0 or k > 64)) throw std::runtime_error("[k-mer view] k must be in [1, 64] for 128-bit k-mers");
         }
         const_iterator cbegin() const {return const_iterator(this);}
         const_iterator cend() const noexcept {return const_iterator(this, 0);}
@@ -142,7 +155,7 @@ class kmer_view
             if (m->own_chars.size() != m->n) cache->own_chars.assign(m->chars, m->n);  // pooled view: copy on demand
             return cache->own_chars;
         }
-        std::vector<uint64_t> const& values() const
+        std::vector<stored_type> const& values() const
         {
             auto const* m = materialise();
             if (m->own_values.size() != m->n) cache->own_values.assign(m->values, m->values + m->n);
@@ -169,7 +182,7 @@ class kmer_view
         {
             if (cache) return cache.get();
             auto m = std::make_shared<materialised>();
-            if constexpr (std::is_same<Iterator, char_iterator>::value) {
+            if constexpr (std::is_same<Iterator, char_iterator>::value and not wide) {
                 // contiguous memory: is it a record a read_pool handed out?  then the batch scan already holds its k-mers
                 const std::size_t n = static_cast<std::size_t>(itr_stop.base() - itr_start.base());
                 if (uint64_t const* pooled = biolib_amd::read_pool::lookup(itr_start.base(), n, klen, canon)) {
@@ -185,11 +198,18 @@ class kmer_view
             m->own_values.assign(n, 0);
             if (n >= klen) {
                 biolib_amd::batch_handle batch(m->own_chars.data(), n);
-                biolib_amd::device_array<uint64_t> d_values(n);
+                const uint32_t flags = (canon ? (uint32_t)BL_FLAG_CANONICAL : 0u) | BL_FLAG_SYNC;
                 bl_result res;
-                biolib_amd::check(bl_scan_kmers(biolib_amd::context::get(), batch.b, 0, 0, klen, 0, (canon ? (uint32_t)BL_FLAG_CANONICAL : 0u) | BL_FLAG_SYNC,
-                                                d_values.d, nullptr, nullptr, &res), "bl_scan_kmers");
-                m->own_values = d_values.to_host(n);
+                if constexpr (wide) {
+                    biolib_amd::device_array<uint64_t> d_values(2 * n);  // per position: low word, high word = one little-endian __uint128_t
+                    biolib_amd::check(bl_scan_kmers128(biolib_amd::context::get(), batch.b, 0, 0, klen, 0, flags, d_values.d, nullptr, nullptr, &res), "bl_scan_kmers128");
+                    const std::vector<uint64_t> words = d_values.to_host(2 * n);
+                    std::memcpy(m->own_values.data(), words.data(), 2 * n * sizeof(uint64_t));
+                } else {
+                    biolib_amd::device_array<uint64_t> d_values(n);
+                    biolib_amd::check(bl_scan_kmers(biolib_amd::context::get(), batch.b, 0, 0, klen, 0, flags, d_values.d, nullptr, nullptr, &res), "bl_scan_kmers");
+                    m->own_values = d_values.to_host(n);
+                }
             }
             m->chars = m->own_chars.data();
             m->values = m->own_values.data();
@@ -237,6 +257,8 @@ class minimizer_position_extractor
         template <typename KmerType>
         std::size_t operator()(wrapper::kmer_context_t<KmerType> const& kmer) const noexcept
         {
+            // the reference hashes `km & mask` in KmerType there — 16 bytes for a 128-bit k-mer, a different extractor: not provided
+            static_assert(sizeof(KmerType) <= 8, "minimizer_position_extractor takes k-mers of up to 64 bits (k <= 32); 128-bit k-mers are not supported here");
             if (!kmer.value) return klen + 1;
             // the k-mer packs its first base in the most significant pair: the m-mer at offset o from the left end is the 2m bits
             // that start 2 * (k - m - o) bits up.  Left to right with a strict '<': the leftmost of equal minima stays.

@@ -30,6 +30,9 @@ class minimizer_sampler
     template <typename It, typename = void> struct has_view : std::false_type {};
     template <typename It> struct has_view<It, std::void_t<decltype(std::declval<It const&>().view()), decltype(std::declval<It const&>().chars_consumed())>> : std::true_type {};
     static constexpr bool gpu_path = has_view<Iterator>::value and std::is_same<HashFunctionFamily, hash::hash64>::value;
+    template <typename It, typename = void> struct wide_view : std::false_type {};
+    template <typename It> struct wide_view<It, std::void_t<decltype(It::wide_kmers)>> : std::integral_constant<bool, It::wide_kmers> {};
+    static_assert(not (gpu_path and wide_view<Iterator>::value), "minimizer_sampler over a kmer_view of 128-bit k-mers is not provided (hashed units are at most 32 bases)");
 
     public:
         class const_iterator

@@ -32,6 +32,9 @@ template <class Iterator, typename PropertyExtractor>
 class syncmer_sampler
 {
     static constexpr bool gpu_path = detail::has_view<Iterator>::value and std::is_same<PropertyExtractor, hash::minimizer_position_extractor>::value;
+    template <typename It, typename = void> struct wide_view : std::false_type {};
+    template <typename It> struct wide_view<It, std::void_t<decltype(It::wide_kmers)>> : std::integral_constant<bool, It::wide_kmers> {};
+    static_assert(not (gpu_path and wide_view<Iterator>::value), "syncmer_sampler over a kmer_view of 128-bit k-mers is not provided (k <= 32)");
 
     public:
         class const_iterator

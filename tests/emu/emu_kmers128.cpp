@@ -1,0 +1,230 @@
+// TEST INFRASTRUCTURE: the per-thread bodies of the 128-bit k-mer scans (biolib_amd/csrc/bl_kmers128_core.hpp) run on the host, lane by
+// lane and tile by tile, under AddressSanitizer / UBSan, against a plain `unsigned __int128` loop written here.  Built and run by
+// tests/test_emu_kmers128.py, which compares the digests printed below with its own Python model.
+//
+//   emu_kmers128 <batch file> <k> <first> <n> <threshold>
+// batch file: u64 n_bases, u64 n_seqs, u64 offsets[n_seqs + 1], bases.  For canonical x drop_last it prints
+//   dense  <canonical> <drop_last> count xor_lo xor_hi xor_hash sum_hash
+//   sample <canonical> <drop_last> count xor_lo xor_hi xor_hash xor_pos
+// and exits non-zero on the first disagreement with the plain loop.
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <vector>
+
+#include "../../biolib_amd/csrc/bl_kmers128_core.hpp"
+
+typedef unsigned __int128 u128;
+
+static int nt4(uint8_t c)
+{
+    switch (c) {
+        case 'A': case 'a': return 0;
+        case 'C': case 'c': return 1;
+        case 'G': case 'g': return 2;
+        case 'T': case 't': case 'U': case 'u': return 3;
+        default: return 4;
+    }
+}
+
+static uint64_t rotl(uint64_t x, int r) { return (x << r) | (x >> (64 - r)); }
+static uint64_t fmix(uint64_t k)
+{
+    k ^= k >> 33; k *= 0xff51afd7ed558ccdULL; k ^= k >> 33; k *= 0xc4ceb9fe1a85ec53ULL; k ^= k >> 33;
+    return k;
+}
+// MurmurHash3_x64_128 of the 16 bytes of v, first word (written out here: no code shared with the header under test)
+static uint64_t plain_hash(u128 v, uint32_t seed)
+{
+    const uint64_t c1 = 0x87c37b91114253d5ULL, c2 = 0x4cf5ad432745937fULL;
+    uint64_t k1 = (uint64_t)v, k2 = (uint64_t)(v >> 64), h1 = seed, h2 = seed;
+    k1 *= c1; k1 = rotl(k1, 31); k1 *= c2; h1 ^= k1;
+    h1 = rotl(h1, 27); h1 += h2; h1 = h1 * 5 + 0x52dce729;
+    k2 *= c2; k2 = rotl(k2, 33); k2 *= c1; h2 ^= k2;
+    h2 = rotl(h2, 31); h2 += h1; h2 = h2 * 5 + 0x38495ab5;
+    h1 ^= 16; h2 ^= 16;
+    h1 += h2; h2 += h1;
+    h1 = fmix(h1); h2 = fmix(h2);
+    return h1 + h2;
+}
+
+struct Plain {
+    std::vector<uint64_t> lo, hi, hash;
+    std::vector<uint8_t> valid;
+};
+
+static Plain plain_scan(const std::vector<uint8_t>& seq, const std::vector<uint64_t>& offs, int k, uint32_t seed, bool canonical, bool drop_last)
+{
+    const size_t n = seq.size();
+    Plain r{std::vector<uint64_t>(n, 0), std::vector<uint64_t>(n, 0), std::vector<uint64_t>(n, 0), std::vector<uint8_t>(n, 0)};
+    const u128 mask = k == 64 ? ~(u128)0 : (((u128)1 << (2 * k)) - 1);
+    for (size_t q = 0; q + 1 < offs.size(); ++q) {
+        u128 fwd = 0, rc = 0;
+        int run = 0;
+        for (uint64_t i = offs[q]; i < offs[q + 1]; ++i) {
+            const int c = nt4(seq[i]);
+            if (c > 3) { run = 0; continue; }
+            fwd = ((fwd << 2) | (u128)c) & mask;
+            rc = (rc >> 2) | ((u128)(3 ^ c) << (2 * (k - 1)));
+            if (++run < k) continue;
+            if (drop_last && i + 1 == offs[q + 1]) continue;
+            const u128 v = canonical && rc < fwd ? rc : fwd;
+            const uint64_t p = i + 1 - k;
+            r.lo[p] = (uint64_t)v;
+            r.hi[p] = (uint64_t)(v >> 64);
+            r.hash[p] = plain_hash(v, seed);
+            r.valid[p] = 1;
+        }
+    }
+    return r;
+}
+
+#define CHECK(cond, ...)                          \
+    do {                                          \
+        if (!(cond)) {                            \
+            std::fprintf(stderr, "emu_kmers128: " __VA_ARGS__); \
+            std::fprintf(stderr, "\n");           \
+            std::exit(1);                         \
+        }                                         \
+    } while (0)
+
+int main(int argc, char** argv)
+{
+    CHECK(argc == 6, "usage: emu_kmers128 <batch file> <k> <first> <n> <threshold>");
+    FILE* f = std::fopen(argv[1], "rb");
+    CHECK(f, "cannot open %s", argv[1]);
+    uint64_t hdr[2];
+    CHECK(std::fread(hdr, 8, 2, f) == 2, "short file");
+    const uint64_t n_bases = hdr[0], n_seqs = hdr[1];
+    std::vector<uint64_t> offs(n_seqs + 1);
+    CHECK(std::fread(offs.data(), 8, n_seqs + 1, f) == n_seqs + 1, "short file");
+    std::vector<uint8_t> seq(n_bases);
+    CHECK(n_bases == 0 || std::fread(seq.data(), 1, n_bases, f) == n_bases, "short file");
+    std::fclose(f);
+    const int k = std::atoi(argv[2]);
+    const uint64_t first = std::strtoull(argv[3], nullptr, 10), n_arg = std::strtoull(argv[4], nullptr, 10);
+    const uint64_t threshold = std::strtoull(argv[5], nullptr, 10);
+    const uint64_t end = (n_arg == 0 || first + n_arg > n_bases) ? n_bases : first + n_arg;
+    const uint32_t seed = 0x9e3779b9u;
+    const uint64_t origin = 1000000007ull;
+    CHECK(k >= 1 && k <= bl::MAX_UNIT128 && first < end, "bad arguments");
+
+    // an exact-size heap copy of the bases (16-byte aligned as the device buffer is; the sanitizer sees every byte past n_bases)
+    uint8_t* exact = static_cast<uint8_t*>(std::malloc(n_bases ? n_bases : 1));
+    std::memcpy(exact, seq.data(), n_bases);
+    std::vector<uint32_t> start_bits((n_bases + 31) / 32 + 4, 0);
+    for (uint64_t q = 0; q < n_seqs; ++q)
+        if (offs[q] < n_bases) start_bits[offs[q] >> 5] |= 1u << (offs[q] & 31);
+
+    for (int canonical = 0; canonical < 2; ++canonical) {
+        for (int drop_last = 0; drop_last < 2; ++drop_last) {
+            const Plain want = plain_scan(seq, offs, k, seed, canonical, drop_last);
+            bl::Kmer128Params p{};
+            p.bases = exact;
+            p.n_bases = (int64_t)n_bases;
+            p.start_bits = start_bits.data();
+            p.pos_base = (int64_t)origin;
+            bl::plan_kmers128((int64_t)first, (int64_t)end, p);
+            p.unit = k;
+            p.seed = seed;
+            p.canonical = canonical;
+            p.drop_last = drop_last;
+            p.hash_below = threshold;
+            bl::ScanParams lp{};
+            lp.bases = p.bases;
+            lp.n_bases = p.n_bases;
+            lp.start_bits = p.start_bits;
+            const size_t span = end - first;
+            // exact-size outputs: a store outside [0, span) is a finding
+            std::vector<bl::U64x2> out_value(span);
+            std::vector<uint64_t> out_hash(span);
+            std::vector<uint8_t> out_valid(span);
+            std::vector<uint32_t> codes(bl::NCHUNK_POS), flags(bl::NCHUNK_POS);
+            std::vector<uint16_t> masks((size_t)p.n_tiles * bl::TPB);
+            std::vector<unsigned long long> tile_counts(p.n_tiles), tile_base(p.n_tiles);
+            bl::Kmer128Acc dense{0, 0, 0, 0, 0}, digest_only{0, 0, 0, 0, 0}, samp{0, 0, 0, 0, 0};
+            for (int tile = 0; tile < p.n_tiles; ++tile) {
+                const int64_t q0 = p.origin + (int64_t)tile * bl::H;
+                for (int c = 0; c < bl::NCHUNK_POS; ++c) bl::stage_chunk(lp, codes.data(), flags.data(), c, q0);
+                unsigned long long cnt = 0;
+                for (int tid = 0; tid < bl::TPB; ++tid) {
+                    p.out_value = reinterpret_cast<uint64_t*>(out_value.data());
+                    p.out_hash = out_hash.data();
+                    p.out_valid = out_valid.data();
+                    bl::kmer128_dense_thread(p, codes.data(), flags.data(), tid, q0, dense);
+                    p.out_value = nullptr;
+                    p.out_hash = nullptr;
+                    p.out_valid = nullptr;
+                    bl::kmer128_dense_thread(p, codes.data(), flags.data(), tid, q0, digest_only);  // the path that stores nothing
+                    const uint32_t sel = bl::kmer128_count_thread(p, codes.data(), flags.data(), tid, q0, samp);
+                    masks[(size_t)tile * bl::TPB + tid] = (uint16_t)sel;
+                    cnt += (unsigned)__builtin_popcount(sel);
+                }
+                tile_counts[tile] = cnt;
+            }
+            // dense: arrays and digest against the plain loop
+            unsigned long long w_cnt = 0, w_lo = 0, w_hi = 0, w_h = 0, w_sum = 0;
+            for (uint64_t q = first; q < end; ++q) {
+                const size_t o = q - first;
+                CHECK(out_valid[o] == want.valid[q] && out_value[o].lo == want.lo[q] && out_value[o].hi == want.hi[q] && out_hash[o] == want.hash[q],
+                      "dense k=%d canonical=%d drop_last=%d position %llu", k, canonical, drop_last, (unsigned long long)q);
+                w_cnt += want.valid[q];
+                w_lo ^= want.lo[q];
+                w_hi ^= want.hi[q];
+                w_h ^= want.hash[q];
+                w_sum += want.hash[q];
+            }
+            CHECK(dense.cnt == w_cnt && dense.xlo == w_lo && dense.xhi == w_hi && dense.xh == w_h && dense.sx == w_sum, "dense digest k=%d", k);
+            CHECK(std::memcmp(&dense, &digest_only, sizeof(dense)) == 0, "digest-only path differs k=%d", k);
+            std::printf("dense %d %d %llu %llu %llu %llu %llu\n", canonical, drop_last, dense.cnt, dense.xlo, dense.xhi, dense.xh, dense.sx);
+
+            // sampler: prefix over tiles, then the record pass — once with room for everything, once one record short
+            std::vector<uint64_t> w_pos;
+            for (uint64_t q = first; q < end; ++q)
+                if (want.valid[q] && want.hash[q] < threshold) w_pos.push_back(q);
+            unsigned long long total = 0;
+            for (int tile = 0; tile < p.n_tiles; ++tile) {
+                tile_base[tile] = total;
+                total += tile_counts[tile];
+            }
+            CHECK(total == w_pos.size() && samp.cnt == total, "sampler count k=%d: %llu, want %zu", k, total, w_pos.size());
+            for (int pass = 0; pass < 2; ++pass) {
+                const uint64_t cap = pass == 0 ? total : (total ? total - 1 : 0);
+                const uint64_t guard = 0xfeedfacecafebeefULL;
+                std::vector<bl::U64x2> rv(cap);            // exact size again
+                std::vector<uint64_t> rp(cap), rh(cap + 1, guard);
+                p.rec_value = reinterpret_cast<uint64_t*>(rv.data());
+                p.rec_pos = rp.data();
+                p.rec_hash = rh.data();
+                p.capacity = cap;
+                for (int tile = 0; tile < p.n_tiles; ++tile) {
+                    const int64_t q0 = p.origin + (int64_t)tile * bl::H;
+                    for (int c = 0; c < bl::NCHUNK_POS; ++c) bl::stage_chunk(lp, codes.data(), flags.data(), c, q0);
+                    uint64_t at = tile_base[tile];
+                    for (int tid = 0; tid < bl::TPB; ++tid) {
+                        const uint32_t sel = masks[(size_t)tile * bl::TPB + tid];
+                        bl::kmer128_emit_thread(p, codes.data(), tid, q0, sel, at);
+                        at += (unsigned)__builtin_popcount(sel);
+                    }
+                }
+                CHECK(rh[cap] == guard, "sampler wrote at capacity k=%d", k);
+                for (uint64_t r = 0; r < cap; ++r) {
+                    const uint64_t q = w_pos[r];
+                    CHECK(rp[r] == q + origin && rv[r].lo == want.lo[q] && rv[r].hi == want.hi[q] && rh[r] == want.hash[q],
+                          "sampler k=%d canonical=%d drop_last=%d record %llu", k, canonical, drop_last, (unsigned long long)r);
+                }
+            }
+            unsigned long long s_lo = 0, s_hi = 0, s_h = 0, s_pos = 0;
+            for (uint64_t q : w_pos) {
+                s_lo ^= want.lo[q];
+                s_hi ^= want.hi[q];
+                s_h ^= want.hash[q];
+                s_pos ^= q + origin;
+            }
+            CHECK(samp.xlo == s_lo && samp.xhi == s_hi && samp.xh == s_h && samp.sx == s_pos, "sampler digest k=%d", k);
+            std::printf("sample %d %d %llu %llu %llu %llu %llu\n", canonical, drop_last, samp.cnt, samp.xlo, samp.xhi, samp.xh, samp.sx);
+        }
+    }
+    std::free(exact);
+    return 0;
+}
