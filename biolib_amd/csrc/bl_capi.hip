@@ -16,6 +16,7 @@
 #include "../../include/biolib_amd.h"
 #include "bl_launch.hpp"
 #include "bl_kmers128_launch.hpp"
+#include "bl_syncmers128_launch.hpp"
 
 namespace {
 
@@ -990,6 +991,57 @@ int bl_scan_hash_sample128(bl_ctx* c, const bl_batch* b, uint64_t first, uint64_
         if (e != hipSuccess) return fail(BL_ERR_HIP, std::string("kmer128_emit_kernel: ") + hipGetErrorString(e));
     }
     return end_scan(c, 1u << 0, result, wants, capacity, flags);
+}
+
+// ---- syncmers of 128-bit k-mers (k <= 64, s <= 32, 16-byte s-mer keys): bl_syncmers128.hip
+
+int bl_scan_syncmers128(bl_ctx* c, const bl_batch* b, uint64_t first, uint64_t n, uint32_t k, uint32_t s, uint32_t start_offset,
+                        uint32_t end_offset, uint64_t seed, uint32_t flags, uint64_t* d_positions, uint64_t capacity, bl_result* result)
+{
+    if (!c || !b || b->ctx != c) return fail(BL_ERR_INVALID, "ctx/batch is NULL or the batch belongs to another context");
+    if (s < 1 || s > bl::MAX_SMER128 || k < s || k > bl::MAX_UNIT128)
+        return fail(BL_ERR_INVALID, "need 1 <= s <= 32 and s <= k <= 64 (KmerType = __uint128_t, 16-byte s-mer keys)");
+    bl::Sync128Params p{};
+    bool empty;
+    int rc = prepare_kmers128(c, b, first, n, k, seed, flags, nullptr, p.km, result, empty);
+    if (rc != BL_OK || empty) return rc;
+    bl::plan_syncmers128((int)k, (int)s, start_offset, end_offset, p);
+    p.km.rec_pos = d_positions;
+    p.km.capacity = d_positions ? capacity : 0;
+    rc = begin_scan(c);
+    if (rc != BL_OK) return rc;
+    // scratch as for bl_scan_hash_sample128: tile counts + local prefixes + scan-block totals / prefixes, one u16 record mask per lane
+    const size_t nt = (size_t)p.km.n_tiles, nb = (nt + bl::SCAN_BLK - 1) / bl::SCAN_BLK;
+    rc = grow(c, reinterpret_cast<void**>(&c->cur->tile_buf), &c->cur->tile_buf_bytes, (2 * nt + 2 * nb + 8) * sizeof(unsigned long long));
+    if (rc != BL_OK) return rc;
+    rc = grow(c, reinterpret_cast<void**>(&c->cur->slot_buf), &c->cur->slot_buf_bytes, nt * bl::TPB * sizeof(uint16_t));
+    if (rc != BL_OK) return rc;
+    unsigned long long* tb = reinterpret_cast<unsigned long long*>(c->cur->tile_buf);
+    p.km.tile_counts = tb;
+    p.km.tile_base = tb + nt;
+    unsigned long long* block_tot = tb + 2 * nt;
+    p.km.block_base = block_tot + nb;
+    p.km.lane_masks = c->cur->slot_buf;
+    p.km.shards = c->shards();
+    rc = kernel_event(c, true);
+    if (rc != BL_OK) return rc;
+    hipError_t e = bl::launch_syncmers128_count(p, c->stream);
+    if (e != hipSuccess) return fail(BL_ERR_HIP, std::string("sync128_count_kernel: ") + hipGetErrorString(e));
+    rc = kernel_event(c, false);
+    if (rc != BL_OK) return rc;
+    bl::ScanParams sp{};  // the prefix scan reads these four fields, and adds the total to the digest's count
+    sp.tile_counts = p.km.tile_counts;
+    sp.tile_base = p.km.tile_base;
+    sp.block_base = p.km.block_base;
+    sp.shards = p.km.shards;
+    unsigned long long* carry = reinterpret_cast<unsigned long long*>(c->cur->ws);  // header word, zeroed by begin_scan
+    e = bl::launch_tile_scan(sp, bl::GroupRange{0, (uint32_t)p.km.n_tiles}, block_tot, carry, c->stream);
+    if (e != hipSuccess) return fail(BL_ERR_HIP, std::string("tile_scan: ") + hipGetErrorString(e));
+    if (d_positions) {
+        e = bl::launch_syncmers128_emit(p, c->stream);
+        if (e != hipSuccess) return fail(BL_ERR_HIP, std::string("sync128_emit_kernel: ") + hipGetErrorString(e));
+    }
+    return end_scan(c, 1u << 0, result, d_positions != nullptr, capacity, flags);
 }
 
 uint64_t bl_hash64_u128(uint64_t lo, uint64_t hi, uint64_t seed) { return bl::murmur64_u128(lo, hi, (uint32_t)seed); }

@@ -443,6 +443,13 @@ class Batch:
         check(self._lib.bl_scan_syncmers(self.ctx._h, self._h, first, n, k, s, soff, eoff, seed, flags, _ptr(positions), capacity, C.byref(result)))
         return result
 
+    def syncmers128_raw(self, k, s, soff, eoff, seed, flags, first=0, n=0, positions=None, capacity=0, result=None):
+        """bl_scan_syncmers128 (s <= 32, s <= k <= 64): s-mers hashed as 16-byte keys"""
+        result = result if result is not None else Result()
+        self.ctx._hold(result, flags)
+        check(self._lib.bl_scan_syncmers128(self.ctx._h, self._h, first, n, k, s, soff, eoff, seed, flags, _ptr(positions), capacity, C.byref(result)))
+        return result
+
     # ---- convenience wrappers returning host numpy arrays
     def _span(self, first, n):
         end = self.n_bases if not n else min(self.n_bases, first + n)
@@ -618,6 +625,28 @@ class Batch:
             r = Result()
             try:
                 self.syncmers_raw(k, s, start_offset, end_offset, seed, _flags(canonical, drop_last, True), first, n, p, cap, r)
+            finally:
+                self._last_count = r.count
+            out = r.as_dict()
+            out.update(positions=_host_u64(p, int(r.count)))
+            return out
+
+        return self._with_capacity(guess, run)
+
+    def syncmers128(self, k, s, start_offset, end_offset, seed=0, canonical=False, drop_last=False, first=0, n=0, positions=True, capacity=None):
+        """syncmers of k-mers up to k = 64 (syncmer_sampler over kmer_view<__uint128_t>): as syncmers(), with the s-mers (s <= 32) hashed
+        as 16-byte keys, hash64_u128(s-mer, 0, seed) — for k <= 32 the records differ in general from syncmers()'s."""
+        span = self._span(first, n)
+        if not positions:
+            r = self.syncmers128_raw(k, s, start_offset, end_offset, seed, _flags(canonical, drop_last, True), first, n)
+            return r.as_dict()
+        guess = capacity if capacity is not None else int(span * 2.6 / max(k - s + 1, 1)) + 4096
+
+        def run(cap):
+            p = self.ctx.empty_u64(cap)
+            r = Result()
+            try:
+                self.syncmers128_raw(k, s, start_offset, end_offset, seed, _flags(canonical, drop_last, True), first, n, p, cap, r)
             finally:
                 self._last_count = r.count
             out = r.as_dict()

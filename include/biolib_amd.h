@@ -16,6 +16,7 @@
  *   bl_scan_super_kmer_records  the same groups as self-contained records  include/super_kmer_view.hpp:20-24 (the record), §8f rank 4
  *   bl_scan_syncmers     sampler::syncmer_sampler<It,minimizer_position_extractor>
  *                                                                         include/syncmer_sampler.hpp:9-137, include/kmer_view.hpp:250-283
+ *   bl_scan_syncmers128  the same sampler over kmer_view<__uint128_t,It>  k <= 64, s <= 32; s-mer keys of 16 bytes (kmer_view.hpp:266-283 in KmerType)
  *   bl_hash64_u64        hash::hash64::hash<uint64_t>                     include/hash.hpp:55-59 (host-side convenience, bit-exact)
  *   bl_hash64_u128       hash::hash64::hash<__uint128_t>                  the same for a 16-byte value
  *
@@ -162,7 +163,7 @@ int bl_scan_kmers(bl_ctx* ctx, const bl_batch* batch, uint64_t first, uint64_t n
  * result: count, xor_value := XOR of the low words, aux := XOR of the high words, xor_hash, xor_pos := wrapping sum of hashes.
  * 1 <= k <= 64 (bl_scan_kmers keeps its own limit of 32).
  * NOT covered for k > 32: 128-bit keys in bl_sort_unique_u64 / bl_jaccard_sorted_u64 / bl_partition_u64 and the spill formats (the
- * 64-bit HASHES of the records are keys those calls take), biolib_amd::read_pool, syncmers, and the super-k-mer records / counter. */
+ * 64-bit HASHES of the records are keys those calls take), biolib_amd::read_pool, and the super-k-mer records / counter.  (Syncmers: bl_scan_syncmers128.) */
 int bl_scan_kmers128(bl_ctx* ctx, const bl_batch* batch, uint64_t first, uint64_t n, uint32_t k, uint64_t seed, uint32_t flags,
                      uint64_t* d_values /* 2 per position: lo, hi */, uint64_t* d_hashes, uint8_t* d_valid, bl_result* result);
 
@@ -207,6 +208,22 @@ int bl_scan_super_kmers(bl_ctx* ctx, const bl_batch* batch, uint64_t first, uint
 int bl_scan_syncmers(bl_ctx* ctx, const bl_batch* batch, uint64_t first, uint64_t n, uint32_t k, uint32_t s, uint32_t start_offset,
                      uint32_t end_offset, uint64_t seed, uint32_t flags, uint64_t* d_positions, uint64_t capacity,
                      bl_result* result);
+
+/* syncmers of k-mers up to k = 64: syncmer_sampler with minimizer_position_extractor over kmer_view<__uint128_t>.
+ * 1 <= s <= 32 and s <= k <= 64 (bl_scan_syncmers keeps its own limit of 32), W = k - s + 1 <= 64.
+ * The k-mers, their validity and canonical form are bl_scan_kmers128's.  For a valid k-mer of 128-bit value v, s-mer number j from the
+ * first base is x_j = (v >> 2(k-s-j)) & (4^s - 1), j = 0 .. W-1; its hash is bl_hash64_u128(x_j, 0, seed) — the reference's
+ * `km & mask` is a KmerType value, so the key is 16 bytes with a zero high word (kmer_view.hpp:272-275).  The k-mer is a record iff
+ * the smallest j of minimal hash (the leftmost minimum: the `>=` loop of kmer_view.hpp:274-282 runs from the right) equals
+ * start_offset or end_offset; an offset >= W matches nothing.
+ *   d_positions[r] global position of the k-mer, increasing (may be NULL: count only); nothing is written at or beyond `capacity`,
+ *   the result always carries the full count (BL_ERR_CAPACITY when it exceeds capacity).
+ * result: count, xor_pos; the other digest words are 0.
+ * k <= 32 through this entry: the k-mers are those of the 64-bit call, but the s-mer keys are 16 bytes instead of 8, so the records
+ * differ in general from bl_scan_syncmers' — as the reference's template does between KmerType = uint64_t and __uint128_t. */
+int bl_scan_syncmers128(bl_ctx* ctx, const bl_batch* batch, uint64_t first, uint64_t n, uint32_t k, uint32_t s, uint32_t start_offset,
+                        uint32_t end_offset, uint64_t seed, uint32_t flags, uint64_t* d_positions, uint64_t capacity,
+                        bl_result* result);
 
 /* on != 0: every later scan on this context decides its windows on the 64-bit hashes themselves — no pass 1 on the approximate high
  * dword, no closed-syncmer form (§5.4).  Same records, 2-4 % slower; for checks and A/B measurements. */

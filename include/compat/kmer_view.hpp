@@ -12,8 +12,7 @@
 // terminate cleanly instead.  KmerType of up to 8 bytes: k <= 32 (the reference's own limit for uint64_t,
 // kmer_view.hpp:195), through bl_scan_kmers.  KmerType = __uint128_t: k <= 64, through bl_scan_kmers128 — values in 128 bits,
 // canonical = numeric minimum with the reverse complement taken in 2k bits (the reference's reverse-strand update is undefined
-// there for k >= 33).  Not covered for 128-bit k-mers: read_pool lookups (every view scans itself), and
-// hash::minimizer_position_extractor below.
+// there for k >= 33).  Not covered for 128-bit k-mers: read_pool lookups (every view scans itself).
 // Views built on memory handed out by a biolib_amd::read_pool (read_pool.hpp) do not go to the GPU one by one: they
 // index into the single scan of the pool's current batch.
 #ifndef BIOLIB_AMD_COMPAT_KMER_VIEW_HPP
@@ -102,7 +101,7 @@ class kmer_view
                     return std::numeric_limits<KmerType>::max();
                 }
 
-                // the samplers' GPU paths work on 64-bit k-mers: they refuse a view of 128-bit ones at compile time
+                // samplers that run the GPU path themselves pick the 128-bit call by this (those without one refuse at compile time)
                 static constexpr bool wide_kmers = wide;
                 // position of the underlying char iterator, for samplers that run the GPU path themselves
                 kmer_view const* view() const noexcept {return parent_view;}
@@ -245,21 +244,40 @@ namespace hash {
 // offset from the k-mer's left end of its leftmost minimum-hash m-mer, hash64 with seed 0; klen + 1
 // for a null k-mer.  A scalar host function by nature (it takes a single value); the bulk form over a
 // whole sequence is sampler::syncmer_sampler / bl_scan_syncmers.
+// k <= 64 (the reference's only limit, src/kmer_view.cpp:10).  The reference hashes `km & mask` IN KmerType: 8 key bytes for a k-mer
+// of up to 64 bits, 16 bytes — the m-mer and a zero high word, so m <= 32 — for a 128-bit one (bl_hash64_u128; the bulk form is
+// bl_scan_syncmers128).  The two give different offsets for the same k-mer, as they do in the reference.
 class minimizer_position_extractor
 {
     public:
         using value_type = uint64_t;
         minimizer_position_extractor(uint8_t k, uint8_t m) : klen(k), mlen(m)
         {
+            assert(k <= 64);
             assert(m <= k);
             mask = (2 * m != 64) ? ((uint64_t(1) << (2 * m)) - 1) : std::numeric_limits<uint64_t>::max();
         }
         template <typename KmerType>
         std::size_t operator()(wrapper::kmer_context_t<KmerType> const& kmer) const noexcept
         {
-            // the reference hashes `km & mask` in KmerType there — 16 bytes for a 128-bit k-mer, a different extractor: not provided
-            static_assert(sizeof(KmerType) <= 8, "minimizer_position_extractor takes k-mers of up to 64 bits (k <= 32); 128-bit k-mers are not supported here");
+            static_assert(sizeof(KmerType) <= 16, "minimizer_position_extractor takes k-mers of up to 128 bits (k <= 64)");
             if (!kmer.value) return klen + 1;
+            if constexpr (sizeof(KmerType) > 8) {
+                // s-mer number j from the first base: x_j = (v >> 2(k-m-j)) & (4^m - 1), hashed as a 16-byte value with a zero high
+                // word; left to right with a strict '<': the leftmost of equal minima stays
+                const unsigned __int128 v = static_cast<unsigned __int128>(*kmer.value);
+                const unsigned last = static_cast<unsigned>(klen - mlen);
+                unsigned best = 0;
+                uint64_t best_hash = bl_hash64_u128(static_cast<uint64_t>(v >> (2 * last)) & mask, 0, 0);
+                for (unsigned o = 1; o <= last; ++o) {
+                    const uint64_t h = bl_hash64_u128(static_cast<uint64_t>(v >> (2 * (last - o))) & mask, 0, 0);
+                    if (h < best_hash) {
+                        best_hash = h;
+                        best = o;
+                    }
+                }
+                return best;
+            }
             // the k-mer packs its first base in the most significant pair: the m-mer at offset o from the left end is the 2m bits
             // that start 2 * (k - m - o) bits up.  Left to right with a strict '<': the leftmost of equal minima stays.
             const uint64_t packed = static_cast<uint64_t>(*kmer.value);

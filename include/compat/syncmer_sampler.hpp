@@ -10,6 +10,10 @@
 //    position list.  Like the reference, a range [cbegin(), cend()) of a kmer_view never includes the k-mer that
 //    ends the sequence (quirk Q1).  operator* yields the k-mer VALUE (PropertyExtractor::value_type); in the
 //    reference that expression does not compile for this pairing (:104-108).
+//  * A kmer_view of 128-bit k-mers (KmerType = __uint128_t, k <= 64, m <= 32) goes through bl_scan_syncmers128: the m-mers are
+//    hashed as 16-byte keys, as the reference's extractor does in that KmerType.  position() and count() work as for narrow
+//    views; operator* returns PropertyExtractor::value_type = uint64_t, so it yields the k-mer's LOW WORD there (the whole
+//    value is view()->values()[position()]).
 #ifndef BIOLIB_AMD_COMPAT_SYNCMER_SAMPLER_HPP
 #define BIOLIB_AMD_COMPAT_SYNCMER_SAMPLER_HPP
 
@@ -34,7 +38,7 @@ class syncmer_sampler
     static constexpr bool gpu_path = detail::has_view<Iterator>::value and std::is_same<PropertyExtractor, hash::minimizer_position_extractor>::value;
     template <typename It, typename = void> struct wide_view : std::false_type {};
     template <typename It> struct wide_view<It, std::void_t<decltype(It::wide_kmers)>> : std::integral_constant<bool, It::wide_kmers> {};
-    static_assert(not (gpu_path and wide_view<Iterator>::value), "syncmer_sampler over a kmer_view of 128-bit k-mers is not provided (k <= 32)");
+    static constexpr bool wide = wide_view<Iterator>::value;
 
     public:
         class const_iterator
@@ -134,8 +138,13 @@ class syncmer_sampler
                     const std::size_t cap = stop - first;
                     biolib_amd::device_array<uint64_t> dp(cap);
                     bl_result res;
-                    biolib_amd::check(bl_scan_syncmers(biolib_amd::context::get(), batch.b, first, stop - first, k, m, soffset, eoffset, 0,
-                                                       (view->is_canonical() ? (uint32_t)BL_FLAG_CANONICAL : 0u) | BL_FLAG_SYNC, dp.d, cap, &res), "bl_scan_syncmers");
+                    const uint32_t flags = (view->is_canonical() ? (uint32_t)BL_FLAG_CANONICAL : 0u) | BL_FLAG_SYNC;
+                    if constexpr (wide)
+                        biolib_amd::check(bl_scan_syncmers128(biolib_amd::context::get(), batch.b, first, stop - first, k, m, soffset, eoffset, 0, flags, dp.d, cap, &res),
+                                          "bl_scan_syncmers128");
+                    else
+                        biolib_amd::check(bl_scan_syncmers(biolib_amd::context::get(), batch.b, first, stop - first, k, m, soffset, eoffset, 0, flags, dp.d, cap, &res),
+                                          "bl_scan_syncmers");
                     *out = dp.to_host(res.count);
                 }
             }
