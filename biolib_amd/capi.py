@@ -21,7 +21,7 @@ SYMBOLS = [
     "bl_ctx_last_scan_ms", "bl_ctx_set_exact_windows", "bl_ctx_set_option", "bl_ctx_kernel_timing", "bl_ctx_kernel_time", "bl_ctx_mark", "bl_ctx_mark_times", "bl_reader_open", "bl_reader_open_threads", "bl_reader_kind", "bl_reader_next_text", "bl_reader_next_batch_device", "bl_reader_close", "bl_reader_next_record",
     "bl_reader_next_batch", "bl_reader_last_batch", "bl_reader_last_name", "bl_batch_from_text", "bl_run_file_name", "bl_write_run_u64", "bl_write_vector_u64", "bl_file_count_u64", "bl_read_file_u64_host", "bl_read_file_u64", "bl_merge_runs_u64", "bl_count_allreduce",
     "bl_device_alloc", "bl_device_free", "bl_copy_to_host", "bl_copy_to_device", "bl_hash64_u64", "bl_bgzf_walk", "bl_bgzf_inflate", "bl_host_alloc", "bl_host_free", "bl_reader_open_shard", "bl_reader_shard_range",
-    "bl_scan_kmers128", "bl_scan_hash_sample128", "bl_hash64_u128", "bl_scan_syncmers128",
+    "bl_scan_kmers128", "bl_scan_hash_sample128", "bl_hash64_u128", "bl_scan_syncmers128", "bl_scan_minimizers128",
 ]
 
 
@@ -145,6 +145,7 @@ def lib():
     L.bl_scan_kmers128.argtypes = [vp, vp, u64, u64, u32, u64, u32, vp, vp, vp, C.POINTER(Result)]
     L.bl_scan_hash_sample128.argtypes = [vp, vp, u64, u64, u32, u64, u64, u32, vp, vp, vp, u64, C.POINTER(Result)]
     L.bl_scan_syncmers128.argtypes = [vp, vp, u64, u64, u32, u32, u32, u32, u64, u32, vp, u64, C.POINTER(Result)]
+    L.bl_scan_minimizers128.argtypes = [vp, vp, u64, u64, u32, u32, u64, u32, vp, vp, vp, u64, C.POINTER(Result)]
     L.bl_hash64_u128.restype = u64
     L.bl_hash64_u128.argtypes = [u64, u64, u64]
     _lib = L

@@ -17,6 +17,7 @@
 #include "bl_launch.hpp"
 #include "bl_kmers128_launch.hpp"
 #include "bl_syncmers128_launch.hpp"
+#include "bl_minimizers128_launch.hpp"
 
 namespace {
 
@@ -1042,6 +1043,64 @@ int bl_scan_syncmers128(bl_ctx* c, const bl_batch* b, uint64_t first, uint64_t n
         if (e != hipSuccess) return fail(BL_ERR_HIP, std::string("sync128_emit_kernel: ") + hipGetErrorString(e));
     }
     return end_scan(c, 1u << 0, result, d_positions != nullptr, capacity, flags);
+}
+
+// ---- window minimizers of 128-bit k-mers (unit <= 64, w <= 64, 16-byte keys): bl_minimizers128.hip
+
+int bl_scan_minimizers128(bl_ctx* c, const bl_batch* b, uint64_t first, uint64_t n, uint32_t unit, uint32_t w, uint64_t seed, uint32_t flags,
+                          uint64_t* d_values, uint64_t* d_positions, uint64_t* d_hashes, uint64_t capacity, bl_result* result)
+{
+    if (!c || !b || b->ctx != c) return fail(BL_ERR_INVALID, "ctx/batch is NULL or the batch belongs to another context");
+    if (unit < 1 || unit > bl::MAX_UNIT128 || w < 1 || w > bl::MAX_W)
+        return fail(BL_ERR_INVALID, "need 1 <= unit <= 64 and 1 <= w <= 64 (KmerType = __uint128_t, 16-byte unit keys)");
+    bl::Min128Params p{};
+    bool empty;
+    int rc = prepare_kmers128(c, b, first, n, unit, seed, flags, d_values, p.km, result, empty);
+    if (rc != BL_OK || empty) return rc;
+    const bool wants = d_values || d_positions || d_hashes;
+    p.w = (int32_t)w;
+    p.km.rec_value = d_values;
+    p.km.rec_pos = d_positions;
+    p.km.rec_hash = d_hashes;
+    p.km.capacity = wants ? capacity : 0;
+    rc = begin_scan(c);
+    if (rc != BL_OK) return rc;
+    // scratch: tile counts + local prefixes + scan-block totals / prefixes; per lane of every tile one u16 record mask and three
+    // dwords of occurrence offsets (a count-only call keeps neither)
+    const size_t nt = (size_t)p.km.n_tiles, nb = (nt + bl::SCAN_BLK - 1) / bl::SCAN_BLK;
+    rc = grow(c, reinterpret_cast<void**>(&c->cur->tile_buf), &c->cur->tile_buf_bytes, (2 * nt + 2 * nb + 8) * sizeof(unsigned long long));
+    if (rc != BL_OK) return rc;
+    unsigned long long* tb = reinterpret_cast<unsigned long long*>(c->cur->tile_buf);
+    p.km.tile_counts = tb;
+    p.km.tile_base = tb + nt;
+    unsigned long long* block_tot = tb + 2 * nt;
+    p.km.block_base = block_tot + nb;
+    if (wants) {
+        rc = grow(c, reinterpret_cast<void**>(&c->cur->slot_buf), &c->cur->slot_buf_bytes, nt * bl::TPB * (sizeof(uint16_t) + 3 * sizeof(uint32_t)));
+        if (rc != BL_OK) return rc;
+        p.km.lane_masks = c->cur->slot_buf;
+        p.lane_offs = reinterpret_cast<uint32_t*>(c->cur->slot_buf + nt * bl::TPB);  // nt * TPB u16: a multiple of 512 bytes
+    }
+    p.km.shards = c->shards();
+    rc = kernel_event(c, true);
+    if (rc != BL_OK) return rc;
+    hipError_t e = bl::launch_minimizers128_count(p, c->stream);
+    if (e != hipSuccess) return fail(BL_ERR_HIP, std::string("min128_count_kernel: ") + hipGetErrorString(e));
+    rc = kernel_event(c, false);
+    if (rc != BL_OK) return rc;
+    bl::ScanParams sp{};  // the prefix scan reads these four fields, and adds the total to the digest's count
+    sp.tile_counts = p.km.tile_counts;
+    sp.tile_base = p.km.tile_base;
+    sp.block_base = p.km.block_base;
+    sp.shards = p.km.shards;
+    unsigned long long* carry = reinterpret_cast<unsigned long long*>(c->cur->ws);  // header word, zeroed by begin_scan
+    e = bl::launch_tile_scan(sp, bl::GroupRange{0, (uint32_t)p.km.n_tiles}, block_tot, carry, c->stream);
+    if (e != hipSuccess) return fail(BL_ERR_HIP, std::string("tile_scan: ") + hipGetErrorString(e));
+    if (wants) {
+        e = bl::launch_minimizers128_emit(p, c->stream);
+        if (e != hipSuccess) return fail(BL_ERR_HIP, std::string("min128_emit_kernel: ") + hipGetErrorString(e));
+    }
+    return end_scan(c, 1u << 0, result, wants, capacity, flags);
 }
 
 uint64_t bl_hash64_u128(uint64_t lo, uint64_t hi, uint64_t seed) { return bl::murmur64_u128(lo, hi, (uint32_t)seed); }

@@ -450,6 +450,14 @@ class Batch:
         check(self._lib.bl_scan_syncmers128(self.ctx._h, self._h, first, n, k, s, soff, eoff, seed, flags, _ptr(positions), capacity, C.byref(result)))
         return result
 
+    def minimizers128_raw(self, unit, w, seed, flags, first=0, n=0, values=None, positions=None, hashes=None, capacity=0, result=None):
+        """bl_scan_minimizers128 (unit <= 64, w <= 64): `values` holds two words per record, low then high"""
+        result = result if result is not None else Result()
+        self.ctx._hold(result, flags)
+        check(self._lib.bl_scan_minimizers128(self.ctx._h, self._h, first, n, unit, w, seed, flags, _ptr(values), _ptr(positions), _ptr(hashes),
+                                              capacity, C.byref(result)))
+        return result
+
     # ---- convenience wrappers returning host numpy arrays
     def _span(self, first, n):
         end = self.n_bases if not n else min(self.n_bases, first + n)
@@ -651,6 +659,33 @@ class Batch:
                 self._last_count = r.count
             out = r.as_dict()
             out.update(positions=_host_u64(p, int(r.count)))
+            return out
+
+        return self._with_capacity(guess, run)
+
+    def minimizers128(self, unit, w, seed=0, canonical=False, drop_last=False, first=0, n=0, capacity=None, arrays=True):
+        """window minimizers of k-mers up to k = 64 (minimizer_sampler over kmer_view<__uint128_t>): as minimizers(), with the units hashed
+        as 16-byte keys, hash64_u128(lo, hi, seed), and drop_last honoured for every w.  values has shape (count, 2) as in kmers128."""
+        import torch
+
+        span = self._span(first, n)
+        if not arrays:
+            r = self.minimizers128_raw(unit, w, seed, _flags(canonical, drop_last, True), first, n)
+            return dict(r.as_dict(), redone=int(r.redone))
+        guess = capacity if capacity is not None else int(span * 2.6 / (w + 1)) + 4096
+        c = self.ctx
+
+        def run(cap):
+            v = torch.empty((cap, 2), dtype=torch.int64, device=c.torch_device)
+            p, h = c.empty_u64(cap), c.empty_u64(cap)
+            r = Result()
+            try:
+                self.minimizers128_raw(unit, w, seed, _flags(canonical, drop_last, True), first, n, v, p, h, cap, r)
+            finally:
+                self._last_count = r.count
+            cnt = int(r.count)
+            out = dict(r.as_dict(), redone=int(r.redone))
+            out.update(values=v[:cnt].cpu().numpy().view(np.uint64).copy().reshape(cnt, 2), positions=_host_u64(p, cnt), hashes=_host_u64(h, cnt))
             return out
 
         return self._with_capacity(guess, run)

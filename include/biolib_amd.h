@@ -14,6 +14,7 @@
  *                        sampler::minimizer_sampler<It,Hash>              include/minimizer_sampler.hpp:12-70
  *   bl_scan_super_kmers  wrapper::super_kmer_view<K,M,hash64>             include/super_kmer_view.hpp:11-58, 121-135
  *   bl_scan_super_kmer_records  the same groups as self-contained records  include/super_kmer_view.hpp:20-24 (the record), §8f rank 4
+ *   bl_scan_minimizers128  sampler::minimizer_sampler over kmer_view<__uint128_t,It>  unit <= 64, w <= 64; unit keys of 16 bytes
  *   bl_scan_syncmers     sampler::syncmer_sampler<It,minimizer_position_extractor>
  *                                                                         include/syncmer_sampler.hpp:9-137, include/kmer_view.hpp:250-283
  *   bl_scan_syncmers128  the same sampler over kmer_view<__uint128_t,It>  k <= 64, s <= 32; s-mer keys of 16 bytes (kmer_view.hpp:266-283 in KmerType)
@@ -163,7 +164,7 @@ int bl_scan_kmers(bl_ctx* ctx, const bl_batch* batch, uint64_t first, uint64_t n
  * result: count, xor_value := XOR of the low words, aux := XOR of the high words, xor_hash, xor_pos := wrapping sum of hashes.
  * 1 <= k <= 64 (bl_scan_kmers keeps its own limit of 32).
  * NOT covered for k > 32: 128-bit keys in bl_sort_unique_u64 / bl_jaccard_sorted_u64 / bl_partition_u64 and the spill formats (the
- * 64-bit HASHES of the records are keys those calls take), biolib_amd::read_pool, and the super-k-mer records / counter.  (Syncmers: bl_scan_syncmers128.) */
+ * 64-bit HASHES of the records are keys those calls take), biolib_amd::read_pool, and the super-k-mer records / counter.  (Syncmers: bl_scan_syncmers128; window minimizers: bl_scan_minimizers128.) */
 int bl_scan_kmers128(bl_ctx* ctx, const bl_batch* batch, uint64_t first, uint64_t n, uint32_t k, uint64_t seed, uint32_t flags,
                      uint64_t* d_values /* 2 per position: lo, hi */, uint64_t* d_hashes, uint8_t* d_valid, bl_result* result);
 
@@ -191,6 +192,34 @@ int bl_scan_hash_sample(bl_ctx* ctx, const bl_batch* batch, uint64_t first, uint
 int bl_scan_hash_sample128(bl_ctx* ctx, const bl_batch* batch, uint64_t first, uint64_t n, uint32_t k, uint64_t seed, uint64_t threshold,
                            uint32_t flags, uint64_t* d_values /* 2 per record */, uint64_t* d_positions, uint64_t* d_hashes,
                            uint64_t capacity, bl_result* result);
+
+/* window minimizers of k-mers up to k = 64: sampler::minimizer_sampler over kmer_view<__uint128_t> (the reference's
+ * minimizer_sampler.hpp does not compile; this is bl_scan_minimizers' contract evaluated in KmerType = __uint128_t).
+ *   units     the k-mers of bl_scan_kmers128, 1 <= unit <= 64: the same value, validity and canonical form; a unit's hash is
+ *             bl_hash64_u128(lo, hi, seed) — 16 key bytes whatever `unit` is
+ *   windows   w consecutive unit start positions p .. p+w-1, 1 <= w <= 64; the window exists iff all w units are valid (hence one
+ *             sequence, one break-free run).  Its occurrence is the position of the smallest hash, the LEFTMOST of equal ones
+ *   records   window p yields one iff it exists and window p-1 does not exist or has its occurrence at another position:
+ *             d_values[2r], d_values[2r+1] the unit (low word, high word; d_values must be 16-byte aligned, else BL_ERR_INVALID),
+ *             d_positions[r] the global start of the unit, d_hashes[r] its hash
+ *   range     [first, first+n) takes the windows whose first base lies in it; units behind the range are read as needed, and window
+ *             first-1 in front of it, so consecutive ranges concatenate exactly to the scan of their union.  n = 0: to the end
+ *   BL_FLAG_DROP_LAST  the unit that ends its sequence is no item (as in bl_scan_kmers128) and takes part in no window: what a
+ *             kmer_view range [cbegin, cend) gives the sampler (quirk Q1).  bl_scan_minimizers honours the flag for its w = 1 unit
+ *             lists only; this call honours it for every w
+ *   capacity  nothing is written at or beyond `capacity`; the result always carries the full count (BL_ERR_CAPACITY when it exceeds
+ *             capacity).  Any of the three arrays may be NULL; with all three NULL the call only counts
+ * result: count, xor_value := XOR of the low words, aux := XOR of the high words, xor_hash, xor_pos := XOR of the positions, redone = 0
+ * (the windows are decided on the 64-bit hashes themselves: there is no approximate pass).
+ * unit <= 32 through this entry: the values are bl_scan_minimizers' with a zero high word, but the key is 16 bytes instead of 8, so
+ * the records differ in general — as the reference's template does between KmerType = uint64_t and __uint128_t.  w = 1 lists every
+ * valid unit: bl_scan_hash_sample128 at threshold = UINT64_MAX, short of a unit whose hash is exactly 2^64 - 1.
+ * bl_scan_minimizers keeps its limit of 32.  NOT provided: minimizer_view / super_kmer_view with m > 32, super-k-mer records and the
+ * counter for k > 32, 128-bit keys in sort / Jaccard / partition / spill, read_pool, and a read-tiled or approximate-hash variant of
+ * this kernel. */
+int bl_scan_minimizers128(bl_ctx* ctx, const bl_batch* batch, uint64_t first, uint64_t n, uint32_t unit, uint32_t w, uint64_t seed,
+                          uint32_t flags, uint64_t* d_values /* 2 per record */, uint64_t* d_positions, uint64_t* d_hashes,
+                          uint64_t capacity, bl_result* result);
 
 /* super-k-mers (C4): maximal groups of consecutive k-mers sharing one minimizer occurrence
  * (m-mer, w = k - m + 1):

@@ -10,6 +10,8 @@
 //    on the GPU by bl_scan_minimizers(unit = k, w = window_size); operator* yields the minimizer's kmer_context_t
 //    (value, position of the k-mer in the view, id = position).  As with the reference, the k-mer that ends the sequence is
 //    outside [cbegin(), cend()) of a kmer_view (quirk Q1) and takes no part in any window.
+//    Over kmer_view<__uint128_t> (k <= 64) the call is bl_scan_minimizers128: the same windows over 128-bit values hashed as
+//    16-byte keys, as hash::hash64::hash<__uint128_t> does; operator* yields the kmer_context_t with the 128-bit value.
 //  * any other pairing: evaluated element by element on the host with the same rules (items must be optional-like).
 #ifndef BIOLIB_AMD_COMPAT_MINIMIZER_SAMPLER_HPP
 #define BIOLIB_AMD_COMPAT_MINIMIZER_SAMPLER_HPP
@@ -32,7 +34,7 @@ class minimizer_sampler
     static constexpr bool gpu_path = has_view<Iterator>::value and std::is_same<HashFunctionFamily, hash::hash64>::value;
     template <typename It, typename = void> struct wide_view : std::false_type {};
     template <typename It> struct wide_view<It, std::void_t<decltype(It::wide_kmers)>> : std::integral_constant<bool, It::wide_kmers> {};
-    static_assert(not (gpu_path and wide_view<Iterator>::value), "minimizer_sampler over a kmer_view of 128-bit k-mers is not provided (hashed units are at most 32 bases)");
+    static constexpr bool wide_path = gpu_path and wide_view<Iterator>::value;
 
     public:
         class const_iterator
@@ -92,17 +94,29 @@ class minimizer_sampler
                     // the last k-mer taken starts at stop - 1 and ends at stop + k - 2
                     biolib_amd::batch_handle batch(chars.data(), stop + k - 1);
                     const std::size_t cap = stop - first;
-                    biolib_amd::device_array<uint64_t> dv(cap), dp(cap);
+                    const uint32_t flags = (view->is_canonical() ? (uint32_t)BL_FLAG_CANONICAL : 0u) | BL_FLAG_SYNC;
+                    using kmer_type = typename decltype(item_type::value)::value_type;
                     bl_result res;
-                    biolib_amd::check(bl_scan_minimizers(biolib_amd::context::get(), batch.b, first, stop - first, k, w, mseed,
-                                                         (view->is_canonical() ? (uint32_t)BL_FLAG_CANONICAL : 0u) | BL_FLAG_SYNC, dv.d, dp.d, nullptr, cap, &res),
-                                      "bl_scan_minimizers");
-                    auto values = dv.to_host(res.count);
-                    auto positions = dp.to_host(res.count);
-                    out->reserve(res.count);
-                    for (std::size_t i = 0; i < res.count; ++i)
-                        out->push_back(item_type{static_cast<typename decltype(item_type::value)::value_type>(values[i]), static_cast<std::size_t>(positions[i]),
-                                                 static_cast<std::size_t>(positions[i])});
+                    if constexpr (wide_path) {
+                        biolib_amd::device_array<uint64_t> dv(2 * cap), dp(cap);
+                        biolib_amd::check(bl_scan_minimizers128(biolib_amd::context::get(), batch.b, first, stop - first, k, w, mseed, flags, dv.d, dp.d, nullptr, cap, &res),
+                                          "bl_scan_minimizers128");
+                        auto values = dv.to_host(2 * res.count);
+                        auto positions = dp.to_host(res.count);
+                        out->reserve(res.count);
+                        for (std::size_t i = 0; i < res.count; ++i)
+                            out->push_back(item_type{(static_cast<kmer_type>(values[2 * i + 1]) << 64) | static_cast<kmer_type>(values[2 * i]),
+                                                     static_cast<std::size_t>(positions[i]), static_cast<std::size_t>(positions[i])});
+                    } else {
+                        biolib_amd::device_array<uint64_t> dv(cap), dp(cap);
+                        biolib_amd::check(bl_scan_minimizers(biolib_amd::context::get(), batch.b, first, stop - first, k, w, mseed, flags, dv.d, dp.d, nullptr, cap, &res),
+                                          "bl_scan_minimizers");
+                        auto values = dv.to_host(res.count);
+                        auto positions = dp.to_host(res.count);
+                        out->reserve(res.count);
+                        for (std::size_t i = 0; i < res.count; ++i)
+                            out->push_back(item_type{static_cast<kmer_type>(values[i]), static_cast<std::size_t>(positions[i]), static_cast<std::size_t>(positions[i])});
+                    }
                 }
             } else {
                 // host evaluation of the same rules over optional-like items

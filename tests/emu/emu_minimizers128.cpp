@@ -1,0 +1,232 @@
+// TEST INFRASTRUCTURE: the per-thread bodies of bl_scan_minimizers128 (biolib_amd/csrc/bl_minimizers128_core.hpp) run on the host — a
+// workgroup's phases lane by lane, host arrays standing in for LDS — under AddressSanitizer / UBSan, against a plain
+// `unsigned __int128` evaluation of the rule written here.  Built and run by tests/test_emu_minimizers128.py, which compares the
+// digests printed below with its own Python model.
+//
+//   emu_minimizers128 <batch file> <unit> <w> <first> <n>
+// batch file: u64 n_bases, u64 n_seqs, u64 offsets[n_seqs + 1], bases.  For canonical x drop_last it prints
+//   min <canonical> <drop_last> count xor_value aux xor_hash xor_pos
+// and exits non-zero on the first disagreement with the plain evaluation.
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <vector>
+
+#include "../../biolib_amd/csrc/bl_minimizers128_core.hpp"
+
+typedef unsigned __int128 u128;
+
+static int nt4(uint8_t c)
+{
+    switch (c) {
+        case 'A': case 'a': return 0;
+        case 'C': case 'c': return 1;
+        case 'G': case 'g': return 2;
+        case 'T': case 't': case 'U': case 'u': return 3;
+        default: return 4;
+    }
+}
+
+static uint64_t rotl(uint64_t x, int r) { return (x << r) | (x >> (64 - r)); }
+static uint64_t fmix(uint64_t k)
+{
+    k ^= k >> 33; k *= 0xff51afd7ed558ccdULL; k ^= k >> 33; k *= 0xc4ceb9fe1a85ec53ULL; k ^= k >> 33;
+    return k;
+}
+// MurmurHash3_x64_128 of the 16 bytes of v, first word (written out here: no code shared with the header under test)
+static uint64_t plain_hash(u128 v, uint32_t seed)
+{
+    const uint64_t c1 = 0x87c37b91114253d5ULL, c2 = 0x4cf5ad432745937fULL;
+    uint64_t k1 = (uint64_t)v, k2 = (uint64_t)(v >> 64), h1 = seed, h2 = seed;
+    k1 *= c1; k1 = rotl(k1, 31); k1 *= c2; h1 ^= k1;
+    h1 = rotl(h1, 27); h1 += h2; h1 = h1 * 5 + 0x52dce729;
+    k2 *= c2; k2 = rotl(k2, 33); k2 *= c1; h2 ^= k2;
+    h2 = rotl(h2, 31); h2 += h1; h2 = h2 * 5 + 0x38495ab5;
+    h1 ^= 16; h2 ^= 16;
+    h1 += h2; h2 += h1;
+    h1 = fmix(h1); h2 = fmix(h2);
+    return h1 + h2;
+}
+
+struct Plain {
+    std::vector<uint8_t> valid;
+    std::vector<u128> value;
+    std::vector<uint64_t> hash;
+    std::vector<int64_t> occ;  // per window start: the occurrence's position, -1 where no window
+};
+
+static Plain plain_scan(const std::vector<uint8_t>& seq, const std::vector<uint64_t>& offs, int k, int w, uint32_t seed, bool canonical, bool drop_last)
+{
+    const size_t n = seq.size();
+    Plain r{std::vector<uint8_t>(n, 0), std::vector<u128>(n, 0), std::vector<uint64_t>(n, 0), std::vector<int64_t>(n, -1)};
+    const u128 mask = k == 64 ? ~(u128)0 : (((u128)1 << (2 * k)) - 1);
+    for (size_t q = 0; q + 1 < offs.size(); ++q) {
+        u128 fwd = 0, rc = 0;
+        int run = 0;
+        for (uint64_t i = offs[q]; i < offs[q + 1]; ++i) {
+            const int c = nt4(seq[i]);
+            if (c > 3) { run = 0; continue; }
+            fwd = ((fwd << 2) | (u128)c) & mask;
+            rc = (rc >> 2) | ((u128)(3 ^ c) << (2 * (k - 1)));
+            if (++run < k) continue;
+            if (drop_last && i + 1 == offs[q + 1]) continue;
+            const u128 v = canonical && rc < fwd ? rc : fwd;
+            r.valid[i + 1 - k] = 1;
+            r.value[i + 1 - k] = v;
+            r.hash[i + 1 - k] = plain_hash(v, seed);
+        }
+    }
+    for (size_t p = 0; p + w <= n; ++p) {
+        int64_t arg = (int64_t)p;
+        bool all = true;
+        for (size_t j = p; j < p + w; ++j) {
+            all = all && r.valid[j];
+            if (r.hash[j] < r.hash[arg]) arg = (int64_t)j;  // strict: the leftmost minimum stays
+        }
+        if (all) r.occ[p] = arg;
+    }
+    return r;
+}
+
+#define CHECK(cond, ...)                          \
+    do {                                          \
+        if (!(cond)) {                            \
+            std::fprintf(stderr, "emu_minimizers128: " __VA_ARGS__); \
+            std::fprintf(stderr, "\n");           \
+            std::exit(1);                         \
+        }                                         \
+    } while (0)
+
+int main(int argc, char** argv)
+{
+    CHECK(argc == 6, "usage: emu_minimizers128 <batch file> <unit> <w> <first> <n>");
+    FILE* f = std::fopen(argv[1], "rb");
+    CHECK(f, "cannot open %s", argv[1]);
+    uint64_t hdr[2];
+    CHECK(std::fread(hdr, 8, 2, f) == 2, "short file");
+    const uint64_t n_bases = hdr[0], n_seqs = hdr[1];
+    std::vector<uint64_t> offs(n_seqs + 1);
+    CHECK(std::fread(offs.data(), 8, n_seqs + 1, f) == n_seqs + 1, "short file");
+    std::vector<uint8_t> seq(n_bases);
+    CHECK(n_bases == 0 || std::fread(seq.data(), 1, n_bases, f) == n_bases, "short file");
+    std::fclose(f);
+    const int k = std::atoi(argv[2]), w = std::atoi(argv[3]);
+    const uint64_t first = std::strtoull(argv[4], nullptr, 10), n_arg = std::strtoull(argv[5], nullptr, 10);
+    const uint64_t end = (n_arg == 0 || first + n_arg > n_bases) ? n_bases : first + n_arg;
+    const uint32_t seed = 0x9e3779b9u;
+    const uint64_t origin = 1000000007ull;
+    CHECK(k >= 1 && k <= bl::MAX_UNIT128 && w >= 1 && w <= bl::MAX_W && first < end, "bad arguments");
+
+    // an exact-size heap copy of the bases (16-byte aligned as the device buffer is; the sanitizer sees every byte past n_bases)
+    uint8_t* exact = static_cast<uint8_t*>(std::malloc(n_bases ? n_bases : 1));
+    std::memcpy(exact, seq.data(), n_bases);
+    std::vector<uint32_t> start_bits((n_bases + 31) / 32 + 4, 0);
+    for (uint64_t q = 0; q < n_seqs; ++q)
+        if (offs[q] < n_bases) start_bits[offs[q] >> 5] |= 1u << (offs[q] & 31);
+
+    for (int canonical = 0; canonical < 2; ++canonical) {
+        for (int drop_last = 0; drop_last < 2; ++drop_last) {
+            const Plain want = plain_scan(seq, offs, k, w, seed, canonical, drop_last);
+            auto is_record = [&](int64_t q) {
+                if (q < (int64_t)first || q >= (int64_t)end || want.occ[q] < 0) return false;
+                return q == 0 || want.occ[q - 1] != want.occ[q];
+            };
+            bl::Min128Params p{};
+            p.km.bases = exact;
+            p.km.n_bases = (int64_t)n_bases;
+            p.km.start_bits = start_bits.data();
+            p.km.pos_base = (int64_t)origin;
+            bl::plan_kmers128((int64_t)first, (int64_t)end, p.km);
+            p.km.unit = k;
+            p.km.seed = seed;
+            p.km.canonical = canonical;
+            p.km.drop_last = drop_last;
+            p.w = w;
+            bl::ScanParams lp{};
+            lp.bases = p.km.bases;
+            lp.n_bases = p.km.n_bases;
+            lp.start_bits = p.km.start_bits;
+            // exact sizes: a read or write outside them is a finding
+            std::vector<uint32_t> codes(bl::MIN128_NCHUNK), flags(bl::MIN128_NCHUNK);
+            std::vector<uint64_t> lds(bl::MIN128_SLOTS);
+            std::vector<uint16_t> valid(bl::MIN128_NVALID);
+            std::vector<uint16_t> masks((size_t)p.km.n_tiles * bl::TPB);
+            std::vector<uint32_t> lane_offs((size_t)p.km.n_tiles * 3 * bl::TPB);  // as pass 1 leaves them for pass 2
+            std::vector<unsigned long long> tile_counts(p.km.n_tiles), tile_base(p.km.n_tiles);
+            bl::Kmer128Acc acc{0, 0, 0, 0, 0};
+            for (int tile = 0; tile < p.km.n_tiles; ++tile) {
+                const int64_t r0 = p.km.origin + (int64_t)tile * bl::H - 16;
+                for (int c = 0; c < bl::MIN128_NCHUNK; ++c) bl::stage_chunk(lp, codes.data(), flags.data(), c, r0);
+                // every phase between two barriers runs for all lanes before the next one starts.  The arrays are zeroed first: a
+                // window that read a word phase A did not write would find a minimum (or an invalid unit) there
+                std::fill(lds.begin(), lds.end(), 0);
+                std::fill(valid.begin(), valid.end(), 0);
+                for (int tid = 0; tid < bl::TPB; ++tid) bl::min128_hash_thread(p, codes.data(), flags.data(), lds.data(), valid.data(), tid, r0);
+                unsigned long long cnt = 0;
+                for (int tid = 0; tid < bl::TPB; ++tid) {
+                    bl::Min128Offs o;
+                    const uint32_t sel = bl::min128_window_thread(p, lds.data(), valid.data(), tid, r0, o);
+                    bl::min128_digest_thread(p.km, codes.data(), lds.data(), tid, r0, sel, o, acc);
+                    masks[(size_t)tile * bl::TPB + tid] = (uint16_t)sel;
+                    bl::min128_offs_store(lane_offs.data(), tile, tid, o);
+                    cnt += (unsigned)__builtin_popcount(sel);
+                    for (int t = 0; t < bl::S; ++t) {
+                        const int64_t q = r0 + 16 * (tid + 1) + t;
+                        const bool rec = q >= 0 && q < (int64_t)n_bases && is_record(q);
+                        CHECK(((sel >> t) & 1u) == (rec ? 1u : 0u), "unit=%d w=%d canonical=%d drop_last=%d window %lld: lane says %u", k, w, canonical, drop_last,
+                              (long long)q, (sel >> t) & 1u);
+                        if (rec) CHECK(q + bl::min128_off(o, t) == want.occ[q], "unit=%d w=%d window %lld: offset %d, occurrence %lld", k, w, (long long)q, bl::min128_off(o, t), (long long)want.occ[q]);
+                    }
+                }
+                tile_counts[tile] = cnt;
+            }
+            std::vector<uint64_t> w_pos, w_hash;
+            std::vector<u128> w_val;
+            unsigned long long x_lo = 0, x_hi = 0, x_h = 0, x_pos = 0;
+            for (uint64_t q = first; q < end; ++q)
+                if (is_record((int64_t)q)) {
+                    const int64_t o = want.occ[q];
+                    w_pos.push_back((uint64_t)o + origin);
+                    w_val.push_back(want.value[o]);
+                    w_hash.push_back(want.hash[o]);
+                    x_lo ^= (uint64_t)want.value[o];
+                    x_hi ^= (uint64_t)(want.value[o] >> 64);
+                    x_h ^= want.hash[o];
+                    x_pos ^= (uint64_t)o + origin;
+                }
+            unsigned long long total = 0;
+            for (int tile = 0; tile < p.km.n_tiles; ++tile) {
+                tile_base[tile] = total;
+                total += tile_counts[tile];
+            }
+            CHECK(total == w_pos.size() && acc.xlo == x_lo && acc.xhi == x_hi && acc.xh == x_h && acc.sx == x_pos, "count / digest unit=%d w=%d: %llu, want %zu", k, w,
+                  total, w_pos.size());
+            // the record pass: once with room for everything, once one record short
+            for (int pass = 0; pass < 2; ++pass) {
+                const uint64_t cap = pass == 0 ? total : (total ? total - 1 : 0);
+                std::vector<bl::U64x2> rv(cap);  // exact sizes
+                std::vector<uint64_t> rp(cap), rh(cap);
+                p.km.rec_value = reinterpret_cast<uint64_t*>(rv.data());
+                p.km.rec_pos = rp.data();
+                p.km.rec_hash = rh.data();
+                p.km.capacity = cap;
+                for (int tile = 0; tile < p.km.n_tiles; ++tile) {
+                    const int64_t r0 = p.km.origin + (int64_t)tile * bl::H - 16;
+                    for (int c = 0; c < bl::MIN128_NCHUNK; ++c) bl::stage_chunk(lp, codes.data(), flags.data(), c, r0);
+                    uint64_t at = tile_base[tile];
+                    for (int tid = 0; tid < bl::TPB; ++tid) {
+                        const uint32_t sel = masks[(size_t)tile * bl::TPB + tid];
+                        bl::min128_emit_thread(p.km, codes.data(), tid, r0, sel, bl::min128_offs_load(lane_offs.data(), tile, tid), at);
+                        at += (unsigned)__builtin_popcount(sel);
+                    }
+                }
+                for (uint64_t r = 0; r < cap; ++r)
+                    CHECK(rp[r] == w_pos[r] && rh[r] == w_hash[r] && rv[r].lo == (uint64_t)w_val[r] && rv[r].hi == (uint64_t)(w_val[r] >> 64), "record %llu unit=%d w=%d",
+                          (unsigned long long)r, k, w);
+            }
+            std::printf("min %d %d %llu %llu %llu %llu %llu\n", canonical, drop_last, total, acc.xlo, acc.xhi, acc.xh, acc.sx);
+        }
+    }
+    std::free(exact);
+    return 0;
+}
