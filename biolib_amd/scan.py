@@ -234,6 +234,54 @@ class Context:
             check(self._lib.bl_expand_super_kmers(self._h, C.c_void_p(records.data_ptr()), n, int(k), flags, C.c_void_p(out.data_ptr()), need.value, C.byref(need)))
         return out[: need.value]
 
+    def partition_records128(self, hashes, records, parts, n=None):
+        """(bucketed copy of the 32-byte records[:n] — int64[n, 4] —, sizes[parts]): bucket b = records with hashes[i] % parts == b"""
+        import torch
+
+        n = records.shape[0] if n is None else int(n)
+        self._inputs_ready()
+        out = torch.empty((max(n, 1), 4), dtype=torch.int64, device=self.torch_device)
+        counts = (C.c_uint64 * int(parts))()
+        check(self._lib.bl_partition_records128(self._h, C.c_void_p(hashes.data_ptr()), C.c_void_p(records.data_ptr()), n, int(parts), C.c_void_p(out.data_ptr()), counts))
+        return out[:n], [int(c) for c in counts]
+
+    def expand_super_kmers128(self, records, k, canonical=True, n=None):
+        """the 128-bit k-mers (device tensor int64[n_kmers, 2]: low, high) the 32-byte super-k-mer records stand for, group after group"""
+        import torch
+
+        n = records.shape[0] if n is None else int(n)
+        self._inputs_ready()
+        need = C.c_uint64()
+        flags = FLAG_CANONICAL if canonical else 0
+        rc = self._lib.bl_expand_super_kmers128(self._h, C.c_void_p(records.data_ptr()), n, int(k), flags, None, 0, C.byref(need))
+        if rc not in (0, capi.BL_ERR_CAPACITY):
+            check(rc)
+        out = torch.empty((max(need.value, 1), 2), dtype=torch.int64, device=self.torch_device)
+        if need.value:
+            check(self._lib.bl_expand_super_kmers128(self._h, C.c_void_p(records.data_ptr()), n, int(k), flags, C.c_void_p(out.data_ptr()), need.value, C.byref(need)))
+        return out[: need.value]
+
+    def count_super_kmers128(self, records, k, m, seed=0, canonical=True, n=None):
+        """(distinct 128-bit k-mers int64[d, 2] — low, high —, multiplicities int32[d]) of the 32-byte super-k-mer records, in no particular
+        order (bl_count_super_kmers128)"""
+        import torch
+
+        n = records.shape[0] if n is None else int(n)
+        self._inputs_ready()
+        flags = FLAG_CANONICAL if canonical else 0
+        need = C.c_uint64()
+        cap = int(n * (k - m + 1) * 0.62) + 4096  # groups average ~ (w+1)/2 k-mers; retried with the exact need if short
+        while True:
+            keys = torch.empty((cap, 2), dtype=torch.int64, device=self.torch_device)
+            cnts = torch.empty(cap, dtype=torch.int32, device=self.torch_device)
+            rc = self._lib.bl_count_super_kmers128(self._h, C.c_void_p(records.data_ptr()), n, int(k), int(m), int(seed), flags, C.c_void_p(keys.data_ptr()),
+                                                   C.c_void_p(cnts.data_ptr()), cap, C.byref(need))
+            if rc == capi.BL_ERR_CAPACITY:
+                cap = int(need.value) + 64
+                continue
+            check(rc)
+            return keys[: need.value], cnts[: need.value]
+
     def read_file_u64(self, path, with_count=False):
         """a run file (raw sorted u64) or, with_count, an io::basic_store'd vector<uint64_t> of biolib -> device tensor"""
         n = C.c_uint64()
@@ -595,6 +643,31 @@ class Batch:
             recs = torch.empty((max(cnt, 1), 2), dtype=torch.int64, device=c.torch_device)
             check(self._lib.bl_pack_super_kmers(c._h, self._h, C.c_void_p(fp.data_ptr()), C.c_void_p(sz.data_ptr()), C.c_void_p(mp.data_ptr()), cnt, int(k), int(m),
                                                 C.c_void_p(recs.data_ptr())))
+            c.sync()
+            return recs[:cnt], hs[:cnt]
+
+        return self._with_capacity(int(span * 2.4 / (k - m + 2)) + 4096, run)
+
+    def super_kmer_records128(self, k, m, seed=0, canonical=False, first=0, n=0):
+        """(records int64[n, 4], minimizer hashes int64[n]) on the device: the 32-byte super-k-mer records of the range for k up to 64, by
+        bl_scan_super_kmers + bl_pack_super_kmers128"""
+        import torch
+
+        span = self._span(first, n)
+        c = self.ctx
+
+        def run(cap):
+            hs = c.empty_u64(cap)
+            fp, sz, mp = c.empty_u64(cap), c.empty_u8(cap), c.empty_u8(cap)
+            r = Result()
+            try:
+                self.super_kmers_raw(k, m, seed, _flags(canonical, False, True), first, n, None, fp, mp, sz, hs, cap, r)
+            finally:
+                self._last_count = r.count
+            cnt = int(r.count)
+            recs = torch.empty((max(cnt, 1), 4), dtype=torch.int64, device=c.torch_device)
+            check(self._lib.bl_pack_super_kmers128(c._h, self._h, C.c_void_p(fp.data_ptr()), C.c_void_p(sz.data_ptr()), C.c_void_p(mp.data_ptr()), cnt, int(k), int(m),
+                                                   C.c_void_p(recs.data_ptr())))
             c.sync()
             return recs[:cnt], hs[:cnt]
 

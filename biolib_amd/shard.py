@@ -251,9 +251,19 @@ def count_kmers_via_super_kmers(ctx, batch, k, m, seed=0, canonical=True, group=
     All occurrences of a canonical k-mer share their minimizer value, so they meet on one rank and its local count is
     the global one.  ~1.8 bytes per input base cross the links instead of 8 bytes per k-mer.  Works without a process
     group (single GPU); force_exchange runs the all-to-all even at world size 1 (tests).  Returns (distinct k-mers,
-    multiplicities) owned by this rank, as device tensors, in no particular order."""
+    multiplicities) owned by this rank, as device tensors, in no particular order.
+
+    k > 32 or 2k - m > 59 (what a 16-byte record holds) takes the wide calls: 32-byte records (bl_pack_super_kmers128,
+    bl_partition_records128) and 128-bit k-mers (bl_count_super_kmers128); the distinct k-mers then come as an (n, 2) tensor of
+    (low, high) words.  Smaller shapes keep the 16-byte path and a 1-D tensor."""
     import torch.distributed as dist
 
+    if k > 32 or 2 * k - m > 59:
+        recs, hashes = batch.super_kmer_records128(k, m, seed=seed, canonical=canonical)
+        if dist.is_available() and dist.is_initialized() and (dist.get_world_size(group) > 1 or force_exchange):
+            bucketed, counts = ctx.partition_records128(hashes, recs, dist.get_world_size(group))
+            recs = exchange(bucketed, counts, group)
+        return ctx.count_super_kmers128(recs, k, m, seed=seed, canonical=canonical)
     recs, hashes = batch.super_kmer_records(k, m, seed=seed, canonical=canonical)
     if dist.is_available() and dist.is_initialized() and (dist.get_world_size(group) > 1 or force_exchange):
         bucketed, counts = ctx.partition_records(hashes, recs, dist.get_world_size(group))

@@ -164,7 +164,8 @@ int bl_scan_kmers(bl_ctx* ctx, const bl_batch* batch, uint64_t first, uint64_t n
  * result: count, xor_value := XOR of the low words, aux := XOR of the high words, xor_hash, xor_pos := wrapping sum of hashes.
  * 1 <= k <= 64 (bl_scan_kmers keeps its own limit of 32).
  * NOT covered for k > 32: 128-bit keys in bl_sort_unique_u64 / bl_jaccard_sorted_u64 / bl_partition_u64 and the spill formats (the
- * 64-bit HASHES of the records are keys those calls take), biolib_amd::read_pool, and the super-k-mer records / counter.  (Syncmers: bl_scan_syncmers128; window minimizers: bl_scan_minimizers128.) */
+ * 64-bit HASHES of the records are keys those calls take), and biolib_amd::read_pool.  (Syncmers: bl_scan_syncmers128; window minimizers: bl_scan_minimizers128; super-k-mer records and the exact
+ * counter: bl_pack_super_kmers128 .. bl_count_super_kmers128.) */
 int bl_scan_kmers128(bl_ctx* ctx, const bl_batch* batch, uint64_t first, uint64_t n, uint32_t k, uint64_t seed, uint32_t flags,
                      uint64_t* d_values /* 2 per position: lo, hi */, uint64_t* d_hashes, uint8_t* d_valid, bl_result* result);
 
@@ -214,9 +215,9 @@ int bl_scan_hash_sample128(bl_ctx* ctx, const bl_batch* batch, uint64_t first, u
  * unit <= 32 through this entry: the values are bl_scan_minimizers' with a zero high word, but the key is 16 bytes instead of 8, so
  * the records differ in general — as the reference's template does between KmerType = uint64_t and __uint128_t.  w = 1 lists every
  * valid unit: bl_scan_hash_sample128 at threshold = UINT64_MAX, short of a unit whose hash is exactly 2^64 - 1.
- * bl_scan_minimizers keeps its limit of 32.  NOT provided: minimizer_view / super_kmer_view with m > 32, super-k-mer records and the
- * counter for k > 32, 128-bit keys in sort / Jaccard / partition / spill, read_pool, and a read-tiled or approximate-hash variant of
- * this kernel. */
+ * bl_scan_minimizers keeps its limit of 32.  NOT provided: minimizer_view / super_kmer_view with m > 32, 128-bit keys in
+ * sort / Jaccard / partition / spill, read_pool, and a read-tiled or approximate-hash variant of this kernel.  (Super-k-mer records and
+ * the counter for k > 32: bl_pack_super_kmers128 .. bl_count_super_kmers128.) */
 int bl_scan_minimizers128(bl_ctx* ctx, const bl_batch* batch, uint64_t first, uint64_t n, uint32_t unit, uint32_t w, uint64_t seed,
                           uint32_t flags, uint64_t* d_values /* 2 per record */, uint64_t* d_positions, uint64_t* d_hashes,
                           uint64_t capacity, bl_result* result);
@@ -264,6 +265,8 @@ int bl_ctx_set_exact_windows(bl_ctx* ctx, int on);
  *                                 where that layout applies)
  *   "emit_lds_bytes"  0 or bytes  two-lane contexts: LDS footprint the record pass's workgroups are padded to, which caps how many of
  *                                 them a CU holds beside the next scan's hashing pass (0: the built-in default per scan kind)
+ *   "count128_tables" 0 / 1       0: bl_count_super_kmers128 counts every bucket by expand + sort + run-length instead of the LDS tables
+ *                                 (default 1)
  * The library reads no environment variable on the scan path. */
 int bl_ctx_set_option(bl_ctx* ctx, const char* name, int64_t value);
 
@@ -396,6 +399,41 @@ int bl_count_super_kmers(bl_ctx* ctx, const uint64_t* d_records, uint64_t n_grou
 int bl_partition_records(bl_ctx* ctx, const uint64_t* d_hashes, const uint64_t* d_records, uint64_t n, uint32_t parts, uint64_t* d_out, uint64_t* counts);
 int bl_expand_super_kmers(bl_ctx* ctx, const uint64_t* d_records, uint64_t n_groups, uint32_t k, uint32_t flags, uint64_t* d_kmers, uint64_t capacity,
                           uint64_t* n_kmers);
+
+/* ---- the same pipeline for k up to 64: 32-byte records, 128-bit k-mers -----------------------------------------------------------
+ * bl_scan_super_kmers has no upper limit on k (1 <= m <= 32, w = k - m + 1 <= 64): it is the reference's own super-k-mer driver
+ * instantiation, KmerType = __uint128_t, MinimizerType = uint64_t.  These four calls take its groups on.  The 64-bit calls above keep
+ * their limits and their 16-byte record.
+ * THE RECORD: four 64-bit words per group, d_records[4g .. 4g+3], the array 32-byte aligned (BL_ERR_INVALID otherwise):
+ *   words 0, 1, 2   bases 0..31, 32..63, 64..95 of the group's size + k - 1 bases
+ *   word 3          bases 96..121 in bits 63..12, mm_pos (0..63) in bits 11..6, size - 1 (0..63) in bits 5..0
+ *   2 bits per base, first base in the most significant pair (the 16-byte record's packing); base bits beyond the group's own bases are 0.
+ * LIMITS: 1 <= m <= 32, m <= k <= 64, k - m + 1 <= 64, 2k - m <= 122 (BL_ERR_INVALID with a message naming them).  k <= 32 is allowed.
+ * The minimizer is the m-mer bl_scan_super_kmers reports, hashed as an 8-BYTE key (bl_hash64_u64).  The k-mers are bl_scan_kmers128's:
+ * value in 128 bits, reverse complement taken in 2k bits, canonical = numeric minimum.
+ * bl_pack_super_kmers128: the arrays of bl_scan_super_kmers -> records.  The clipping contract is bl_pack_super_kmers': the batch's
+ *   origin is honoured; a position in front of the origin (by any distance) or at or behind origin + n_bases packs an EMPTY record (all
+ *   base bits zero) with bits 11..0 as given; a group that runs over the end packs code 0 behind the end, bits 11..0 as given; no byte
+ *   outside the batch's n_bases is read.  d_mm_pos is required.
+ * bl_partition_records128: bl_partition_records for 32-byte records (d_out 32-byte aligned too).
+ * bl_expand_super_kmers128: records -> their k-mers, group after group, two words per k-mer (low, high; d_kmers 16-byte aligned).
+ *   BL_ERR_CAPACITY with *n_kmers = need when d_kmers is too small; nothing is written then.  Only 1 <= k <= 64 is checked (no m).
+ * bl_count_super_kmers128: bl_count_super_kmers' contract — exact multiplicities of the (canonical) k-mers, no particular order, two
+ *   words per distinct k-mer in d_kmers (low, high; 16-byte aligned); either output pointer NULL = count only; BL_ERR_CAPACITY with
+ *   *n_distinct = need when the arrays are too small, and NOTHING is written then.  Buckets by minimizer hash are counted by one wave
+ *   each in an LDS table of 16-byte keys whose empty slots are marked by an owner word, not by a key value: every k and strand mode is
+ *   taken, k = 64 without the canonical flag (the all-T 64-mer is all ones) included.  Oversized buckets take expand + 128-bit sort +
+ *   run-length; bl_ctx_set_option("count128_tables", 0) sends every bucket that way (same result).  Terminates on any record bits.
+ * NOT provided for k > 32: the fused in-scan record variant (bl_scan_super_kmer_records; records come from scan + pack here), 128-bit
+ *   keys in bl_sort_unique_u64 / bl_jaccard_sorted_u64 and the spill formats, biolib_amd::read_pool for wide views, and any multi-GPU
+ *   measurement of this path. */
+int bl_pack_super_kmers128(bl_ctx* ctx, const bl_batch* batch, const uint64_t* d_first_pos, const uint8_t* d_sizes, const uint8_t* d_mm_pos, uint64_t n_groups,
+                           uint32_t k, uint32_t m, uint64_t* d_records /* 4 per group */);
+int bl_partition_records128(bl_ctx* ctx, const uint64_t* d_hashes, const uint64_t* d_records, uint64_t n, uint32_t parts, uint64_t* d_out, uint64_t* counts);
+int bl_expand_super_kmers128(bl_ctx* ctx, const uint64_t* d_records, uint64_t n_groups, uint32_t k, uint32_t flags, uint64_t* d_kmers /* 2 per k-mer: lo, hi */,
+                             uint64_t capacity, uint64_t* n_kmers);
+int bl_count_super_kmers128(bl_ctx* ctx, const uint64_t* d_records, uint64_t n_groups, uint32_t k, uint32_t m, uint64_t seed, uint32_t flags,
+                            uint64_t* d_kmers /* 2 per distinct k-mer: lo, hi */, uint32_t* d_counts, uint64_t capacity, uint64_t* n_distinct);
 
 /* ---- BGZF on the device (ingest) -----------------------------------------------------------------------
  * A bgzip'ed file is a chain of gzip members of at most 64 KiB of text each, every one an independent deflate stream: the

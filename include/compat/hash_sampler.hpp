@@ -6,6 +6,8 @@
 //  * Iterator = wrapper::kmer_view<K,It>::const_iterator with HashFunctionFamily = hash::hash64: evaluated on the
 //    GPU (bl_scan_hash_sample); the sampler walks the resulting list.  As with the reference, the k-mer that ends the
 //    sequence is outside [cbegin(), cend()) of a kmer_view (quirk Q1).
+//    Over kmer_view<__uint128_t> (k <= 64) the call is bl_scan_hash_sample128: the values are 128 bits wide and hashed as 16-byte keys,
+//    as hash::hash64::hash<__uint128_t> does; operator* yields a __uint128_t.
 //  * any other pairing: element-by-element filter, exactly as the reference does.
 #ifndef BIOLIB_AMD_COMPAT_HASH_SAMPLER_HPP
 #define BIOLIB_AMD_COMPAT_HASH_SAMPLER_HPP
@@ -28,7 +30,8 @@ class hash_sampler
     static constexpr bool gpu_path = has_view<Iterator>::value and std::is_same<HashFunctionFamily, hash::hash64>::value;
     template <typename It, typename = void> struct wide_view : std::false_type {};
     template <typename It> struct wide_view<It, std::void_t<decltype(It::wide_kmers)>> : std::integral_constant<bool, It::wide_kmers> {};
-    static_assert(not (gpu_path and wide_view<Iterator>::value), "hash_sampler over a kmer_view of 128-bit k-mers is not provided: call bl_scan_hash_sample128");
+    static constexpr bool wide_path = gpu_path and wide_view<Iterator>::value;
+    using kept_type = std::conditional_t<wide_path, __uint128_t, uint64_t>;
     using hash_type = typename HashFunctionFamily::hash_type;
 
     public:
@@ -37,7 +40,7 @@ class hash_sampler
             public:
                 using iterator_category = std::forward_iterator_tag;
                 using difference_type   = std::ptrdiff_t;
-                using value_type        = std::conditional_t<gpu_path, uint64_t, typename std::iterator_traits<Iterator>::value_type>;
+                using value_type        = std::conditional_t<gpu_path, kept_type, typename std::iterator_traits<Iterator>::value_type>;
                 using pointer           = value_type*;
                 using reference         = value_type&;
 
@@ -98,12 +101,12 @@ class hash_sampler
         uint64_t mseed;
         double srate;
         hash_type threshold;
-        mutable std::shared_ptr<std::vector<uint64_t>> cache;
+        mutable std::shared_ptr<std::vector<kept_type>> cache;
 
-        std::vector<uint64_t> const& kept() const
+        std::vector<kept_type> const& kept() const
         {
             if (cache) return *cache;
-            auto out = std::make_shared<std::vector<uint64_t>>();
+            auto out = std::make_shared<std::vector<kept_type>>();
             if constexpr (gpu_path) {
                 auto const* view = itr_start.view();
                 std::string const& chars = view->chars();
@@ -113,12 +116,23 @@ class hash_sampler
                 if (chars.size() >= k and stop > first) {
                     biolib_amd::batch_handle batch(chars.data(), chars.size());
                     const std::size_t cap = stop - first;
-                    biolib_amd::device_array<uint64_t> dv(cap);
+                    const uint32_t flags = (view->is_canonical() ? (uint32_t)BL_FLAG_CANONICAL : 0u) | BL_FLAG_SYNC;
                     bl_result res;
-                    biolib_amd::check(bl_scan_hash_sample(biolib_amd::context::get(), batch.b, first, stop - first, k, mseed, threshold,
-                                                          (view->is_canonical() ? (uint32_t)BL_FLAG_CANONICAL : 0u) | BL_FLAG_SYNC, dv.d, nullptr, nullptr, cap, &res),
-                                      "bl_scan_hash_sample");
-                    *out = dv.to_host(res.count);
+                    if constexpr (wide_path) {
+                        biolib_amd::device_array<uint64_t> dv(2 * cap);
+                        biolib_amd::check(bl_scan_hash_sample128(biolib_amd::context::get(), batch.b, first, stop - first, k, mseed, threshold, flags, dv.d, nullptr,
+                                                                 nullptr, cap, &res),
+                                          "bl_scan_hash_sample128");
+                        auto words = dv.to_host(2 * res.count);
+                        out->reserve(res.count);
+                        for (std::size_t i = 0; i < res.count; ++i) out->push_back((static_cast<__uint128_t>(words[2 * i + 1]) << 64) | words[2 * i]);
+                    } else {
+                        biolib_amd::device_array<uint64_t> dv(cap);
+                        biolib_amd::check(bl_scan_hash_sample(biolib_amd::context::get(), batch.b, first, stop - first, k, mseed, threshold, flags, dv.d, nullptr, nullptr,
+                                                              cap, &res),
+                                          "bl_scan_hash_sample");
+                        *out = dv.to_host(res.count);
+                    }
                 }
             }
             cache = out;
