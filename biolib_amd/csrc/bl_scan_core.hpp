@@ -304,10 +304,13 @@ BL_DEV uint32_t murmur64_top(uint64_t key, uint32_t seed)
     h2 ^= h2 >> 33;
     h2 = mul64c_as<true>(h2, 0xff51afd7ed558ccdULL);
     h2 ^= h2 >> 33;
-    // high dwords of h1 * C and h2 * C, summed: the four cross products in one chain of multiply-adds, the two v_mul_hi on top
+    // high dwords of h1 * C and h2 * C, summed.  Only the low dword of the four cross products a1*chi + b1*clo + a2*chi + b2*clo is
+    // wanted, and modulo 2^32 the products that share a factor fold: (a1 + a2)*chi + (b1 + b2)*clo, two v_add_u32 and a chain of two
+    // multiply-adds (the sums may wrap: the wrapped bit only reaches bit 32 of a product).  The two v_mul_hi on top stay apart —
+    // hi(a1*clo) + hi(a2*clo) is not hi((a1 + a2)*clo), and S is defined by the former.
     const uint32_t clo = 0x1a85ec53u, chi = 0xc4ceb9feu;
     const uint32_t a1 = (uint32_t)h1, b1 = (uint32_t)(h1 >> 32), a2 = (uint32_t)h2, b2 = (uint32_t)(h2 >> 32);
-    const uint32_t cross = (uint32_t)mad_lo(b2, clo, mad_lo(a2, chi, mad_lo(b1, clo, mad_lo0<PLUS_ONE>(a1, chi))));
+    const uint32_t cross = (uint32_t)mad_lo(b1 + b2, clo, mad_lo0<PLUS_ONE>(a1 + a2, chi));
 #if defined(__HIP_DEVICE_COMPILE__) && !defined(BL_CPU_EMU)
     // the sum as one opaque v_add3_u32: left visible, the compiler may fold `hi(a * c) + x` into a v_mad_u64_u32 with the 64-bit addend
     // {0, x} — one v_mov more per product for the same result (it did, in the read-tiled kernel once the running maximum was gone)
