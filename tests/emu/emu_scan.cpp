@@ -422,6 +422,19 @@ void emu_top_values(const uint64_t* keys, uint64_t n, uint32_t seed, int plus_on
 {
     for (uint64_t i = 0; i < n; ++i) out[i] = plus_one ? murmur64_top<true>(keys[i], seed) : murmur64_top<false>(keys[i], seed);
 }
+// the tile plan a scan of [first, first + n) would run with (plan_scan, and plan_scan_frl_for where scan_windows would ask it), for tests that
+// place inputs by lane, wave and tile: out = {frl, origin, stride, n_tiles, read_len, lpr, rpw, ns, nwin}
+void emu_plan(int mode, uint64_t first, uint64_t n, uint64_t n_bases, uint64_t read_len, unsigned unit, unsigned w, unsigned flags, long long* out)
+{
+    uint64_t end = n == 0 ? n_bases : first + n;
+    if (end > n_bases) end = n_bases;
+    ScanParams p{};
+    plan_scan(mode, (int64_t)first, (int64_t)end, (int)w, p);
+    if (read_len && frl_width_built(mode, (int)w))
+        plan_scan_frl_for(mode, (int64_t)first, (int64_t)end, (int64_t)n_bases, (int64_t)read_len, (int)unit, (int)w, (flags & 1) != 0, p);
+    const long long v[9] = {p.frl, (long long)p.origin, p.stride, p.n_tiles, p.read_len, p.lpr, p.rpw, p.ns, p.nwin};
+    for (int i = 0; i < 9; ++i) out[i] = v[i];
+}
 int emu_frl_scans() { return g_frl_scans; }
 int emu_frl_redone() { return g_frl_redone; }
 int emu_closed_redone() { return g_closed_redone; }

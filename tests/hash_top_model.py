@@ -1,5 +1,6 @@
 """A plain numpy model of the approximate hash dword pass 1 of the window scans decides on, written from the rule and not from
-the kernel text.  TEST INFRASTRUCTURE: imported by tests/ and by tests/golden/make_approx_adversaries.py only.
+the kernel text, and (at the end) of what the exact kernels' own fast forms keep of a hash.  TEST INFRASTRUCTURE: imported by tests/ and by
+tests/golden/make_approx_adversaries.py and make_tie_adversaries.py only.
 
 The rule.  hash64(key, seed) = F1 + F2 (mod 2^64), the two finalised halves of MurmurHash3_x64_128 over the 8 key bytes.  Write
 F = hi:lo in dwords.  Then
@@ -228,3 +229,53 @@ def closed_syncmers(seq, k, s, seed, offsets):
     off_r = _windows(hr, w)[:, ::-1].argmin(axis=1)  # the canonical strand reads the s-mers back to front
     off = np.where(rev, off_r, off_f)
     return np.flatnonzero(np.isin(off, list(offsets))).astype(np.uint64)
+
+
+# ----------------------------------------------------------------------------- the exact kernels' own fast path (tie adversaries)
+
+def syncmer_offsets(seq, k, s, seed, canonical):
+    """per k-mer of one ACGT sequence: the offset, along the strand that counts, of its smallest s-mer hash (s-mers hashed as they stand on that
+    strand; leftmost of equals along it) and whether that strand is the reverse one"""
+    w = k - s + 1
+    u = units(seq, s, False)
+    hf = hash64(u, seed)
+    off = _windows(hf, w).argmin(axis=1)
+    kf = units(seq, k, False)
+    rev = np.zeros(len(kf), bool)
+    if canonical:
+        hr = hash64(revcomp_value(u, s), seed)
+        rev = revcomp_value(kf, k) < kf
+        off = np.where(rev, _windows(hr, w)[:, ::-1].argmin(axis=1), off)
+    return off, rev
+
+
+def _argmin_last(x, w):
+    return (w - 1) - _windows(x, w)[:, ::-1].argmin(axis=1)
+
+
+def fast_argmins(h, w):
+    """per window of w consecutive hashes, what each fast form ALONE would elect, beside the truth:
+         p26_left / p26_right   26-bit prefix above a 6-bit tag (window_argmin_packed), leftmost / rightmost of equal prefixes
+         p25_left / p25_right   25-bit prefix above a 7-bit tag (the run-time widths)
+         hi32_left / hi32_right the high dword alone, ties to one side
+         true_left / true_right the 64-bit hashes (the two differ only where equal units repeat)"""
+    h = np.asarray(h, dtype=np.uint64)
+    out = {}
+    for name, x in (("p26", h >> M(38)), ("p25", h >> M(39)), ("hi32", h >> M(32)), ("true", h)):
+        out[name + "_left"] = _windows(x, w).argmin(axis=1)
+        out[name + "_right"] = _argmin_last(x, w)
+    return out
+
+
+def tie_class(ha, hb):
+    """how two different hashes tie in the fast forms: 'hi32', 'p26', 'p25' or None"""
+    ha, hb = int(ha), int(hb)
+    if ha == hb:
+        return None
+    if ha >> 32 == hb >> 32:
+        return "hi32"
+    if ha >> 38 == hb >> 38:
+        return "p26"
+    if ha >> 39 == hb >> 39:
+        return "p25"
+    return None
