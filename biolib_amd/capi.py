@@ -23,6 +23,8 @@ SYMBOLS = [
     "bl_device_alloc", "bl_device_free", "bl_copy_to_host", "bl_copy_to_device", "bl_hash64_u64", "bl_bgzf_walk", "bl_bgzf_inflate", "bl_host_alloc", "bl_host_free", "bl_reader_open_shard", "bl_reader_shard_range",
     "bl_scan_kmers128", "bl_scan_hash_sample128", "bl_hash64_u128", "bl_scan_syncmers128", "bl_scan_minimizers128",
     "bl_pack_super_kmers128", "bl_partition_records128", "bl_expand_super_kmers128", "bl_count_super_kmers128",
+    "bl_sort_u128", "bl_sort_unique_u128", "bl_count_sorted_u128", "bl_jaccard_sorted_u128", "bl_partition_u128",
+    "bl_write_run_u128", "bl_write_vector_u128", "bl_file_count_u128", "bl_read_file_u128_host", "bl_read_file_u128", "bl_merge_runs_u128",
 ]
 
 
@@ -151,6 +153,17 @@ def lib():
     L.bl_partition_records128.argtypes = [vp, vp, vp, u64, u32, vp, vp]
     L.bl_expand_super_kmers128.argtypes = [vp, vp, u64, u32, u32, vp, u64, C.POINTER(u64)]
     L.bl_count_super_kmers128.argtypes = [vp, vp, u64, u32, u32, u64, u32, vp, vp, u64, C.POINTER(u64)]
+    L.bl_sort_u128.argtypes = [vp, vp, u64, u32]
+    L.bl_sort_unique_u128.argtypes = [vp, vp, u64, u32, C.POINTER(u64)]
+    L.bl_count_sorted_u128.argtypes = [vp, vp, u64, vp, vp, C.POINTER(u64)]
+    L.bl_jaccard_sorted_u128.argtypes = [vp, vp, u64, vp, u64, C.POINTER(u64), C.POINTER(u64)]
+    L.bl_partition_u128.argtypes = [vp, vp, u64, u32, u64, vp, vp]
+    L.bl_write_run_u128.argtypes = [vp, vp, u64, C.c_char_p]
+    L.bl_write_vector_u128.argtypes = [vp, vp, u64, C.c_char_p]
+    L.bl_file_count_u128.argtypes = [C.c_char_p, C.c_int, C.POINTER(u64)]
+    L.bl_read_file_u128_host.argtypes = [C.c_char_p, C.c_int, vp, u64, C.POINTER(u64)]
+    L.bl_read_file_u128.argtypes = [vp, C.c_char_p, C.c_int, vp, u64, C.POINTER(u64)]
+    L.bl_merge_runs_u128.argtypes = [vp, C.POINTER(C.c_char_p), u32, vp, u64, C.POINTER(u64)]
     L.bl_hash64_u128.restype = u64
     L.bl_hash64_u128.argtypes = [u64, u64, u64]
     _lib = L

@@ -107,6 +107,7 @@ struct bl_ctx {
     // optional per-launch timing of the main scan kernel alone (bl_ctx_kernel_timing)
     bool exact_windows = false;  // bl_ctx_set_exact_windows
     bool position_tiled = false; // bl_ctx_set_option("position_tiled"): never the read-tiled layout
+    int jaccard128_path = 0;     // bl_ctx_set_option("jaccard128_path"): 0 = bl_jaccard_sorted_u128 chooses, 1 = merge kernel, 2 = search kernel
     bool count128_tables = true; // bl_ctx_set_option("count128_tables"): 0 = bl_count_super_kmers128 counts every bucket by sort + run-length
     bool ktiming = false;
     std::vector<hipEvent_t> ev_pool;                       // free events
@@ -355,6 +356,7 @@ hipStream_t bl_ctx_stream(bl_ctx* c)
 int bl_batch_adopt_device(bl_ctx* ctx, void* d_bases, uint64_t n_bases, uint64_t* d_offsets, uint64_t n_seqs, uint64_t fixed_len, bl_batch** out);
 int bl_ctx_device(bl_ctx* c) { return c->device; }
 int bl_ctx_count128_tables(bl_ctx* c) { return c->count128_tables ? 1 : 0; }  // bl_superkmer128.hip
+int bl_ctx_jaccard128_path(bl_ctx* c) { return c->jaccard128_path; }            // bl_setops128.hip
 
 // Device scratch that lives with the context (slot 0..7), grown on demand and never shrunk: the set operations and the
 // bucketed counter need gigabytes of temporary space per call, and hipMalloc / hipFree of that size costs more than their
@@ -581,6 +583,10 @@ int bl_ctx_set_option(bl_ctx* c, const char* name, int64_t value)
     }
     if (n == "count128_tables" && (value == 0 || value == 1)) {
         c->count128_tables = value != 0;
+        return BL_OK;
+    }
+    if (n == "jaccard128_path" && value >= 0 && value <= 2) {
+        c->jaccard128_path = (int)value;
         return BL_OK;
     }
     if (n == "emit_lds_bytes" && value >= 0 && value <= 160 * 1024) {

@@ -1,0 +1,332 @@
+// bl_setops128.hip — the consumer side of the pipeline for 16-byte keys (k-mers of 33 <= k <= 64, kmer_view<__uint128_t>): sort,
+// unique, run-length count, owner split, the device half of the run-file calls, and the sizes of intersection / union of two sorted
+// unique sets.  As in bl_setops.hip the sort, the unique, the run-length count and the pairwise merge of runs are rocPRIM device
+// primitives on __uint128_t (library plumbing), the owner split is blpart::partition with a 16-byte element.  Hand-written: the two
+// intersection kernels, whose per-thread bodies live in bl_setops128_core.hpp —
+//   merge kernel    merge path: one thread per tile boundary finds the tile's split in global memory (merge_partition_kernel); one
+//                   workgroup per tile of 2048 merged elements stages its A range and its B range plus ONE more B element in LDS with
+//                   16-byte accesses, every thread merges 8 elements from its own diagonal and counts the equal pairs
+//                   (merge_tile_kernel).  Every key is read from HBM once.
+//   search kernel   every key of the smaller set binary-searches the larger one: log2(n_large) dependent 16-byte loads per key, the
+//                   better form when the sets differ much in size.
+// The context option "jaccard128_path" forces one of them (1 merge, 2 search); 0 chooses by the size ratio (bl128s::choose_merge).
+#include <hip/hip_runtime.h>
+
+#include <rocprim/device/device_merge.hpp>
+#include <rocprim/device/device_radix_sort.hpp>
+#include <rocprim/device/device_run_length_encode.hpp>
+#include <rocprim/device/device_select.hpp>
+
+#include <vector>
+
+#include "../../include/biolib_amd.h"
+#include "bl_kmers128_core.hpp"
+#include "bl_partition.hpp"
+#include "bl_setops128_core.hpp"
+
+extern int bl_set_error(int code, const char* msg);  // bl_capi.hip
+extern hipStream_t bl_ctx_stream(bl_ctx* ctx);
+extern int bl_ctx_device(bl_ctx* ctx);
+extern void* bl_ctx_scratch(bl_ctx* ctx, int slot, size_t bytes);  // slots 4-6 are the set operations': 4 data, 5 library workspace, 6 counters
+extern int bl_ctx_jaccard128_path(bl_ctx* ctx);                    // the "jaccard128_path" option
+
+namespace {
+
+using bl128s::Key;
+using bl128s::TILE;
+using bl128s::TPB;
+typedef unsigned long long ull;
+
+static_assert(sizeof(Key) == 16 && sizeof(__uint128_t) == 16, "a key is the object representation of __uint128_t");
+
+// splits[t] = A elements in front of diagonal min(t * TILE, na + nb), t = 0 .. n_tiles
+__global__ __launch_bounds__(TPB) void merge_partition_kernel(const Key* __restrict__ a, ull na, const Key* __restrict__ b, ull nb, ull n_tiles, ull* __restrict__ splits)
+{
+    const ull t = (ull)blockIdx.x * TPB + threadIdx.x;
+    if (t > n_tiles) return;
+    const ull total = na + nb;
+    const ull d = t * (ull)TILE < total ? t * (ull)TILE : total;
+    splits[t] = bl128s::diag_split<ull>(a, na, b, nb, d);
+}
+
+// per wave, then one atomic per workgroup (integer sums: the order does not matter)
+__device__ __forceinline__ void block_add(uint32_t found, ull* out)
+{
+    __shared__ uint32_t wave_sum[TPB / 64];
+    for (int d = 32; d >= 1; d >>= 1) found += __shfl_xor(found, d, 64);
+    if ((threadIdx.x & 63) == 0) wave_sum[threadIdx.x >> 6] = found;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        ull sum = 0;
+        for (int w = 0; w < TPB / 64; ++w) sum += wave_sum[w];
+        if (sum) atomicAdd(out, sum);
+    }
+}
+
+__global__ __launch_bounds__(TPB) void merge_tile_kernel(const Key* __restrict__ a, ull na, const Key* __restrict__ b, ull nb, const ull* __restrict__ splits, ull* out)
+{
+    __shared__ Key keys[bl128s::LDS_KEYS];
+    const bl128s::TileRange r = bl128s::tile_range(splits, blockIdx.x, na, nb);
+    for (uint32_t x = threadIdx.x; x < r.la; x += TPB) keys[x] = a[r.a0 + x];
+    for (uint32_t x = threadIdx.x; x < r.lbx; x += TPB) keys[r.la + x] = b[r.b0 + x];
+    __syncthreads();
+    const uint32_t found = bl128s::tile_thread_count(keys, r.la, keys + r.la, r.lb, r.lbx, threadIdx.x);
+    block_add(found, out);
+}
+
+__global__ __launch_bounds__(TPB) void search_count_kernel(const Key* __restrict__ a, ull na, const Key* __restrict__ b, ull nb, ull* out)
+{
+    uint32_t found = 0;
+    for (ull i = (ull)blockIdx.x * TPB + threadIdx.x; i < na; i += (ull)gridDim.x * TPB) found += bl128s::search_count(a[i], b, nb);
+    block_add(found, out);
+}
+
+struct Key128HashOwner {
+    const Key* keys;
+    uint32_t seed;
+    __device__ uint32_t operator()(ull i, uint32_t parts) const
+    {
+        const Key k = keys[i];
+        return blpart::bucket_of(bl::murmur64_u128(k.lo, k.hi, seed), parts);
+    }
+};
+
+int hip_rc(hipError_t e) { return bl_set_error(e == hipErrorOutOfMemory ? BL_ERR_OOM : BL_ERR_HIP, hipGetErrorString(e)); }
+bool misaligned(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) != 0; }
+int bad_alignment() { return bl_set_error(BL_ERR_INVALID, "arrays of 16-byte keys must be 16-byte aligned"); }
+
+// keys[0 .. n) -> sorted[0 .. n) over the bits [0, key_bits).  Scratch slot 5.
+hipError_t sort128(bl_ctx* ctx, __uint128_t* keys, __uint128_t* sorted, ull n, uint32_t key_bits, hipStream_t s)
+{
+    size_t bytes = 0;
+    hipError_t e = rocprim::radix_sort_keys(nullptr, bytes, keys, sorted, (size_t)n, 0u, key_bits, s);
+    if (e != hipSuccess) return e;
+    void* tmp = bl_ctx_scratch(ctx, 5, bytes ? bytes : 16);
+    if (!tmp) return hipErrorOutOfMemory;
+    return rocprim::radix_sort_keys(tmp, bytes, keys, sorted, (size_t)n, 0u, key_bits, s);
+}
+
+}  // namespace
+
+extern "C" {
+
+int bl_sort_u128(bl_ctx* ctx, uint64_t* d_keys, uint64_t n, uint32_t key_bits)
+{
+    if (!ctx || (n && !d_keys) || key_bits < 1 || key_bits > 128) return bl_set_error(BL_ERR_INVALID, "bad argument (1 <= key_bits <= 128)");
+    if (n == 0) return BL_OK;
+    if (misaligned(d_keys)) return bad_alignment();
+    hipError_t e = hipSetDevice(bl_ctx_device(ctx));
+    if (e != hipSuccess) return hip_rc(e);
+    hipStream_t s = bl_ctx_stream(ctx);
+    __uint128_t* keys = reinterpret_cast<__uint128_t*>(d_keys);
+    __uint128_t* tmp = static_cast<__uint128_t*>(bl_ctx_scratch(ctx, 4, n * sizeof(__uint128_t)));
+    if (!tmp) return bl_set_error(BL_ERR_OOM, "scratch allocation failed");
+    e = sort128(ctx, keys, tmp, n, key_bits, s);
+    if (e == hipSuccess) e = hipMemcpyAsync(keys, tmp, n * sizeof(__uint128_t), hipMemcpyDeviceToDevice, s);
+    if (e == hipSuccess) e = hipStreamSynchronize(s);
+    return e == hipSuccess ? BL_OK : hip_rc(e);
+}
+
+int bl_sort_unique_u128(bl_ctx* ctx, uint64_t* d_keys, uint64_t n, uint32_t key_bits, uint64_t* n_unique)
+{
+    if (!ctx || !n_unique || (n && !d_keys) || key_bits < 1 || key_bits > 128) return bl_set_error(BL_ERR_INVALID, "bad argument (1 <= key_bits <= 128)");
+    *n_unique = 0;
+    if (n == 0) return BL_OK;
+    if (misaligned(d_keys)) return bad_alignment();
+    hipError_t e = hipSetDevice(bl_ctx_device(ctx));
+    if (e != hipSuccess) return hip_rc(e);
+    hipStream_t s = bl_ctx_stream(ctx);
+    __uint128_t* keys = reinterpret_cast<__uint128_t*>(d_keys);
+    __uint128_t* tmp = static_cast<__uint128_t*>(bl_ctx_scratch(ctx, 4, n * sizeof(__uint128_t)));
+    ull* d_count = static_cast<ull*>(bl_ctx_scratch(ctx, 6, 64));
+    if (!tmp || !d_count) return bl_set_error(BL_ERR_OOM, "scratch allocation failed");
+    e = sort128(ctx, keys, tmp, n, key_bits, s);  // keys -> tmp (sorted)
+    size_t bytes = 0;
+    if (e == hipSuccess) e = rocprim::unique(nullptr, bytes, tmp, keys, d_count, (size_t)n, rocprim::equal_to<__uint128_t>(), s);
+    void* ws = nullptr;
+    if (e == hipSuccess) {
+        ws = bl_ctx_scratch(ctx, 5, bytes ? bytes : 16);  // (the sort's use of the slot is ordered in front of this one by the stream)
+        if (!ws) e = hipErrorOutOfMemory;
+    }
+    if (e == hipSuccess) e = rocprim::unique(ws, bytes, tmp, keys, d_count, (size_t)n, rocprim::equal_to<__uint128_t>(), s);  // tmp -> keys
+    ull cnt = 0;
+    if (e == hipSuccess) e = hipMemcpyAsync(&cnt, d_count, sizeof(cnt), hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess) e = hipStreamSynchronize(s);
+    if (e != hipSuccess) return hip_rc(e);
+    *n_unique = cnt;
+    return BL_OK;
+}
+
+int bl_count_sorted_u128(bl_ctx* ctx, const uint64_t* d_sorted, uint64_t n, uint64_t* d_unique, uint32_t* d_counts, uint64_t* n_unique)
+{
+    if (!ctx || !n_unique || (n && (!d_sorted || !d_unique || !d_counts))) return bl_set_error(BL_ERR_INVALID, "NULL argument");
+    *n_unique = 0;
+    if (n == 0) return BL_OK;
+    if (misaligned(d_sorted) || misaligned(d_unique)) return bad_alignment();
+    if (n >= (1ull << 32)) return bl_set_error(BL_ERR_INVALID, "bl_count_sorted_u128 takes fewer than 2^32 keys");  // (run_length_encode's size is 32 bits)
+    hipError_t e = hipSetDevice(bl_ctx_device(ctx));
+    if (e != hipSuccess) return hip_rc(e);
+    hipStream_t s = bl_ctx_stream(ctx);
+    const __uint128_t* sorted = reinterpret_cast<const __uint128_t*>(d_sorted);
+    __uint128_t* uniq = reinterpret_cast<__uint128_t*>(d_unique);
+    ull* d_runs = static_cast<ull*>(bl_ctx_scratch(ctx, 6, 64));
+    if (!d_runs) return bl_set_error(BL_ERR_OOM, "scratch allocation failed");
+    size_t bytes = 0;
+    void* tmp = nullptr;
+    e = rocprim::run_length_encode(nullptr, bytes, sorted, (unsigned int)n, uniq, d_counts, d_runs, s);
+    if (e == hipSuccess) {
+        tmp = bl_ctx_scratch(ctx, 5, bytes ? bytes : 16);
+        if (!tmp) e = hipErrorOutOfMemory;
+    }
+    if (e == hipSuccess) e = rocprim::run_length_encode(tmp, bytes, sorted, (unsigned int)n, uniq, d_counts, d_runs, s);
+    ull runs = 0;
+    if (e == hipSuccess) e = hipMemcpyAsync(&runs, d_runs, sizeof(runs), hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess) e = hipStreamSynchronize(s);
+    if (e != hipSuccess) return hip_rc(e);
+    *n_unique = runs;
+    return BL_OK;
+}
+
+int bl_jaccard_sorted_u128(bl_ctx* ctx, const uint64_t* d_a, uint64_t na, const uint64_t* d_b, uint64_t nb, uint64_t* intersection, uint64_t* union_size)
+{
+    if (!ctx || !intersection || !union_size || (na && !d_a) || (nb && !d_b)) return bl_set_error(BL_ERR_INVALID, "NULL argument");
+    if ((na && misaligned(d_a)) || (nb && misaligned(d_b))) return bad_alignment();
+    if (na >= (1ull << 40) || nb >= (1ull << 40)) return bl_set_error(BL_ERR_INVALID, "bl_jaccard_sorted_u128 takes fewer than 2^40 keys per set");
+    if (na == 0 || nb == 0) {
+        *intersection = 0;
+        *union_size = na + nb;
+        return BL_OK;
+    }
+    hipError_t e = hipSetDevice(bl_ctx_device(ctx));
+    if (e != hipSuccess) return hip_rc(e);
+    hipStream_t s = bl_ctx_stream(ctx);
+    const Key* a = reinterpret_cast<const Key*>(d_a);
+    const Key* b = reinterpret_cast<const Key*>(d_b);
+    ull* d_out = static_cast<ull*>(bl_ctx_scratch(ctx, 6, 64));
+    if (!d_out) return bl_set_error(BL_ERR_OOM, "scratch allocation failed");
+    e = hipMemsetAsync(d_out, 0, sizeof(ull), s);
+    const int path = bl_ctx_jaccard128_path(ctx);
+    const bool merge = path == 1 || (path == 0 && bl128s::choose_merge(na, nb));
+    if (e == hipSuccess && merge) {
+        const ull n_tiles = (na + nb + TILE - 1) / TILE;  // < 2^30
+        ull* splits = static_cast<ull*>(bl_ctx_scratch(ctx, 5, (n_tiles + 1) * sizeof(ull)));
+        if (!splits) return bl_set_error(BL_ERR_OOM, "scratch allocation failed");
+        hipLaunchKernelGGL(merge_partition_kernel, dim3((unsigned)((n_tiles + 1 + TPB - 1) / TPB)), dim3(TPB), 0, s, a, (ull)na, b, (ull)nb, n_tiles, splits);
+        hipLaunchKernelGGL(merge_tile_kernel, dim3((unsigned)n_tiles), dim3(TPB), 0, s, a, (ull)na, b, (ull)nb, splits, d_out);
+        e = hipGetLastError();
+    } else if (e == hipSuccess) {
+        // search the larger set with the elements of the smaller one
+        const bool a_small = na <= nb;
+        const Key* x = a_small ? a : b;
+        const Key* y = a_small ? b : a;
+        const ull nx = a_small ? na : nb, ny = a_small ? nb : na;
+        const unsigned blocks = (unsigned)((nx + TPB - 1) / TPB < 256 * 16 ? (nx + TPB - 1) / TPB : 256 * 16);
+        hipLaunchKernelGGL(search_count_kernel, dim3(blocks), dim3(TPB), 0, s, x, nx, y, ny, d_out);
+        e = hipGetLastError();
+    }
+    ull inter = 0;
+    if (e == hipSuccess) e = hipMemcpyAsync(&inter, d_out, sizeof(inter), hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess) e = hipStreamSynchronize(s);
+    if (e != hipSuccess) return hip_rc(e);
+    *intersection = inter;
+    *union_size = na + nb - inter;
+    return BL_OK;
+}
+
+int bl_partition_u128(bl_ctx* ctx, const uint64_t* d_keys, uint64_t n, uint32_t parts, uint64_t seed, uint64_t* d_out, uint64_t* counts)
+{
+    if (!ctx || !counts || parts == 0 || parts > blpart::MAX_PARTS || (n && (!d_keys || !d_out))) return bl_set_error(BL_ERR_INVALID, "bad argument (1 <= parts <= 64)");
+    if (n && (misaligned(d_keys) || misaligned(d_out))) return bad_alignment();
+    hipError_t e = hipSetDevice(bl_ctx_device(ctx));
+    if (e != hipSuccess) return hip_rc(e);
+    const Key* keys = reinterpret_cast<const Key*>(d_keys);
+    ull host[blpart::MAX_PARTS];
+    e = blpart::partition(keys, (ull)n, parts, Key128HashOwner{keys, (uint32_t)seed}, reinterpret_cast<Key*>(d_out), host, bl_ctx_stream(ctx));
+    if (e != hipSuccess) return hip_rc(e);
+    for (uint32_t b = 0; b < parts; ++b) counts[b] = host[b];
+    return BL_OK;
+}
+
+int bl_read_file_u128(bl_ctx* ctx, const char* path, int with_count, uint64_t* d_out, uint64_t capacity, uint64_t* n)
+{
+    if (!ctx || !path) return bl_set_error(BL_ERR_INVALID, "NULL argument");
+    uint64_t cnt = 0;
+    int rc = bl_file_count_u128(path, with_count, &cnt);
+    if (rc != BL_OK) return rc;
+    if (n) *n = cnt;
+    if (cnt > capacity) return bl_set_error(BL_ERR_CAPACITY, "device array too small for the file");
+    if (cnt == 0) return BL_OK;
+    if (!d_out) return bl_set_error(BL_ERR_INVALID, "NULL argument");
+    if (misaligned(d_out)) return bad_alignment();
+    std::vector<uint64_t> host(2 * cnt);
+    rc = bl_read_file_u128_host(path, with_count, host.data(), cnt, nullptr);
+    if (rc != BL_OK) return rc;
+    hipError_t e = hipSetDevice(bl_ctx_device(ctx));
+    hipStream_t s = bl_ctx_stream(ctx);
+    if (e == hipSuccess) e = hipMemcpyAsync(d_out, host.data(), cnt * 16, hipMemcpyHostToDevice, s);
+    if (e == hipSuccess) e = hipStreamSynchronize(s);  // `host` goes away
+    return e == hipSuccess ? BL_OK : hip_rc(e);
+}
+
+int bl_merge_runs_u128(bl_ctx* ctx, const char* const* paths, uint32_t n_paths, uint64_t* d_out, uint64_t capacity, uint64_t* n_total)
+{
+    if (!ctx || (n_paths && !paths) || !n_total) return bl_set_error(BL_ERR_INVALID, "NULL argument");
+    std::vector<uint64_t> len(n_paths), off(n_paths + 1, 0);
+    for (uint32_t i = 0; i < n_paths; ++i) {
+        int rc = bl_file_count_u128(paths[i], 0, &len[i]);
+        if (rc != BL_OK) return rc;
+        off[i + 1] = off[i] + len[i];
+    }
+    const uint64_t total = off[n_paths];
+    *n_total = total;
+    if (total > capacity) return bl_set_error(BL_ERR_CAPACITY, "device array too small for the merged runs");
+    if (total == 0) return BL_OK;
+    if (!d_out) return bl_set_error(BL_ERR_INVALID, "NULL argument");
+    if (misaligned(d_out)) return bad_alignment();
+    for (uint32_t i = 0; i < n_paths; ++i) {
+        int rc = bl_read_file_u128(ctx, paths[i], 0, d_out + 2 * off[i], len[i], nullptr);
+        if (rc != BL_OK) return rc;
+    }
+    hipError_t e = hipSetDevice(bl_ctx_device(ctx));
+    if (e != hipSuccess) return hip_rc(e);
+    hipStream_t s = bl_ctx_stream(ctx);
+    // runs = [cur[i], cur[i+1]); merge neighbours pairwise, ping-ponging between d_out and the scratch array
+    __uint128_t* a = reinterpret_cast<__uint128_t*>(d_out);
+    __uint128_t* b = nullptr;
+    std::vector<uint64_t> cur(off);
+    bool in_a = true;
+    while (cur.size() > 2 && e == hipSuccess) {
+        if (!b) {
+            b = static_cast<__uint128_t*>(bl_ctx_scratch(ctx, 4, total * sizeof(__uint128_t)));
+            if (!b) return bl_set_error(BL_ERR_OOM, "scratch allocation failed");
+        }
+        __uint128_t* src = in_a ? a : b;
+        __uint128_t* dst = in_a ? b : a;
+        std::vector<uint64_t> next(1, 0);
+        for (size_t i = 0; i + 1 < cur.size() && e == hipSuccess; i += 2) {
+            const uint64_t lo = cur[i], mid = cur[i + 1], hi = i + 2 < cur.size() ? cur[i + 2] : cur[i + 1];
+            if (hi == mid) {  // odd run out: copied through
+                if (mid > lo) e = hipMemcpyAsync(dst + lo, src + lo, (mid - lo) * sizeof(__uint128_t), hipMemcpyDeviceToDevice, s);
+            } else {
+                size_t need = 0;
+                e = rocprim::merge(nullptr, need, src + lo, src + mid, dst + lo, mid - lo, hi - mid, rocprim::less<__uint128_t>(), s);
+                void* tmp = nullptr;
+                if (e == hipSuccess) {
+                    // the slot only grows, and growing it synchronises the device first: the merges in flight are done with the old block
+                    tmp = bl_ctx_scratch(ctx, 5, need ? need : 16);
+                    if (!tmp) e = hipErrorOutOfMemory;
+                }
+                if (e == hipSuccess) e = rocprim::merge(tmp, need, src + lo, src + mid, dst + lo, mid - lo, hi - mid, rocprim::less<__uint128_t>(), s);
+            }
+            next.push_back(hi);
+        }
+        cur.swap(next);
+        in_a = !in_a;
+    }
+    if (e == hipSuccess && !in_a) e = hipMemcpyAsync(a, b, total * sizeof(__uint128_t), hipMemcpyDeviceToDevice, s);
+    const hipError_t se = hipStreamSynchronize(s);
+    if (e == hipSuccess) e = se;
+    return e == hipSuccess ? BL_OK : hip_rc(e);
+}
+
+}  // extern "C"

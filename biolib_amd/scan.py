@@ -97,7 +97,8 @@ class Context:
         check(self._lib.bl_ctx_set_exact_windows(self._h, 1 if on else 0))
 
     def set_option(self, name, value):
-        """tuning / test switches by name (bl_ctx_set_option: "exact_windows", "lanes", "position_tiled", "emit_lds_bytes")"""
+        """tuning / test switches by name (bl_ctx_set_option: "exact_windows", "lanes", "position_tiled", "emit_lds_bytes", "count128_tables",
+        "jaccard128_path")"""
         check(self._lib.bl_ctx_set_option(self._h, name.encode(), int(value)))
 
     def kernel_timing(self, enable=True):
@@ -301,6 +302,81 @@ class Context:
         out = self.empty_u64(total.value)
         if total.value:
             check(self._lib.bl_merge_runs_u64(self._h, arr, len(paths), C.c_void_p(out.data_ptr()), total.value, C.byref(total)))
+        return out[: total.value]
+
+    # ---- the same set operations on 16-byte keys: int64[n, 2] CUDA tensors (low, high), as kmers128 / expand_super_kmers128 return
+    def _keys128(self, keys, n):
+        if keys.dim() != 2 or keys.shape[1] != 2 or keys.element_size() != 8 or not keys.is_contiguous():
+            raise ValueError("128-bit keys are a contiguous int64[n, 2] tensor (low, high)")
+        n = keys.shape[0] if n is None else int(n)
+        if n > keys.shape[0]:
+            raise ValueError("n exceeds the tensor")
+        self._inputs_ready()
+        return n
+
+    def empty_u128(self, n):
+        import torch
+
+        return torch.empty((max(int(n), 1), 2), dtype=torch.int64, device=self.torch_device)
+
+    def sort128(self, keys, key_bits=128, n=None):
+        """in-place ascending sort of keys[:n] as 128-bit integers; key_bits = number of low bits that can be non-zero (2k for k-mers)"""
+        n = self._keys128(keys, n)
+        check(self._lib.bl_sort_u128(self._h, C.c_void_p(keys.data_ptr()), n, int(key_bits)))
+
+    def sort_unique128(self, keys, key_bits=128, n=None):
+        """in-place sort + unique of keys[:n]; returns the number of distinct keys now at the front"""
+        n = self._keys128(keys, n)
+        out = C.c_uint64()
+        check(self._lib.bl_sort_unique_u128(self._h, C.c_void_p(keys.data_ptr()), n, int(key_bits), C.byref(out)))
+        return int(out.value)
+
+    def jaccard128(self, a, na, b, nb):
+        """(|A n B|, |A u B|) of two sorted duplicate-free arrays of 128-bit keys"""
+        na, nb = self._keys128(a, na), self._keys128(b, nb)
+        i, u = C.c_uint64(), C.c_uint64()
+        check(self._lib.bl_jaccard_sorted_u128(self._h, C.c_void_p(a.data_ptr()), na, C.c_void_p(b.data_ptr()), nb, C.byref(i), C.byref(u)))
+        return int(i.value), int(u.value)
+
+    def partition128(self, keys, parts, seed=0, n=None):
+        """(bucketed copy of keys[:n], sizes[parts]): bucket b = keys with hash64_u128(lo, hi, seed) % parts == b, contiguous, in bucket order"""
+        n = self._keys128(keys, n)
+        out = self.empty_u128(n)
+        counts = (C.c_uint64 * max(int(parts), 1))()
+        check(self._lib.bl_partition_u128(self._h, C.c_void_p(keys.data_ptr()), n, int(parts), int(seed), C.c_void_p(out.data_ptr()), counts))
+        return out[:n], [int(c) for c in counts]
+
+    def sort_count128(self, keys, key_bits=128, n=None):
+        """(distinct keys ascending int64[d, 2], multiplicities int32[d]) of keys[:n]; keys is sorted in place"""
+        import torch
+
+        n = self._keys128(keys, n)
+        check(self._lib.bl_sort_u128(self._h, C.c_void_p(keys.data_ptr()), n, int(key_bits)))
+        uniq = self.empty_u128(n)
+        mult = torch.empty(max(n, 1), dtype=torch.int32, device=self.torch_device)
+        runs = C.c_uint64()
+        check(self._lib.bl_count_sorted_u128(self._h, C.c_void_p(keys.data_ptr()), n, C.c_void_p(uniq.data_ptr()), C.c_void_p(mult.data_ptr()), C.byref(runs)))
+        return uniq[: runs.value], mult[: runs.value]
+
+    def read_file_u128(self, path, with_count=False):
+        """a run file (raw sorted 16-byte keys) or, with_count, an io::basic_store'd vector<__uint128_t> of biolib -> int64[n, 2] device tensor"""
+        n = C.c_uint64()
+        check(self._lib.bl_file_count_u128(str(path).encode(), 1 if with_count else 0, C.byref(n)))
+        out = self.empty_u128(n.value)
+        check(self._lib.bl_read_file_u128(self._h, str(path).encode(), 1 if with_count else 0, C.c_void_p(out.data_ptr()), n.value, C.byref(n)))
+        return out[: n.value]
+
+    def merge_runs128(self, paths):
+        """the sorted union (duplicates kept) of run files of 16-byte keys, on the device: what iterating the reference's
+        external_memory_vector<__uint128_t> yields"""
+        arr = (C.c_char_p * len(paths))(*[str(p).encode() for p in paths])
+        total = C.c_uint64()
+        rc = self._lib.bl_merge_runs_u128(self._h, arr, len(paths), None, 0, C.byref(total))
+        if rc not in (0, capi.BL_ERR_CAPACITY):
+            check(rc)
+        out = self.empty_u128(total.value)
+        if total.value:
+            check(self._lib.bl_merge_runs_u128(self._h, arr, len(paths), C.c_void_p(out.data_ptr()), total.value, C.byref(total)))
         return out[: total.value]
 
     def count_super_kmers(self, records, k, m, seed=0, canonical=True, n=None, out=None):
@@ -544,7 +620,8 @@ class Batch:
     def hash_sample128(self, k, seed=0, threshold=2**64 - 1, canonical=False, drop_last=False, first=0, n=0, capacity=None, device=False):
         """k-mers up to k = 64 with hash64_u128(value, seed) < threshold, in position order; values has shape (count, 2) as in kmers128.
         Run again with the count the scan reports when `capacity` (default: the expected number of records) was too small.
-        device=True keeps the hash tensor on the GPU (keys for sort_unique / jaccard)."""
+        device=True keeps the tensors on the GPU: values_device (int64[capacity, 2], the keys sort_unique128 / jaccard128 take) and
+        hashes_device, the first n entries of each."""
         import torch
 
         span = self._span(first, n)
@@ -562,7 +639,7 @@ class Batch:
             cnt = int(r.count)
             out = r.as_dict()
             if device:
-                out.update(hashes_device=h, n=cnt)
+                out.update(values_device=v, hashes_device=h, n=cnt)
             else:
                 out.update(values=v[:cnt].cpu().numpy().view(np.uint64).copy(), positions=_host_u64(p, cnt), hashes=_host_u64(h, cnt))
             return out

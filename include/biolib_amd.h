@@ -18,6 +18,8 @@
  *   bl_scan_syncmers     sampler::syncmer_sampler<It,minimizer_position_extractor>
  *                                                                         include/syncmer_sampler.hpp:9-137, include/kmer_view.hpp:250-283
  *   bl_scan_syncmers128  the same sampler over kmer_view<__uint128_t,It>  k <= 64, s <= 32; s-mer keys of 16 bytes (kmer_view.hpp:266-283 in KmerType)
+ *   bl_sort_unique_u128, bl_jaccard_sorted_u128, bl_write_run_u128 ..     the consumer of those k-mers: emem::external_memory_vector<__uint128_t>,
+ *                        sampler::ordered_unique_sampler, algorithm::jaccard  include/external_memory_vector.hpp, ordered_unique_sampler.hpp, jaccard.hpp
  *   bl_hash64_u64        hash::hash64::hash<uint64_t>                     include/hash.hpp:55-59 (host-side convenience, bit-exact)
  *   bl_hash64_u128       hash::hash64::hash<__uint128_t>                  the same for a 16-byte value
  *
@@ -163,9 +165,10 @@ int bl_scan_kmers(bl_ctx* ctx, const bl_batch* batch, uint64_t first, uint64_t n
  *                      k >= 33.  This is the intended meaning, its formulas evaluated in KmerType)
  * result: count, xor_value := XOR of the low words, aux := XOR of the high words, xor_hash, xor_pos := wrapping sum of hashes.
  * 1 <= k <= 64 (bl_scan_kmers keeps its own limit of 32).
- * NOT covered for k > 32: 128-bit keys in bl_sort_unique_u64 / bl_jaccard_sorted_u64 / bl_partition_u64 and the spill formats (the
- * 64-bit HASHES of the records are keys those calls take), and biolib_amd::read_pool.  (Syncmers: bl_scan_syncmers128; window minimizers: bl_scan_minimizers128; super-k-mer records and the exact
- * counter: bl_pack_super_kmers128 .. bl_count_super_kmers128.) */
+ * What takes these values on: bl_sort_u128 / bl_sort_unique_u128 / bl_count_sorted_u128 / bl_jaccard_sorted_u128 / bl_partition_u128 and
+ * the run-file calls bl_write_run_u128 .. bl_merge_runs_u128 (16-byte keys in this layout); syncmers: bl_scan_syncmers128; window
+ * minimizers: bl_scan_minimizers128; super-k-mer records and the exact counter: bl_pack_super_kmers128 .. bl_count_super_kmers128.
+ * NOT covered for k > 32: biolib_amd::read_pool. */
 int bl_scan_kmers128(bl_ctx* ctx, const bl_batch* batch, uint64_t first, uint64_t n, uint32_t k, uint64_t seed, uint32_t flags,
                      uint64_t* d_values /* 2 per position: lo, hi */, uint64_t* d_hashes, uint8_t* d_valid, bl_result* result);
 
@@ -215,9 +218,9 @@ int bl_scan_hash_sample128(bl_ctx* ctx, const bl_batch* batch, uint64_t first, u
  * unit <= 32 through this entry: the values are bl_scan_minimizers' with a zero high word, but the key is 16 bytes instead of 8, so
  * the records differ in general — as the reference's template does between KmerType = uint64_t and __uint128_t.  w = 1 lists every
  * valid unit: bl_scan_hash_sample128 at threshold = UINT64_MAX, short of a unit whose hash is exactly 2^64 - 1.
- * bl_scan_minimizers keeps its limit of 32.  NOT provided: minimizer_view / super_kmer_view with m > 32, 128-bit keys in
- * sort / Jaccard / partition / spill, read_pool, and a read-tiled or approximate-hash variant of this kernel.  (Super-k-mer records and
- * the counter for k > 32: bl_pack_super_kmers128 .. bl_count_super_kmers128.) */
+ * bl_scan_minimizers keeps its limit of 32.  NOT provided: minimizer_view / super_kmer_view with m > 32, read_pool, and a read-tiled or
+ * approximate-hash variant of this kernel.  (Super-k-mer records and the counter for k > 32: bl_pack_super_kmers128 ..
+ * bl_count_super_kmers128; sort, unique, Jaccard, owner split and run files of the 16-byte units: the bl_*_u128 calls.) */
 int bl_scan_minimizers128(bl_ctx* ctx, const bl_batch* batch, uint64_t first, uint64_t n, uint32_t unit, uint32_t w, uint64_t seed,
                           uint32_t flags, uint64_t* d_values /* 2 per record */, uint64_t* d_positions, uint64_t* d_hashes,
                           uint64_t capacity, bl_result* result);
@@ -267,6 +270,8 @@ int bl_ctx_set_exact_windows(bl_ctx* ctx, int on);
  *                                 them a CU holds beside the next scan's hashing pass (0: the built-in default per scan kind)
  *   "count128_tables" 0 / 1       0: bl_count_super_kmers128 counts every bucket by expand + sort + run-length instead of the LDS tables
  *                                 (default 1)
+ *   "jaccard128_path" 0 / 1 / 2   which kernel bl_jaccard_sorted_u128 runs: 1 the merge kernel, 2 the search kernel, 0 (default) the
+ *                                 merge kernel when the larger set is less than 4 times the smaller one
  * The library reads no environment variable on the scan path. */
 int bl_ctx_set_option(bl_ctx* ctx, const char* name, int64_t value);
 
@@ -359,6 +364,29 @@ int bl_partition_u64(bl_ctx* ctx, const uint64_t* d_keys, uint64_t n, uint32_t p
 int bl_sort_u64(bl_ctx* ctx, uint64_t* d_keys, uint64_t n);
 int bl_count_sorted_u64(bl_ctx* ctx, const uint64_t* d_sorted, uint64_t n, uint64_t* d_unique, uint32_t* d_counts, uint64_t* n_unique);
 
+/* ---- the same set operations on 16-byte keys: k-mers of kmer_view<__uint128_t> (k up to 64) -----------------------------------------
+ * What the reference's Jaccard tool does after `typedef __uint128_t kmer_t;` (tests/test_jaccard.cpp): sort, unique, intersection.
+ * KEY LAYOUT  16 bytes per key: the LOW word, then the HIGH word — the object representation of __uint128_t, what bl_scan_kmers128,
+ *             bl_scan_hash_sample128 and bl_expand_super_kmers128 write; an array of n keys is a valid __uint128_t[n].
+ * ORDER       the numeric order of the 128-bit value: the high word decides, then the low word, both unsigned.
+ * ALIGNMENT   every key array must be 16-byte aligned (BL_ERR_INVALID otherwise).
+ * n = 0 succeeds and touches nothing.  Temporaries come from the context's scratch; the calls are synchronous.
+ * bl_sort_u128: ascending, in place, duplicates kept.  key_bits (1 .. 128) is the number of low bits that can be non-zero — 2k for
+ *   k-mers; the caller promises that the bits above are zero and the radix sort runs over [0, key_bits) only.  128 is always valid.
+ * bl_sort_unique_u128: sort + remove duplicates; *n_unique distinct keys are at the front afterwards.
+ * bl_count_sorted_u128: run-length count of a sorted list (n < 2^32): distinct keys, their multiplicities, their number.
+ * bl_jaccard_sorted_u128: |A n B| and |A u B| of two sorted duplicate-free arrays.  With duplicates in an input the two numbers are
+ *   unspecified, but no access leaves the arrays.  Two kernels: a merge-path kernel that streams both sets once (sets of comparable
+ *   size) and a binary-search kernel (sets of very different size); the option "jaccard128_path" of bl_ctx_set_option forces one.
+ * bl_partition_u128: bl_partition_u64's contract with bucket = bl_hash64_u128(lo, hi, seed) % parts, 1 <= parts <= 64; d_out takes
+ *   n keys, counts[b] (host) = size of bucket b. */
+int bl_sort_u128(bl_ctx* ctx, uint64_t* d_keys /* 2 per key: lo, hi */, uint64_t n, uint32_t key_bits);
+int bl_sort_unique_u128(bl_ctx* ctx, uint64_t* d_keys, uint64_t n, uint32_t key_bits, uint64_t* n_unique);
+int bl_count_sorted_u128(bl_ctx* ctx, const uint64_t* d_sorted, uint64_t n, uint64_t* d_unique, uint32_t* d_counts, uint64_t* n_unique);
+int bl_jaccard_sorted_u128(bl_ctx* ctx, const uint64_t* d_a, uint64_t na, const uint64_t* d_b, uint64_t nb, uint64_t* intersection,
+                           uint64_t* union_size);
+int bl_partition_u128(bl_ctx* ctx, const uint64_t* d_keys, uint64_t n, uint32_t parts, uint64_t seed, uint64_t* d_out, uint64_t* counts);
+
 /* Count reduction across the GPUs of one node: ctxs[g] is the context of device g (all distinct devices),
  * counters holds n_gpu rows of n 64-bit counters — row g = GPU g's local counts in, the column sums out (in every row).  One
  * ncclAllReduce(sum, uint64) per GPU over RCCL / xGMI, called on RCCL's C API directly (librccl.so.1 is loaded on first use);
@@ -424,9 +452,9 @@ int bl_expand_super_kmers(bl_ctx* ctx, const uint64_t* d_records, uint64_t n_gro
  *   each in an LDS table of 16-byte keys whose empty slots are marked by an owner word, not by a key value: every k and strand mode is
  *   taken, k = 64 without the canonical flag (the all-T 64-mer is all ones) included.  Oversized buckets take expand + 128-bit sort +
  *   run-length; bl_ctx_set_option("count128_tables", 0) sends every bucket that way (same result).  Terminates on any record bits.
- * NOT provided for k > 32: the fused in-scan record variant (bl_scan_super_kmer_records; records come from scan + pack here), 128-bit
- *   keys in bl_sort_unique_u64 / bl_jaccard_sorted_u64 and the spill formats, biolib_amd::read_pool for wide views, and any multi-GPU
- *   measurement of this path. */
+ *   (bl_sort_u128 / bl_count_sorted_u128 put the distinct k-mers in order.)
+ * NOT provided for k > 32: the fused in-scan record variant (bl_scan_super_kmer_records; records come from scan + pack here),
+ *   biolib_amd::read_pool for wide views, and any multi-GPU measurement of this path. */
 int bl_pack_super_kmers128(bl_ctx* ctx, const bl_batch* batch, const uint64_t* d_first_pos, const uint8_t* d_sizes, const uint8_t* d_mm_pos, uint64_t n_groups,
                            uint32_t k, uint32_t m, uint64_t* d_records /* 4 per group */);
 int bl_partition_records128(bl_ctx* ctx, const uint64_t* d_hashes, const uint64_t* d_records, uint64_t n, uint32_t parts, uint64_t* d_out, uint64_t* counts);
@@ -497,6 +525,19 @@ int bl_file_count_u64(const char* path, int with_count, uint64_t* n);
 int bl_read_file_u64_host(const char* path, int with_count, uint64_t* out, uint64_t capacity, uint64_t* n);
 int bl_read_file_u64(bl_ctx* ctx, const char* path, int with_count, uint64_t* d_out, uint64_t capacity, uint64_t* n);
 int bl_merge_runs_u64(bl_ctx* ctx, const char* const* paths, uint32_t n_paths, uint64_t* d_out, uint64_t capacity, uint64_t* n_total);
+
+/* The same files for 16-byte keys: emem::external_memory_vector<__uint128_t> and io::basic_store(std::vector<__uint128_t>).  A run
+ * file holds the sorted keys as raw 16-byte little-endian elements (low word first), no header; a stored vector is a size_t count
+ * followed by the elements.  This is what the reference writes when it is built the way its own CMake builds it — the GNU dialect
+ * gnu++17, under which std::is_fundamental<__uint128_t> holds, which io::basic_store asserts before it writes the raw bytes; a strict
+ * -std=c++17 build of the reference does not compile such a vector.  Arguments, capacities (in KEYS, two words each) and error codes as
+ * their u64 namesakes; the device arrays are 16-byte aligned. */
+int bl_write_run_u128(bl_ctx* ctx, const uint64_t* d_sorted_keys, uint64_t n, const char* path);
+int bl_write_vector_u128(bl_ctx* ctx, const uint64_t* d_keys, uint64_t n, const char* path);
+int bl_file_count_u128(const char* path, int with_count, uint64_t* n);
+int bl_read_file_u128_host(const char* path, int with_count, uint64_t* out /* 2 per key */, uint64_t capacity, uint64_t* n);
+int bl_read_file_u128(bl_ctx* ctx, const char* path, int with_count, uint64_t* d_out, uint64_t capacity, uint64_t* n);
+int bl_merge_runs_u128(bl_ctx* ctx, const char* const* paths, uint32_t n_paths, uint64_t* d_out, uint64_t capacity, uint64_t* n_total);
 
 /* ---- device memory helpers (for callers without their own allocator) ----------------------------- */
 int bl_device_alloc(bl_ctx* ctx, uint64_t bytes, void** d_ptr);

@@ -1,14 +1,14 @@
-// external_memory_vector.hpp — drop-in for biolib's include/external_memory_vector.hpp for the case the path uses:
-// emem::external_memory_vector<uint64_t> (sorted, default order), the container the reference's tools push k-mers into
-// (tests/test_jaccard.cpp:55-79) and then iterate in sorted order.
+// external_memory_vector.hpp — drop-in for biolib's include/external_memory_vector.hpp for the cases the path uses:
+// emem::external_memory_vector<uint64_t> and emem::external_memory_vector<__uint128_t> (sorted, default order), the container the
+// reference's tools push k-mers into (tests/test_jaccard.cpp:55-79, `typedef ... kmer_t`) and then iterate in sorted order.
 //
 // Same public surface (reference external_memory_vector.hpp:29-136): (available_space_bytes, tmp_dir, name), push_back,
 // cbegin/cend (forward iterator over the elements in sorted order, duplicates kept), size, minimize; and the same FILES:
-// when the buffer is full it is sorted and written as a run file <tmp_dir>/tmp.run[_<name>]_<id>.bin of raw 8-byte values
+// when the buffer is full it is sorted and written as a run file <tmp_dir>/tmp.run[_<name>]_<id>.bin of raw 8-byte (16-byte) values
 // (:243-262), removed by the destructor — so a process built on the reference can read the runs this one spills and vice
-// versa.  What differs is where the work happens: the buffer is sorted on the GPU (bl_sort_u64) and iteration does not run a
-// heap over memory-mapped runs (:265-347) — the runs are merged on the device (bl_merge_runs_u64) and the iterator walks the
-// merged array.  to_device() hands that array to device consumers (algorithm::jaccard_device) without a host round trip.
+// versa.  What differs is where the work happens: the buffer is sorted on the GPU (bl_sort_u64 / bl_sort_u128) and iteration does not
+// run a heap over memory-mapped runs (:265-347) — the runs are merged on the device (bl_merge_runs_u64 / _u128) and the iterator walks
+// the merged array.  to_device() hands that array to device consumers (algorithm::jaccard_device) without a host round trip.
 #ifndef BIOLIB_AMD_COMPAT_EXTERNAL_MEMORY_VECTOR_HPP
 #define BIOLIB_AMD_COMPAT_EXTERNAL_MEMORY_VECTOR_HPP
 
@@ -25,7 +25,11 @@ namespace emem {
 template <typename T, bool sorted = true>
 class external_memory_vector
 {
-    static_assert(std::is_same<T, uint64_t>::value and sorted, "the GPU path keeps sorted vectors of uint64_t (packed k-mers)");
+    static_assert((std::is_same<T, uint64_t>::value or std::is_same<T, __uint128_t>::value) and sorted,
+                  "the GPU path keeps sorted vectors of uint64_t or __uint128_t (packed k-mers)");
+    static constexpr bool wide = sizeof(T) == 16;
+    // a __uint128_t array is two words per key, low word first: the layout of the bl_*_u128 calls
+    static uint64_t* words(T* p) {return reinterpret_cast<uint64_t*>(p);}
 
     public:
         using value_type = T;
@@ -85,14 +89,15 @@ class external_memory_vector
         std::vector<std::string> const& run_files() const {return m_tmp_files;}
 
         // all elements, sorted (duplicates kept), in device memory: the k-way merge of the run files done on the GPU
-        std::shared_ptr<biolib_amd::device_array<uint64_t>> to_device() const
+        std::shared_ptr<biolib_amd::device_array<T>> to_device() const
         {
             const_cast<external_memory_vector*>(this)->minimize();
-            auto out = std::make_shared<biolib_amd::device_array<uint64_t>>(m_total_elems ? m_total_elems : 1);
+            auto out = std::make_shared<biolib_amd::device_array<T>>(m_total_elems ? m_total_elems : 1);
             std::vector<char const*> paths;
             for (auto const& f : m_tmp_files) paths.push_back(f.c_str());
             uint64_t total = 0;
-            biolib_amd::check(bl_merge_runs_u64(biolib_amd::context::get(), paths.data(), static_cast<uint32_t>(paths.size()), out->d, m_total_elems, &total), "bl_merge_runs_u64");
+            if (wide) biolib_amd::check(bl_merge_runs_u128(biolib_amd::context::get(), paths.data(), static_cast<uint32_t>(paths.size()), words(out->d), m_total_elems, &total), "bl_merge_runs_u128");
+            else biolib_amd::check(bl_merge_runs_u64(biolib_amd::context::get(), paths.data(), static_cast<uint32_t>(paths.size()), words(out->d), m_total_elems, &total), "bl_merge_runs_u64");
             if (total != m_total_elems) throw std::runtime_error("[EMV] run files do not hold the elements pushed");
             return out;
         }
@@ -113,12 +118,14 @@ class external_memory_vector
         }
         void sort_and_flush()
         {
-            biolib_amd::device_array<uint64_t> d(m_buffer.size());
+            biolib_amd::device_array<T> d(m_buffer.size());
             biolib_amd::check(bl_copy_to_device(biolib_amd::context::get(), d.d, m_buffer.data(), m_buffer.size() * sizeof(T)), "bl_copy_to_device");
-            biolib_amd::check(bl_sort_u64(biolib_amd::context::get(), d.d, m_buffer.size()), "bl_sort_u64");
+            if (wide) biolib_amd::check(bl_sort_u128(biolib_amd::context::get(), words(d.d), m_buffer.size(), 128), "bl_sort_u128");
+            else biolib_amd::check(bl_sort_u64(biolib_amd::context::get(), words(d.d), m_buffer.size()), "bl_sort_u64");
             char name[4096];
             biolib_amd::check(bl_run_file_name(m_tmp_dirname.c_str(), m_prefix.c_str(), m_tmp_files.size(), name, sizeof(name)), "bl_run_file_name");
-            biolib_amd::check(bl_write_run_u64(biolib_amd::context::get(), d.d, m_buffer.size(), name), "bl_write_run_u64");
+            if (wide) biolib_amd::check(bl_write_run_u128(biolib_amd::context::get(), words(d.d), m_buffer.size(), name), "bl_write_run_u128");
+            else biolib_amd::check(bl_write_run_u64(biolib_amd::context::get(), words(d.d), m_buffer.size(), name), "bl_write_run_u64");
             m_tmp_files.push_back(name);
             m_buffer.clear();
         }
