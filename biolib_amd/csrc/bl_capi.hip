@@ -15,9 +15,7 @@
 
 #include "../../include/biolib_amd.h"
 #include "bl_launch.hpp"
-#include "bl_kmers128_launch.hpp"
-#include "bl_syncmers128_launch.hpp"
-#include "bl_minimizers128_launch.hpp"
+#include "bl_scan128_launch.hpp"
 
 namespace {
 
@@ -934,6 +932,56 @@ static int prepare_kmers128(bl_ctx* c, const bl_batch* b, uint64_t first, uint64
     return BL_OK;
 }
 
+// Count -> tile prefix scan -> emit over the tiles of a 128-bit scan: the twin of scan_windows.  km: the Kmer128Params inside p.
+// lane_bytes: scratch per lane of every tile that pass 1 leaves for pass 2 — the u16 record mask (km.lane_masks) and, behind all the masks,
+// whatever else the family keeps (*lane_rest); 0: a count-only call that keeps neither.  family: the kernels' names in error texts.
+extern "C++" {  // (a template cannot have the C linkage of the entry points around it)
+template <typename P>
+static int scan_two_pass128(bl_ctx* c, P& p, bl::Kmer128Params& km, size_t lane_bytes, uint32_t** lane_rest, bool wants, uint64_t capacity, uint32_t flags,
+                            bl_result* result, hipError_t (*count)(const P&, hipStream_t), hipError_t (*emit)(const P&, hipStream_t), const char* family)
+{
+    km.capacity = wants ? capacity : 0;
+    int rc = begin_scan(c);
+    if (rc != BL_OK) return rc;
+    // scratch: tile counts + local prefixes + scan-block totals / prefixes
+    const size_t nt = (size_t)km.n_tiles, nb = (nt + bl::SCAN_BLK - 1) / bl::SCAN_BLK;
+    rc = grow(c, reinterpret_cast<void**>(&c->cur->tile_buf), &c->cur->tile_buf_bytes, (2 * nt + 2 * nb + 8) * sizeof(unsigned long long));
+    if (rc != BL_OK) return rc;
+    unsigned long long* tb = reinterpret_cast<unsigned long long*>(c->cur->tile_buf);
+    km.tile_counts = tb;
+    km.tile_base = tb + nt;
+    unsigned long long* block_tot = tb + 2 * nt;
+    km.block_base = block_tot + nb;
+    if (lane_bytes) {
+        rc = grow(c, reinterpret_cast<void**>(&c->cur->slot_buf), &c->cur->slot_buf_bytes, nt * bl::TPB * lane_bytes);
+        if (rc != BL_OK) return rc;
+        km.lane_masks = c->cur->slot_buf;
+        if (lane_rest) *lane_rest = reinterpret_cast<uint32_t*>(c->cur->slot_buf + nt * bl::TPB);  // nt * TPB u16: a multiple of 512 bytes
+    }
+    km.shards = c->shards();
+    rc = kernel_event(c, true);
+    if (rc != BL_OK) return rc;
+    hipError_t e = count(p, c->stream);  // pass 1 (timed alone)
+    if (e != hipSuccess) return fail(BL_ERR_HIP, std::string(family) + "_count_kernel: " + hipGetErrorString(e));
+    rc = kernel_event(c, false);
+    if (rc != BL_OK) return rc;
+    // the prefix scan of the window scans: it reads these four fields, and adds the total to the digest's count
+    bl::ScanParams sp{};
+    sp.tile_counts = km.tile_counts;
+    sp.tile_base = km.tile_base;
+    sp.block_base = km.block_base;
+    sp.shards = km.shards;
+    unsigned long long* carry = reinterpret_cast<unsigned long long*>(c->cur->ws);  // header word, zeroed by begin_scan
+    e = bl::launch_tile_scan(sp, bl::GroupRange{0, (uint32_t)km.n_tiles}, block_tot, carry, c->stream);
+    if (e != hipSuccess) return fail(BL_ERR_HIP, std::string("tile_scan: ") + hipGetErrorString(e));
+    if (wants) {
+        e = emit(p, c->stream);
+        if (e != hipSuccess) return fail(BL_ERR_HIP, std::string(family) + "_emit_kernel: " + hipGetErrorString(e));
+    }
+    return end_scan(c, 1u << 0, result, wants, capacity, flags);
+}
+}  // extern "C++"
+
 int bl_scan_kmers128(bl_ctx* c, const bl_batch* b, uint64_t first, uint64_t n, uint32_t k, uint64_t seed, uint32_t flags,
                      uint64_t* d_values, uint64_t* d_hashes, uint8_t* d_valid, bl_result* result)
 {
@@ -963,47 +1011,12 @@ int bl_scan_hash_sample128(bl_ctx* c, const bl_batch* b, uint64_t first, uint64_
     bool empty;
     int rc = prepare_kmers128(c, b, first, n, k, seed, flags, d_values, p, result, empty);
     if (rc != BL_OK || empty) return rc;
-    const bool wants = d_values || d_positions || d_hashes;
     p.hash_below = threshold;
     p.rec_value = d_values;
     p.rec_pos = d_positions;
     p.rec_hash = d_hashes;
-    p.capacity = wants ? capacity : 0;
-    rc = begin_scan(c);
-    if (rc != BL_OK) return rc;
-    // scratch: tile counts + local prefixes + scan-block totals / prefixes, and one u16 record mask per lane of every tile
-    const size_t nt = (size_t)p.n_tiles, nb = (nt + bl::SCAN_BLK - 1) / bl::SCAN_BLK;
-    rc = grow(c, reinterpret_cast<void**>(&c->cur->tile_buf), &c->cur->tile_buf_bytes, (2 * nt + 2 * nb + 8) * sizeof(unsigned long long));
-    if (rc != BL_OK) return rc;
-    rc = grow(c, reinterpret_cast<void**>(&c->cur->slot_buf), &c->cur->slot_buf_bytes, nt * bl::TPB * sizeof(uint16_t));
-    if (rc != BL_OK) return rc;
-    unsigned long long* tb = reinterpret_cast<unsigned long long*>(c->cur->tile_buf);
-    p.tile_counts = tb;
-    p.tile_base = tb + nt;
-    unsigned long long* block_tot = tb + 2 * nt;
-    p.block_base = block_tot + nb;
-    p.lane_masks = c->cur->slot_buf;
-    p.shards = c->shards();
-    rc = kernel_event(c, true);
-    if (rc != BL_OK) return rc;
-    hipError_t e = bl::launch_kmers128_count(p, c->stream);
-    if (e != hipSuccess) return fail(BL_ERR_HIP, std::string("kmer128_count_kernel: ") + hipGetErrorString(e));
-    rc = kernel_event(c, false);
-    if (rc != BL_OK) return rc;
-    // the prefix scan of the window scans: it reads these four fields, and adds the total to the digest's count
-    bl::ScanParams sp{};
-    sp.tile_counts = p.tile_counts;
-    sp.tile_base = p.tile_base;
-    sp.block_base = p.block_base;
-    sp.shards = p.shards;
-    unsigned long long* carry = reinterpret_cast<unsigned long long*>(c->cur->ws);  // header word, zeroed by begin_scan
-    e = bl::launch_tile_scan(sp, bl::GroupRange{0, (uint32_t)p.n_tiles}, block_tot, carry, c->stream);
-    if (e != hipSuccess) return fail(BL_ERR_HIP, std::string("tile_scan: ") + hipGetErrorString(e));
-    if (wants) {
-        e = bl::launch_kmers128_emit(p, c->stream);
-        if (e != hipSuccess) return fail(BL_ERR_HIP, std::string("kmer128_emit_kernel: ") + hipGetErrorString(e));
-    }
-    return end_scan(c, 1u << 0, result, wants, capacity, flags);
+    return scan_two_pass128(c, p, p, sizeof(uint16_t), nullptr, d_values || d_positions || d_hashes, capacity, flags, result, bl::launch_kmers128_count,
+                            bl::launch_kmers128_emit, "kmer128");
 }
 
 // ---- syncmers of 128-bit k-mers (k <= 64, s <= 32, 16-byte s-mer keys): bl_syncmers128.hip
@@ -1020,41 +1033,8 @@ int bl_scan_syncmers128(bl_ctx* c, const bl_batch* b, uint64_t first, uint64_t n
     if (rc != BL_OK || empty) return rc;
     bl::plan_syncmers128((int)k, (int)s, start_offset, end_offset, p);
     p.km.rec_pos = d_positions;
-    p.km.capacity = d_positions ? capacity : 0;
-    rc = begin_scan(c);
-    if (rc != BL_OK) return rc;
-    // scratch as for bl_scan_hash_sample128: tile counts + local prefixes + scan-block totals / prefixes, one u16 record mask per lane
-    const size_t nt = (size_t)p.km.n_tiles, nb = (nt + bl::SCAN_BLK - 1) / bl::SCAN_BLK;
-    rc = grow(c, reinterpret_cast<void**>(&c->cur->tile_buf), &c->cur->tile_buf_bytes, (2 * nt + 2 * nb + 8) * sizeof(unsigned long long));
-    if (rc != BL_OK) return rc;
-    rc = grow(c, reinterpret_cast<void**>(&c->cur->slot_buf), &c->cur->slot_buf_bytes, nt * bl::TPB * sizeof(uint16_t));
-    if (rc != BL_OK) return rc;
-    unsigned long long* tb = reinterpret_cast<unsigned long long*>(c->cur->tile_buf);
-    p.km.tile_counts = tb;
-    p.km.tile_base = tb + nt;
-    unsigned long long* block_tot = tb + 2 * nt;
-    p.km.block_base = block_tot + nb;
-    p.km.lane_masks = c->cur->slot_buf;
-    p.km.shards = c->shards();
-    rc = kernel_event(c, true);
-    if (rc != BL_OK) return rc;
-    hipError_t e = bl::launch_syncmers128_count(p, c->stream);
-    if (e != hipSuccess) return fail(BL_ERR_HIP, std::string("sync128_count_kernel: ") + hipGetErrorString(e));
-    rc = kernel_event(c, false);
-    if (rc != BL_OK) return rc;
-    bl::ScanParams sp{};  // the prefix scan reads these four fields, and adds the total to the digest's count
-    sp.tile_counts = p.km.tile_counts;
-    sp.tile_base = p.km.tile_base;
-    sp.block_base = p.km.block_base;
-    sp.shards = p.km.shards;
-    unsigned long long* carry = reinterpret_cast<unsigned long long*>(c->cur->ws);  // header word, zeroed by begin_scan
-    e = bl::launch_tile_scan(sp, bl::GroupRange{0, (uint32_t)p.km.n_tiles}, block_tot, carry, c->stream);
-    if (e != hipSuccess) return fail(BL_ERR_HIP, std::string("tile_scan: ") + hipGetErrorString(e));
-    if (d_positions) {
-        e = bl::launch_syncmers128_emit(p, c->stream);
-        if (e != hipSuccess) return fail(BL_ERR_HIP, std::string("sync128_emit_kernel: ") + hipGetErrorString(e));
-    }
-    return end_scan(c, 1u << 0, result, d_positions != nullptr, capacity, flags);
+    return scan_two_pass128(c, p, p.km, sizeof(uint16_t), nullptr, d_positions != nullptr, capacity, flags, result, bl::launch_syncmers128_count,
+                            bl::launch_syncmers128_emit, "sync128");
 }
 
 // ---- window minimizers of 128-bit k-mers (unit <= 64, w <= 64, 16-byte keys): bl_minimizers128.hip
@@ -1074,45 +1054,9 @@ int bl_scan_minimizers128(bl_ctx* c, const bl_batch* b, uint64_t first, uint64_t
     p.km.rec_value = d_values;
     p.km.rec_pos = d_positions;
     p.km.rec_hash = d_hashes;
-    p.km.capacity = wants ? capacity : 0;
-    rc = begin_scan(c);
-    if (rc != BL_OK) return rc;
-    // scratch: tile counts + local prefixes + scan-block totals / prefixes; per lane of every tile one u16 record mask and three
-    // dwords of occurrence offsets (a count-only call keeps neither)
-    const size_t nt = (size_t)p.km.n_tiles, nb = (nt + bl::SCAN_BLK - 1) / bl::SCAN_BLK;
-    rc = grow(c, reinterpret_cast<void**>(&c->cur->tile_buf), &c->cur->tile_buf_bytes, (2 * nt + 2 * nb + 8) * sizeof(unsigned long long));
-    if (rc != BL_OK) return rc;
-    unsigned long long* tb = reinterpret_cast<unsigned long long*>(c->cur->tile_buf);
-    p.km.tile_counts = tb;
-    p.km.tile_base = tb + nt;
-    unsigned long long* block_tot = tb + 2 * nt;
-    p.km.block_base = block_tot + nb;
-    if (wants) {
-        rc = grow(c, reinterpret_cast<void**>(&c->cur->slot_buf), &c->cur->slot_buf_bytes, nt * bl::TPB * (sizeof(uint16_t) + 3 * sizeof(uint32_t)));
-        if (rc != BL_OK) return rc;
-        p.km.lane_masks = c->cur->slot_buf;
-        p.lane_offs = reinterpret_cast<uint32_t*>(c->cur->slot_buf + nt * bl::TPB);  // nt * TPB u16: a multiple of 512 bytes
-    }
-    p.km.shards = c->shards();
-    rc = kernel_event(c, true);
-    if (rc != BL_OK) return rc;
-    hipError_t e = bl::launch_minimizers128_count(p, c->stream);
-    if (e != hipSuccess) return fail(BL_ERR_HIP, std::string("min128_count_kernel: ") + hipGetErrorString(e));
-    rc = kernel_event(c, false);
-    if (rc != BL_OK) return rc;
-    bl::ScanParams sp{};  // the prefix scan reads these four fields, and adds the total to the digest's count
-    sp.tile_counts = p.km.tile_counts;
-    sp.tile_base = p.km.tile_base;
-    sp.block_base = p.km.block_base;
-    sp.shards = p.km.shards;
-    unsigned long long* carry = reinterpret_cast<unsigned long long*>(c->cur->ws);  // header word, zeroed by begin_scan
-    e = bl::launch_tile_scan(sp, bl::GroupRange{0, (uint32_t)p.km.n_tiles}, block_tot, carry, c->stream);
-    if (e != hipSuccess) return fail(BL_ERR_HIP, std::string("tile_scan: ") + hipGetErrorString(e));
-    if (wants) {
-        e = bl::launch_minimizers128_emit(p, c->stream);
-        if (e != hipSuccess) return fail(BL_ERR_HIP, std::string("min128_emit_kernel: ") + hipGetErrorString(e));
-    }
-    return end_scan(c, 1u << 0, result, wants, capacity, flags);
+    // per lane of every tile one u16 record mask and three dwords of occurrence offsets; a count-only call keeps neither
+    return scan_two_pass128(c, p, p.km, wants ? sizeof(uint16_t) + 3 * sizeof(uint32_t) : 0, &p.lane_offs, wants, capacity, flags, result,
+                            bl::launch_minimizers128_count, bl::launch_minimizers128_emit, "min128");
 }
 
 uint64_t bl_hash64_u128(uint64_t lo, uint64_t hi, uint64_t seed) { return bl::murmur64_u128(lo, hi, (uint32_t)seed); }

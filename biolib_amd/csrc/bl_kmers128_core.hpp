@@ -64,6 +64,16 @@ struct Kmer128Params {
     unsigned long long* shards;        // [NSHARD][8]: count, xor low words, xor hashes, sum of hashes | xor of positions, xor high words
 };
 
+// stage_chunk (bl_scan_phases.hpp) stages the chunks of these scans too: the staging code only looks at these three fields
+BL_DEV ScanParams kmer128_staging_params(const Kmer128Params& p)
+{
+    ScanParams lp{};
+    lp.bases = p.bases;
+    lp.n_bases = p.n_bases;
+    lp.start_bits = p.start_bits;
+    return lp;
+}
+
 struct Kmer128Acc {
     unsigned long long cnt, xlo, xhi, xh, sx;
 };

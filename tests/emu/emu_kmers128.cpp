@@ -7,46 +7,9 @@
 //   dense  <canonical> <drop_last> count xor_lo xor_hi xor_hash sum_hash
 //   sample <canonical> <drop_last> count xor_lo xor_hi xor_hash xor_pos
 // and exits non-zero on the first disagreement with the plain loop.
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <vector>
-
+#define EMU_NAME "emu_kmers128"
+#include "emu128_common.hpp"
 #include "../../biolib_amd/csrc/bl_kmers128_core.hpp"
-
-typedef unsigned __int128 u128;
-
-static int nt4(uint8_t c)
-{
-    switch (c) {
-        case 'A': case 'a': return 0;
-        case 'C': case 'c': return 1;
-        case 'G': case 'g': return 2;
-        case 'T': case 't': case 'U': case 'u': return 3;
-        default: return 4;
-    }
-}
-
-static uint64_t rotl(uint64_t x, int r) { return (x << r) | (x >> (64 - r)); }
-static uint64_t fmix(uint64_t k)
-{
-    k ^= k >> 33; k *= 0xff51afd7ed558ccdULL; k ^= k >> 33; k *= 0xc4ceb9fe1a85ec53ULL; k ^= k >> 33;
-    return k;
-}
-// MurmurHash3_x64_128 of the 16 bytes of v, first word (written out here: no code shared with the header under test)
-static uint64_t plain_hash(u128 v, uint32_t seed)
-{
-    const uint64_t c1 = 0x87c37b91114253d5ULL, c2 = 0x4cf5ad432745937fULL;
-    uint64_t k1 = (uint64_t)v, k2 = (uint64_t)(v >> 64), h1 = seed, h2 = seed;
-    k1 *= c1; k1 = rotl(k1, 31); k1 *= c2; h1 ^= k1;
-    h1 = rotl(h1, 27); h1 += h2; h1 = h1 * 5 + 0x52dce729;
-    k2 *= c2; k2 = rotl(k2, 33); k2 *= c1; h2 ^= k2;
-    h2 = rotl(h2, 31); h2 += h1; h2 = h2 * 5 + 0x38495ab5;
-    h1 ^= 16; h2 ^= 16;
-    h1 += h2; h2 += h1;
-    h1 = fmix(h1); h2 = fmix(h2);
-    return h1 + h2;
-}
 
 struct Plain {
     std::vector<uint64_t> lo, hi, hash;
@@ -79,28 +42,13 @@ static Plain plain_scan(const std::vector<uint8_t>& seq, const std::vector<uint6
     return r;
 }
 
-#define CHECK(cond, ...)                          \
-    do {                                          \
-        if (!(cond)) {                            \
-            std::fprintf(stderr, "emu_kmers128: " __VA_ARGS__); \
-            std::fprintf(stderr, "\n");           \
-            std::exit(1);                         \
-        }                                         \
-    } while (0)
-
 int main(int argc, char** argv)
 {
     CHECK(argc == 6, "usage: emu_kmers128 <batch file> <k> <first> <n> <threshold>");
-    FILE* f = std::fopen(argv[1], "rb");
-    CHECK(f, "cannot open %s", argv[1]);
-    uint64_t hdr[2];
-    CHECK(std::fread(hdr, 8, 2, f) == 2, "short file");
-    const uint64_t n_bases = hdr[0], n_seqs = hdr[1];
-    std::vector<uint64_t> offs(n_seqs + 1);
-    CHECK(std::fread(offs.data(), 8, n_seqs + 1, f) == n_seqs + 1, "short file");
-    std::vector<uint8_t> seq(n_bases);
-    CHECK(n_bases == 0 || std::fread(seq.data(), 1, n_bases, f) == n_bases, "short file");
-    std::fclose(f);
+    const EmuBatch batch(argv[1]);
+    const uint64_t n_bases = batch.n_bases;
+    const std::vector<uint64_t>& offs = batch.offs;
+    const std::vector<uint8_t>& seq = batch.seq;
     const int k = std::atoi(argv[2]);
     const uint64_t first = std::strtoull(argv[3], nullptr, 10), n_arg = std::strtoull(argv[4], nullptr, 10);
     const uint64_t threshold = std::strtoull(argv[5], nullptr, 10);
@@ -109,20 +57,11 @@ int main(int argc, char** argv)
     const uint64_t origin = 1000000007ull;
     CHECK(k >= 1 && k <= bl::MAX_UNIT128 && first < end, "bad arguments");
 
-    // an exact-size heap copy of the bases (16-byte aligned as the device buffer is; the sanitizer sees every byte past n_bases)
-    uint8_t* exact = static_cast<uint8_t*>(std::malloc(n_bases ? n_bases : 1));
-    std::memcpy(exact, seq.data(), n_bases);
-    std::vector<uint32_t> start_bits((n_bases + 31) / 32 + 4, 0);
-    for (uint64_t q = 0; q < n_seqs; ++q)
-        if (offs[q] < n_bases) start_bits[offs[q] >> 5] |= 1u << (offs[q] & 31);
-
     for (int canonical = 0; canonical < 2; ++canonical) {
         for (int drop_last = 0; drop_last < 2; ++drop_last) {
             const Plain want = plain_scan(seq, offs, k, seed, canonical, drop_last);
             bl::Kmer128Params p{};
-            p.bases = exact;
-            p.n_bases = (int64_t)n_bases;
-            p.start_bits = start_bits.data();
+            batch.describe(p);
             p.pos_base = (int64_t)origin;
             bl::plan_kmers128((int64_t)first, (int64_t)end, p);
             p.unit = k;
@@ -130,10 +69,6 @@ int main(int argc, char** argv)
             p.canonical = canonical;
             p.drop_last = drop_last;
             p.hash_below = threshold;
-            bl::ScanParams lp{};
-            lp.bases = p.bases;
-            lp.n_bases = p.n_bases;
-            lp.start_bits = p.start_bits;
             const size_t span = end - first;
             // exact-size outputs: a store outside [0, span) is a finding
             std::vector<bl::U64x2> out_value(span);
@@ -145,7 +80,7 @@ int main(int argc, char** argv)
             bl::Kmer128Acc dense{0, 0, 0, 0, 0}, digest_only{0, 0, 0, 0, 0}, samp{0, 0, 0, 0, 0};
             for (int tile = 0; tile < p.n_tiles; ++tile) {
                 const int64_t q0 = p.origin + (int64_t)tile * bl::H;
-                for (int c = 0; c < bl::NCHUNK_POS; ++c) bl::stage_chunk(lp, codes.data(), flags.data(), c, q0);
+                stage_all(p, codes, flags, q0);
                 unsigned long long cnt = 0;
                 for (int tid = 0; tid < bl::TPB; ++tid) {
                     p.out_value = reinterpret_cast<uint64_t*>(out_value.data());
@@ -199,7 +134,7 @@ int main(int argc, char** argv)
                 p.capacity = cap;
                 for (int tile = 0; tile < p.n_tiles; ++tile) {
                     const int64_t q0 = p.origin + (int64_t)tile * bl::H;
-                    for (int c = 0; c < bl::NCHUNK_POS; ++c) bl::stage_chunk(lp, codes.data(), flags.data(), c, q0);
+                    stage_all(p, codes, flags, q0);
                     uint64_t at = tile_base[tile];
                     for (int tid = 0; tid < bl::TPB; ++tid) {
                         const uint32_t sel = masks[(size_t)tile * bl::TPB + tid];
@@ -225,6 +160,5 @@ int main(int argc, char** argv)
             std::printf("sample %d %d %llu %llu %llu %llu %llu\n", canonical, drop_last, samp.cnt, samp.xlo, samp.xhi, samp.xh, samp.sx);
         }
     }
-    std::free(exact);
     return 0;
 }

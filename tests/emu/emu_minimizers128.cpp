@@ -7,46 +7,9 @@
 // batch file: u64 n_bases, u64 n_seqs, u64 offsets[n_seqs + 1], bases.  For canonical x drop_last it prints
 //   min <canonical> <drop_last> count xor_value aux xor_hash xor_pos
 // and exits non-zero on the first disagreement with the plain evaluation.
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <vector>
-
+#define EMU_NAME "emu_minimizers128"
+#include "emu128_common.hpp"
 #include "../../biolib_amd/csrc/bl_minimizers128_core.hpp"
-
-typedef unsigned __int128 u128;
-
-static int nt4(uint8_t c)
-{
-    switch (c) {
-        case 'A': case 'a': return 0;
-        case 'C': case 'c': return 1;
-        case 'G': case 'g': return 2;
-        case 'T': case 't': case 'U': case 'u': return 3;
-        default: return 4;
-    }
-}
-
-static uint64_t rotl(uint64_t x, int r) { return (x << r) | (x >> (64 - r)); }
-static uint64_t fmix(uint64_t k)
-{
-    k ^= k >> 33; k *= 0xff51afd7ed558ccdULL; k ^= k >> 33; k *= 0xc4ceb9fe1a85ec53ULL; k ^= k >> 33;
-    return k;
-}
-// MurmurHash3_x64_128 of the 16 bytes of v, first word (written out here: no code shared with the header under test)
-static uint64_t plain_hash(u128 v, uint32_t seed)
-{
-    const uint64_t c1 = 0x87c37b91114253d5ULL, c2 = 0x4cf5ad432745937fULL;
-    uint64_t k1 = (uint64_t)v, k2 = (uint64_t)(v >> 64), h1 = seed, h2 = seed;
-    k1 *= c1; k1 = rotl(k1, 31); k1 *= c2; h1 ^= k1;
-    h1 = rotl(h1, 27); h1 += h2; h1 = h1 * 5 + 0x52dce729;
-    k2 *= c2; k2 = rotl(k2, 33); k2 *= c1; h2 ^= k2;
-    h2 = rotl(h2, 31); h2 += h1; h2 = h2 * 5 + 0x38495ab5;
-    h1 ^= 16; h2 ^= 16;
-    h1 += h2; h2 += h1;
-    h1 = fmix(h1); h2 = fmix(h2);
-    return h1 + h2;
-}
 
 struct Plain {
     std::vector<uint8_t> valid;
@@ -88,41 +51,19 @@ static Plain plain_scan(const std::vector<uint8_t>& seq, const std::vector<uint6
     return r;
 }
 
-#define CHECK(cond, ...)                          \
-    do {                                          \
-        if (!(cond)) {                            \
-            std::fprintf(stderr, "emu_minimizers128: " __VA_ARGS__); \
-            std::fprintf(stderr, "\n");           \
-            std::exit(1);                         \
-        }                                         \
-    } while (0)
-
 int main(int argc, char** argv)
 {
     CHECK(argc == 6, "usage: emu_minimizers128 <batch file> <unit> <w> <first> <n>");
-    FILE* f = std::fopen(argv[1], "rb");
-    CHECK(f, "cannot open %s", argv[1]);
-    uint64_t hdr[2];
-    CHECK(std::fread(hdr, 8, 2, f) == 2, "short file");
-    const uint64_t n_bases = hdr[0], n_seqs = hdr[1];
-    std::vector<uint64_t> offs(n_seqs + 1);
-    CHECK(std::fread(offs.data(), 8, n_seqs + 1, f) == n_seqs + 1, "short file");
-    std::vector<uint8_t> seq(n_bases);
-    CHECK(n_bases == 0 || std::fread(seq.data(), 1, n_bases, f) == n_bases, "short file");
-    std::fclose(f);
+    const EmuBatch batch(argv[1]);
+    const uint64_t n_bases = batch.n_bases;
+    const std::vector<uint64_t>& offs = batch.offs;
+    const std::vector<uint8_t>& seq = batch.seq;
     const int k = std::atoi(argv[2]), w = std::atoi(argv[3]);
     const uint64_t first = std::strtoull(argv[4], nullptr, 10), n_arg = std::strtoull(argv[5], nullptr, 10);
     const uint64_t end = (n_arg == 0 || first + n_arg > n_bases) ? n_bases : first + n_arg;
     const uint32_t seed = 0x9e3779b9u;
     const uint64_t origin = 1000000007ull;
     CHECK(k >= 1 && k <= bl::MAX_UNIT128 && w >= 1 && w <= bl::MAX_W && first < end, "bad arguments");
-
-    // an exact-size heap copy of the bases (16-byte aligned as the device buffer is; the sanitizer sees every byte past n_bases)
-    uint8_t* exact = static_cast<uint8_t*>(std::malloc(n_bases ? n_bases : 1));
-    std::memcpy(exact, seq.data(), n_bases);
-    std::vector<uint32_t> start_bits((n_bases + 31) / 32 + 4, 0);
-    for (uint64_t q = 0; q < n_seqs; ++q)
-        if (offs[q] < n_bases) start_bits[offs[q] >> 5] |= 1u << (offs[q] & 31);
 
     for (int canonical = 0; canonical < 2; ++canonical) {
         for (int drop_last = 0; drop_last < 2; ++drop_last) {
@@ -132,9 +73,7 @@ int main(int argc, char** argv)
                 return q == 0 || want.occ[q - 1] != want.occ[q];
             };
             bl::Min128Params p{};
-            p.km.bases = exact;
-            p.km.n_bases = (int64_t)n_bases;
-            p.km.start_bits = start_bits.data();
+            batch.describe(p.km);
             p.km.pos_base = (int64_t)origin;
             bl::plan_kmers128((int64_t)first, (int64_t)end, p.km);
             p.km.unit = k;
@@ -142,10 +81,6 @@ int main(int argc, char** argv)
             p.km.canonical = canonical;
             p.km.drop_last = drop_last;
             p.w = w;
-            bl::ScanParams lp{};
-            lp.bases = p.km.bases;
-            lp.n_bases = p.km.n_bases;
-            lp.start_bits = p.km.start_bits;
             // exact sizes: a read or write outside them is a finding
             std::vector<uint32_t> codes(bl::MIN128_NCHUNK), flags(bl::MIN128_NCHUNK);
             std::vector<uint64_t> lds(bl::MIN128_SLOTS);
@@ -156,7 +91,7 @@ int main(int argc, char** argv)
             bl::Kmer128Acc acc{0, 0, 0, 0, 0};
             for (int tile = 0; tile < p.km.n_tiles; ++tile) {
                 const int64_t r0 = p.km.origin + (int64_t)tile * bl::H - 16;
-                for (int c = 0; c < bl::MIN128_NCHUNK; ++c) bl::stage_chunk(lp, codes.data(), flags.data(), c, r0);
+                stage_all(p.km, codes, flags, r0);
                 // every phase between two barriers runs for all lanes before the next one starts.  The arrays are zeroed first: a
                 // window that read a word phase A did not write would find a minimum (or an invalid unit) there
                 std::fill(lds.begin(), lds.end(), 0);
@@ -212,7 +147,7 @@ int main(int argc, char** argv)
                 p.km.capacity = cap;
                 for (int tile = 0; tile < p.km.n_tiles; ++tile) {
                     const int64_t r0 = p.km.origin + (int64_t)tile * bl::H - 16;
-                    for (int c = 0; c < bl::MIN128_NCHUNK; ++c) bl::stage_chunk(lp, codes.data(), flags.data(), c, r0);
+                    stage_all(p.km, codes, flags, r0);
                     uint64_t at = tile_base[tile];
                     for (int tid = 0; tid < bl::TPB; ++tid) {
                         const uint32_t sel = masks[(size_t)tile * bl::TPB + tid];
@@ -227,6 +162,5 @@ int main(int argc, char** argv)
             std::printf("min %d %d %llu %llu %llu %llu %llu\n", canonical, drop_last, total, acc.xlo, acc.xhi, acc.xh, acc.sx);
         }
     }
-    std::free(exact);
     return 0;
 }

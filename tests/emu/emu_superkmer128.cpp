@@ -12,21 +12,10 @@
 //               minhash <xor of the records' minimizer hashes>   sk128_minimizer_hash == the plain evaluation
 //               path table|fallback, rounds <records per round ...>
 //               kmer <lo> <hi> <count>                 the table's contents, slot order (table path only)
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <vector>
-
+#define EMU_NAME "emu_superkmer128"
+#include "emu128_common.hpp"  // u128, rotl, fmix
 #include "../../biolib_amd/csrc/bl_superkmer128_core.hpp"
 
-typedef unsigned __int128 u128;
-
-static uint64_t rotl(uint64_t x, int r) { return (x << r) | (x >> (64 - r)); }
-static uint64_t fmix(uint64_t k)
-{
-    k ^= k >> 33; k *= 0xff51afd7ed558ccdULL; k ^= k >> 33; k *= 0xc4ceb9fe1a85ec53ULL; k ^= k >> 33;
-    return k;
-}
 // MurmurHash3_x64_128 of the 8 bytes of v, first word (written out here: no code shared with the header under test)
 static uint64_t plain_hash8(uint64_t v, uint32_t seed)
 {

@@ -7,46 +7,9 @@
 // batch file: u64 n_bases, u64 n_seqs, u64 offsets[n_seqs + 1], bases.  For canonical x drop_last it prints
 //   sync <canonical> <drop_last> count xor_pos
 // and exits non-zero on the first disagreement with the plain evaluation.
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <vector>
-
+#define EMU_NAME "emu_syncmers128"
+#include "emu128_common.hpp"
 #include "../../biolib_amd/csrc/bl_syncmers128_core.hpp"
-
-typedef unsigned __int128 u128;
-
-static int nt4(uint8_t c)
-{
-    switch (c) {
-        case 'A': case 'a': return 0;
-        case 'C': case 'c': return 1;
-        case 'G': case 'g': return 2;
-        case 'T': case 't': case 'U': case 'u': return 3;
-        default: return 4;
-    }
-}
-
-static uint64_t rotl(uint64_t x, int r) { return (x << r) | (x >> (64 - r)); }
-static uint64_t fmix(uint64_t k)
-{
-    k ^= k >> 33; k *= 0xff51afd7ed558ccdULL; k ^= k >> 33; k *= 0xc4ceb9fe1a85ec53ULL; k ^= k >> 33;
-    return k;
-}
-// MurmurHash3_x64_128 of the 16 bytes of v, first word (written out here: no code shared with the header under test)
-static uint64_t plain_hash(u128 v, uint32_t seed)
-{
-    const uint64_t c1 = 0x87c37b91114253d5ULL, c2 = 0x4cf5ad432745937fULL;
-    uint64_t k1 = (uint64_t)v, k2 = (uint64_t)(v >> 64), h1 = seed, h2 = seed;
-    k1 *= c1; k1 = rotl(k1, 31); k1 *= c2; h1 ^= k1;
-    h1 = rotl(h1, 27); h1 += h2; h1 = h1 * 5 + 0x52dce729;
-    k2 *= c2; k2 = rotl(k2, 33); k2 *= c1; h2 ^= k2;
-    h2 = rotl(h2, 31); h2 += h1; h2 = h2 * 5 + 0x38495ab5;
-    h1 ^= 16; h2 ^= 16;
-    h1 += h2; h2 += h1;
-    h1 = fmix(h1); h2 = fmix(h2);
-    return h1 + h2;
-}
 
 // per position: 1 + the extractor's offset of the (canonical) k-mer that starts there, 0 where none does
 static std::vector<int> plain_offsets(const std::vector<uint8_t>& seq, const std::vector<uint64_t>& offs, int k, int s, uint32_t seed, bool canonical, bool drop_last)
@@ -80,28 +43,13 @@ static std::vector<int> plain_offsets(const std::vector<uint8_t>& seq, const std
     return r;
 }
 
-#define CHECK(cond, ...)                          \
-    do {                                          \
-        if (!(cond)) {                            \
-            std::fprintf(stderr, "emu_syncmers128: " __VA_ARGS__); \
-            std::fprintf(stderr, "\n");           \
-            std::exit(1);                         \
-        }                                         \
-    } while (0)
-
 int main(int argc, char** argv)
 {
     CHECK(argc == 8, "usage: emu_syncmers128 <batch file> <k> <s> <first> <n> <start_offset> <end_offset>");
-    FILE* f = std::fopen(argv[1], "rb");
-    CHECK(f, "cannot open %s", argv[1]);
-    uint64_t hdr[2];
-    CHECK(std::fread(hdr, 8, 2, f) == 2, "short file");
-    const uint64_t n_bases = hdr[0], n_seqs = hdr[1];
-    std::vector<uint64_t> offs(n_seqs + 1);
-    CHECK(std::fread(offs.data(), 8, n_seqs + 1, f) == n_seqs + 1, "short file");
-    std::vector<uint8_t> seq(n_bases);
-    CHECK(n_bases == 0 || std::fread(seq.data(), 1, n_bases, f) == n_bases, "short file");
-    std::fclose(f);
+    const EmuBatch batch(argv[1]);
+    const uint64_t n_bases = batch.n_bases;
+    const std::vector<uint64_t>& offs = batch.offs;
+    const std::vector<uint8_t>& seq = batch.seq;
     const int k = std::atoi(argv[2]), s = std::atoi(argv[3]);
     const uint64_t first = std::strtoull(argv[4], nullptr, 10), n_arg = std::strtoull(argv[5], nullptr, 10);
     const uint32_t soff = (uint32_t)std::strtoul(argv[6], nullptr, 10), eoff = (uint32_t)std::strtoul(argv[7], nullptr, 10);
@@ -120,30 +68,17 @@ int main(int argc, char** argv)
         CHECK(got == bl::murmur64_u128(key, 0, sd) && got == plain_hash(key, sd), "murmur64_u128_lo(%llx, %x)", (unsigned long long)key, sd);
     }
 
-    // an exact-size heap copy of the bases (16-byte aligned as the device buffer is; the sanitizer sees every byte past n_bases)
-    uint8_t* exact = static_cast<uint8_t*>(std::malloc(n_bases ? n_bases : 1));
-    std::memcpy(exact, seq.data(), n_bases);
-    std::vector<uint32_t> start_bits((n_bases + 31) / 32 + 4, 0);
-    for (uint64_t q = 0; q < n_seqs; ++q)
-        if (offs[q] < n_bases) start_bits[offs[q] >> 5] |= 1u << (offs[q] & 31);
-
     for (int canonical = 0; canonical < 2; ++canonical) {
         for (int drop_last = 0; drop_last < 2; ++drop_last) {
             const std::vector<int> want = plain_offsets(seq, offs, k, s, seed, canonical, drop_last);
             bl::Sync128Params p{};
-            p.km.bases = exact;
-            p.km.n_bases = (int64_t)n_bases;
-            p.km.start_bits = start_bits.data();
+            batch.describe(p.km);
             p.km.pos_base = (int64_t)origin;
             bl::plan_kmers128((int64_t)first, (int64_t)end, p.km);
             p.km.seed = seed;
             p.km.canonical = canonical;
             p.km.drop_last = drop_last;
             bl::plan_syncmers128(k, s, soff, eoff, p);
-            bl::ScanParams lp{};
-            lp.bases = p.km.bases;
-            lp.n_bases = p.km.n_bases;
-            lp.start_bits = p.km.start_bits;
             std::vector<uint32_t> codes(bl::NCHUNK_POS), flags(bl::NCHUNK_POS);
             std::vector<uint64_t> lds(bl::SYNC128_SLOTS);  // exact size: a read or write outside it is a finding
             std::vector<uint16_t> masks((size_t)p.km.n_tiles * bl::TPB);
@@ -152,7 +87,7 @@ int main(int argc, char** argv)
             unsigned long long xor_pos = 0;
             for (int tile = 0; tile < p.km.n_tiles; ++tile) {
                 const int64_t q0 = p.km.origin + (int64_t)tile * bl::H;
-                for (int c = 0; c < bl::NCHUNK_POS; ++c) bl::stage_chunk(lp, codes.data(), flags.data(), c, q0);
+                stage_all(p.km, codes, flags, q0);
                 // every phase between two barriers runs for all lanes before the next one starts.  The array is zeroed first: a
                 // window that read a word phase A did not write would find a minimum there
                 std::fill(lds.begin(), lds.end(), 0);
@@ -215,6 +150,5 @@ int main(int argc, char** argv)
             std::printf("sync %d %d %llu %llu\n", canonical, drop_last, total, xor_pos);
         }
     }
-    std::free(exact);
     return 0;
 }

@@ -20,7 +20,7 @@ import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, ROOT)
-SOURCES = ("bl_kmers128.hip", "bl_kmers128_core.hpp", "bl_kmers128_launch.hpp", "bl_kernels.hip", "bl_scan_core.hpp", "bl_scan_phases.hpp")
+SOURCES = ("bl_kmers128.hip", "bl_kmers128_core.hpp", "bl_scan128_launch.hpp", "bl_tile128.hpp", "bl_kernels.hip", "bl_scan_core.hpp", "bl_scan_phases.hpp")
 
 
 def sources_digest():

@@ -22,7 +22,7 @@ import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, ROOT)
-SOURCES = ("bl_minimizers128.hip", "bl_minimizers128_core.hpp", "bl_minimizers128_launch.hpp", "bl_kmers128.hip", "bl_kmers128_core.hpp", "bl_kernels.hip",
+SOURCES = ("bl_minimizers128.hip", "bl_minimizers128_core.hpp", "bl_scan128_launch.hpp", "bl_tile128.hpp", "bl_kmers128.hip", "bl_kmers128_core.hpp", "bl_kernels.hip",
            "bl_scan_core.hpp", "bl_scan_phases.hpp")
 SHAPES = ((33, 11), (51, 11), (64, 11), (64, 64), (33, 2))
 
