@@ -22,7 +22,7 @@ SYMBOLS = [
     "bl_reader_next_batch", "bl_reader_last_batch", "bl_reader_last_name", "bl_batch_from_text", "bl_run_file_name", "bl_write_run_u64", "bl_write_vector_u64", "bl_file_count_u64", "bl_read_file_u64_host", "bl_read_file_u64", "bl_merge_runs_u64", "bl_count_allreduce",
     "bl_device_alloc", "bl_device_free", "bl_copy_to_host", "bl_copy_to_device", "bl_hash64_u64", "bl_bgzf_walk", "bl_bgzf_inflate", "bl_host_alloc", "bl_host_free", "bl_reader_open_shard", "bl_reader_shard_range",
     "bl_scan_kmers128", "bl_scan_hash_sample128", "bl_hash64_u128", "bl_scan_syncmers128", "bl_scan_minimizers128",
-    "bl_pack_super_kmers128", "bl_partition_records128", "bl_expand_super_kmers128", "bl_count_super_kmers128",
+    "bl_scan_super_kmer_records128", "bl_pack_super_kmers128", "bl_partition_records128", "bl_expand_super_kmers128", "bl_count_super_kmers128",
     "bl_sort_u128", "bl_sort_unique_u128", "bl_count_sorted_u128", "bl_jaccard_sorted_u128", "bl_partition_u128",
     "bl_write_run_u128", "bl_write_vector_u128", "bl_file_count_u128", "bl_read_file_u128_host", "bl_read_file_u128", "bl_merge_runs_u128",
 ]
@@ -149,6 +149,8 @@ def lib():
     L.bl_scan_hash_sample128.argtypes = [vp, vp, u64, u64, u32, u64, u64, u32, vp, vp, vp, u64, C.POINTER(Result)]
     L.bl_scan_syncmers128.argtypes = [vp, vp, u64, u64, u32, u32, u32, u32, u64, u32, vp, u64, C.POINTER(Result)]
     L.bl_scan_minimizers128.argtypes = [vp, vp, u64, u64, u32, u32, u64, u32, vp, vp, vp, u64, C.POINTER(Result)]
+    if "BIOLIB_AMD_LIB" not in os.environ or hasattr(L, "bl_scan_super_kmer_records128"):  # (an A/B build of an older revision lacks it)
+        L.bl_scan_super_kmer_records128.argtypes = [vp, vp, u64, u64, u32, u32, u64, u32, vp, vp, u64, C.POINTER(Result)]
     L.bl_pack_super_kmers128.argtypes = [vp, vp, vp, vp, vp, u64, u32, u32, vp]
     L.bl_partition_records128.argtypes = [vp, vp, vp, u64, u32, vp, vp]
     L.bl_expand_super_kmers128.argtypes = [vp, vp, u64, u32, u32, vp, u64, C.POINTER(u64)]

@@ -1208,6 +1208,25 @@ int bl_scan_super_kmer_records(bl_ctx* c, const bl_batch* b, uint64_t first, uin
     return end_scan(c, (1u << 0) | (1u << 4), result, wants, capacity, flags);
 }
 
+// The same scan with the 32-byte record of bl_superkmer128.hip built in pass 2 (emit_record128): what bl_scan_super_kmers followed by
+// bl_pack_super_kmers128 gives, without the per-group arrays and the second pass over the bases in between.
+int bl_scan_super_kmer_records128(bl_ctx* c, const bl_batch* b, uint64_t first, uint64_t n, uint32_t k, uint32_t m, uint64_t seed, uint32_t flags,
+                                  uint64_t* d_records, uint64_t* d_hashes, uint64_t capacity, bl_result* result)
+{
+    if (m < 1 || m > 32 || k < m || k > 64 || k - m + 1 > 64 || 2 * k - m > 122)
+        return fail(BL_ERR_INVALID, "need 1 <= m <= 32, m <= k <= 64, k - m + 1 <= 64 and 2k - m <= 122 (bases per 32-byte record)");
+    if ((uintptr_t)d_records & 31u) return fail(BL_ERR_INVALID, "d_records must be 32-byte aligned");
+    if (!c) return fail(BL_ERR_INVALID, "ctx is NULL");
+    bl::ScanParams p{};
+    p.out_records = d_records;
+    p.out_hash = d_hashes;
+    p.records128 = 1;  // four words per group; position-tiled tiles stage what a group of 122 bases needs (staged_chunks)
+    const bool wants = d_records || d_hashes;
+    int rc = scan_windows(bl::MODE_SUPERKMER, c, b, first, n, m, k - m + 1, seed, flags, p, wants ? capacity : 0, result);
+    if (rc != BL_OK || p.n_tiles == 0) return rc;
+    return end_scan(c, (1u << 0) | (1u << 4), result, wants, capacity, flags);
+}
+
 int bl_scan_syncmers(bl_ctx* c, const bl_batch* b, uint64_t first, uint64_t n, uint32_t k, uint32_t s, uint32_t start_offset,
                      uint32_t end_offset, uint64_t seed, uint32_t flags, uint64_t* d_positions, uint64_t capacity, bl_result* result)
 {

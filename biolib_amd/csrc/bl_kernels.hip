@@ -270,7 +270,8 @@ __device__ __forceinline__ void count_tile_frl(const ScanParams& p, TileShared<M
 // C3: the C3 shape (emit_c3): `codes` holds two strands, the tile's codes from codes[1] on and their reverse complement from
 // codes[C3_RC + 1] on (unit31_canonical), each behind one dword it may read and mask away.
 constexpr int C3_RC = NCHUNK + 4;
-template <int MODE, bool LOOPED = false, bool C3 = false>
+// WIDE: out_records takes the 32-byte record (emit_record128) instead of the 16-byte one.
+template <int MODE, bool LOOPED = false, bool C3 = false, bool WIDE = false>
 __device__ __forceinline__ void emit_tile(const ScanParams& p, uint32_t* codes, uint32_t tile, int tid, Digest& dg)
 {
     // one memory round trip for the common case: every load of the tile — counts, offsets, codes, the first 2 * TPB list entries
@@ -325,7 +326,11 @@ __device__ __forceinline__ void emit_tile(const ScanParams& p, uint32_t* codes, 
         if (MODE == MODE_SUPERKMER && (p.out_size || p.out_records) && (fits || base_s + r < p.capacity)) {
             const int size = (int)(end_position(p, L, tile, q0, r + d, n_e) - (int64_t)rec.first + 1);
             if (p.out_size) p.out_size[base_s + r] = (uint8_t)size;
-            if (p.out_records) emit_record(p, codes, needed - 1, q0, rec, size, base_s + r);
+            if (WIDE) {
+                if (p.out_records) emit_record128(p, codes, needed - 1, q0, rec, size, base_s + r);
+            } else if (p.out_records) {
+                emit_record(p, codes, needed - 1, q0, rec, size, base_s + r);
+            }
         }
     };
     // (fences: left alone the scheduler interleaves the two records for instruction-level parallelism — 30 registers instead of 22, and
@@ -453,9 +458,12 @@ constexpr int emit_tiles() { return MODE == MODE_MINIMIZER ? BL_EMIT_TILES : 1; 
 // C3 (minimizers of canonical 31-mers, read-tiled): each code buffer holds the reverse-complemented strand too (emit_tile).
 template <int MODE, int U, int C, int FRL>
 constexpr bool emit_c3() { return MODE == MODE_MINIMIZER && U == 31 && C == 1 && FRL == 1; }
-template <int MODE, int U = 0, int C = -1, int FRL = -1>
+// WIDE: super-k-mer scans that hand out 32-byte records (p.records128): the one instantiation that packs them (emit_tile) — the
+// others carry no branch for it.
+template <int MODE, int U = 0, int C = -1, int FRL = -1, bool WIDE = false>
 __global__ __launch_bounds__(TPB) void scan_emit_kernel(const ScanParams pin, GroupRange g)
 {
+    static_assert(!WIDE || (MODE == MODE_SUPERKMER && U == 0), "32-byte records are super-k-mer groups; the unit length comes from the arguments");
     constexpr int K = emit_tiles<MODE>();
     constexpr bool C3 = emit_c3<MODE, U, C, FRL>();
     __shared__ uint32_t codes[K > 1 ? 2 : 1][C3 ? 2 * C3_RC : NCHUNK];
@@ -483,7 +491,7 @@ __global__ __launch_bounds__(TPB) void scan_emit_kernel(const ScanParams pin, Gr
         dg.xp = ((unsigned long long)acc[5][tid] << 32) | acc[4][tid];
     } else {
         if (blockIdx.x >= g.count) return;
-        emit_tile<MODE, false, C3>(p, codes[0], g.first + blockIdx.x, tid, dg);
+        emit_tile<MODE, false, C3, WIDE>(p, codes[0], g.first + blockIdx.x, tid, dg);
     }
 
     // digest: wave reduce (DPP xor-scan), then one set of atomics per WAVE into a shard line.  Measured alternatives: an LDS stage
@@ -845,6 +853,10 @@ static void launch_emit_mode(const ScanParams& p, GroupRange g, hipStream_t stre
     if (MODE == MODE_MINIMIZER && p.frl && p.unit == 31 && p.canonical) {  // BASELINE C3: code buffers of two strands (emit_c3)
         const uint32_t have_c3 = (uint32_t)(((K > 1 ? 2 : 1) * 2 * C3_RC + (K > 1 ? 6 * TPB : 0)) * sizeof(uint32_t));
         hipLaunchKernelGGL((scan_emit_kernel<MODE_MINIMIZER, 31, 1, 1>), grid, block, lds_per_wg > have_c3 ? lds_per_wg - have_c3 : 0, stream, p, g);
+        return;
+    }
+    if (MODE == MODE_SUPERKMER && p.records128) {  // 32-byte records: the instantiation that packs them (same LDS footprint)
+        hipLaunchKernelGGL((scan_emit_kernel<MODE_SUPERKMER, 0, -1, -1, true>), grid, block, pad, stream, p, g);
         return;
     }
     hipLaunchKernelGGL((scan_emit_kernel<MODE>), grid, block, pad, stream, p, g);

@@ -79,7 +79,7 @@ struct ScanParams {
     uint64_t* out_first;         // super-k-mer: position of the first k-mer of the group
     uint8_t* out_mmpos;          // super-k-mer: minimizer offset inside the first k-mer
     uint8_t* out_size;           // super-k-mer: number of k-mers of the group (last k-mer - first k-mer + 1, super_kmer_view.hpp:133)
-    uint64_t* out_records;       // super-k-mer: the group's bases packed into 16 bytes (bl_superkmer.hip's record), two words per group
+    uint64_t* out_records;       // super-k-mer: the group's bases packed into 16 bytes (bl_superkmer.hip's record), two words per group (records128: 32 bytes, four words)
     uint64_t capacity;           // records the output arrays can hold
     // two-pass ordered compaction (no inter-workgroup communication inside a kernel):
     //   pass 1 (scan_count_kernel) writes per tile its record counts and its compacted u16 lists,
@@ -109,6 +109,9 @@ struct ScanParams {
     int32_t nwin;                     // windows per read = read_len - unit - w + 2
     uint32_t lpr_inv;                 // ceil(65536 / lpr): lane / lpr == (lane * lpr_inv) >> 16 for lane < 64
     int64_t n_reads;                  // reads in the range
+    // super-k-mer scans that hand out 32-BYTE records (bl_scan_super_kmer_records128: k up to 64, groups of up to 122 bases): out_records
+    // takes four words per group (pack_group128) and position-tiled tiles stage WCHUNK chunks per wave (staged_chunks has the bound)
+    int32_t records128;
 };
 
 // widths the read-tiled kernels are built for (bl_kernels.hip: launch_count_frl; the emulation harness instantiates the same set)
@@ -524,6 +527,32 @@ BL_DEV void pack_group(const uint32_t* codes, int last_chunk, int pos, int nb, u
     else if (nb < 64) lo &= ~0ULL << (64 - 2 * (nb - 32));
     x = hi;
     y = (lo & ~0x3ffULL) | ((uint64_t)(mm_pos & 31u) << 5) | (uint64_t)((size - 1) & 31);
+}
+
+// The `nb` <= 122 bases from tile-relative base `pos` on, as the 32-byte super-k-mer record of bl_superkmer128_core.hpp: w[0..2] = bases
+// 0..95 (first base in the two top bits of w[0]), w[3] = bases 96..121 in bits 63..12 | mm_pos << 6 | size - 1; base bits beyond nb are 0.
+// A base offset of 0..15 and 122 bases span nine chunks: read from the staged codes by address (chunks beyond `last_chunk` are not looked
+// at: their bases would be masked anyway), then a funnel shift per output chunk — c[] and o[] are indexed by constants only.
+BL_DEV void pack_group128(const uint32_t* codes, int last_chunk, int pos, int nb, uint32_t mm_pos, int size, uint64_t* w)
+{
+    const int ch = pos >> 4, off = pos & 15;
+    uint32_t c[9];
+    BL_UNROLL
+    for (int i = 0; i < 9; ++i) c[i] = codes[ch + i <= last_chunk ? ch + i : last_chunk];
+    const int sh = (32 - 2 * off) & 31;  // off = 0: no shift at all (a funnel shift by 32 is not one the instruction has)
+    uint32_t o[8];
+    BL_UNROLL
+    for (int i = 0; i < 8; ++i) {
+        const uint32_t f = funnel_shr(c[i], c[i + 1], sh);
+        o[i] = off ? f : c[i];
+    }
+    BL_UNROLL
+    for (int i = 0; i < 4; ++i) {
+        const int rem = nb - 32 * i;  // bases of the group that word i holds (32 or more: all of it)
+        const uint64_t v = ((uint64_t)o[2 * i] << 32) | o[2 * i + 1];
+        w[i] = rem <= 0 ? 0ULL : (rem < 32 ? v & (~0ULL << (64 - 2 * rem)) : v);
+    }
+    w[3] = (w[3] & ~0xfffULL) | ((uint64_t)(mm_pos & 63u) << 6) | (uint64_t)((size - 1) & 63);
 }
 
 // ------------------------------------------------------------------------------------------------

@@ -154,8 +154,17 @@ BL_DEV int staged_chunks(const ScanParams& p)
     const int wchunks = p.stride / NWAVE / 16;
     int per_wave = (wchunks - 1) + (S + p.unit + p.w) / 16 + 1;
     per_wave = per_wave < 66 ? 66 : (per_wave > WCHUNK ? WCHUNK : per_wave);
+    // 32-byte records (p.records128): pass 2 packs a group's bases from these chunks, and a wide group outruns what the windows need.
+    // With ws = stride / NWAVE = 16 * wchunks owned positions per wave, a group's first k-mer is window j <= ws (the owner of position
+    // i decides window i + 1) and its last base is j + (size - 1) + (k - 1) <= ws + (w - 1) + (unit + w - 2) = ws + 2k - m - 1
+    // <= ws + 121 (the call's limit 2k - m <= 122), which lies in chunk wchunks + 7; pack_group128 reads the nine chunks from j >> 4
+    // <= wchunks on, so wchunks + 8.  wchunks = 64 - ceil(w / 16) <= 63: WCHUNK = 72 chunks per wave hold both for every shape, and
+    // 3 * 63 + 72 = 261 <= NCHUNK_POS, what a tile's slot and two staging rounds of TPB threads take.  Chunks beyond the batch's end
+    // come out of the same guarded stage_chunk as zeros.  Every other scan keeps the count above.
+    if (p.records128) per_wave = WCHUNK;
     return wave_chunk0(p, NWAVE - 1) + per_wave;  // <= NCHUNK
 }
+static_assert(3 * 63 + WCHUNK <= NCHUNK_POS && NCHUNK_POS <= 2 * TPB && NCHUNK_POS <= NCHUNK, "a tile's staged chunks fit its slot, two staging rounds and the LDS array");
 
 template <int MODE, int W>
 BL_DEV void phase_load(const ScanParams& p, TileShared<MODE, W>& sh, int tid, int64_t q0)
@@ -1337,6 +1346,27 @@ BL_DEV void emit_record(const ScanParams& p, const uint32_t* codes, int last_chu
     stream_store(&p.out_records[2 * g + 1], y);
 }
 
+// The 32-byte record (k up to 64, a group of up to 2k - m <= 122 bases) from the same staged codes.  Position-tiled tiles stage WCHUNK
+// chunks per wave for these calls (staged_chunks derives why that holds every group that begins in the tile); read-tiled tiles stage
+// their reads whole, a group never leaves its read, and the chunks pack_group128 would read behind the last staged one are clamped to
+// it (they hold bases behind the group, which are masked).  Written once, 32-byte aligned: two 16-byte non-temporal stores.
+BL_DEV void emit_record128(const ScanParams& p, const uint32_t* codes, int last_chunk, int64_t q0, const Record& rec, int size, uint64_t g)
+{
+    uint64_t w[4];
+    pack_group128(codes, last_chunk, (int)((int64_t)rec.first - q0), size + p.unit + p.w - 2, rec.mmpos, size, w);
+#if defined(__HIP_DEVICE_COMPILE__) && !defined(BL_CPU_EMU)
+    typedef uint64_t u64x2 __attribute__((ext_vector_type(2)));
+    u64x2* dst = reinterpret_cast<u64x2*>(p.out_records + 4 * g);
+    u64x2 lo, hi;
+    lo.x = w[0]; lo.y = w[1];
+    hi.x = w[2]; hi.y = w[3];
+    __builtin_nontemporal_store(lo, dst);
+    __builtin_nontemporal_store(hi, dst + 1);
+#else
+    for (int i = 0; i < 4; ++i) p.out_records[4 * g + i] = w[i];
+#endif
+}
+
 // whole phase for one thread: records tid, tid + TPB, ...
 template <int MODE>
 BL_DEV void phase_emit(const ScanParams& p, const TileLists& L, uint32_t tile, int tid, int64_t q0, uint32_t n_s, uint32_t n_e, uint64_t base_s, uint64_t base_e,
@@ -1351,7 +1381,8 @@ BL_DEV void phase_emit(const ScanParams& p, const TileLists& L, uint32_t tile, i
         if (MODE == MODE_SUPERKMER && (p.out_size || p.out_records) && base_s + r < p.capacity) {
             const int size = (int)(end_position(p, L, tile, q0, r + d, n_e) - (int64_t)rec.first + 1);
             if (p.out_size) p.out_size[base_s + r] = (uint8_t)size;
-            if (p.out_records) emit_record(p, L.codes, staged_chunks(p) - 1, q0, rec, size, base_s + r);
+            if (p.out_records && p.records128) emit_record128(p, L.codes, staged_chunks(p) - 1, q0, rec, size, base_s + r);
+            else if (p.out_records) emit_record(p, L.codes, staged_chunks(p) - 1, q0, rec, size, base_s + r);
         }
     }
 }

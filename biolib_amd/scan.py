@@ -725,9 +725,9 @@ class Batch:
 
         return self._with_capacity(int(span * 2.4 / (k - m + 2)) + 4096, run)
 
-    def super_kmer_records128(self, k, m, seed=0, canonical=False, first=0, n=0):
-        """(records int64[n, 4], minimizer hashes int64[n]) on the device: the 32-byte super-k-mer records of the range for k up to 64, by
-        bl_scan_super_kmers + bl_pack_super_kmers128"""
+    def super_kmer_records128(self, k, m, seed=0, canonical=False, first=0, n=0, fused=True):
+        """(records int64[n, 4], minimizer hashes int64[n]) on the device: the 32-byte super-k-mer records of the range for k up to 64,
+        straight from the scan (bl_scan_super_kmer_records128; fused=False: bl_scan_super_kmers + bl_pack_super_kmers128, the same records)"""
         import torch
 
         span = self._span(first, n)
@@ -735,6 +735,17 @@ class Batch:
 
         def run(cap):
             hs = c.empty_u64(cap)
+            if fused:
+                r = Result()
+                recs = torch.empty((max(cap, 1), 4), dtype=torch.int64, device=c.torch_device)  # (the allocator aligns to 512 bytes)
+                c._hold(r, _flags(canonical, False, True))
+                try:
+                    check(self._lib.bl_scan_super_kmer_records128(c._h, self._h, int(first), int(n), int(k), int(m), int(seed), _flags(canonical, False, True),
+                                                                  C.c_void_p(recs.data_ptr()), C.c_void_p(hs.data_ptr()), int(cap), C.byref(r)))
+                finally:
+                    self._last_count = r.count
+                cnt = int(r.count)
+                return recs[:cnt], hs[:cnt]
             fp, sz, mp = c.empty_u64(cap), c.empty_u8(cap), c.empty_u8(cap)
             r = Result()
             try:

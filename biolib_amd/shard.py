@@ -253,7 +253,7 @@ def count_kmers_via_super_kmers(ctx, batch, k, m, seed=0, canonical=True, group=
     group (single GPU); force_exchange runs the all-to-all even at world size 1 (tests).  Returns (distinct k-mers,
     multiplicities) owned by this rank, as device tensors, in no particular order.
 
-    k > 32 or 2k - m > 59 (what a 16-byte record holds) takes the wide calls: 32-byte records (bl_pack_super_kmers128,
+    k > 32 or 2k - m > 59 (what a 16-byte record holds) takes the wide calls: 32-byte records (bl_scan_super_kmer_records128,
     bl_partition_records128) and 128-bit k-mers (bl_count_super_kmers128); the distinct k-mers then come as an (n, 2) tensor of
     (low, high) words.  Smaller shapes keep the 16-byte path and a 1-D tensor."""
     import torch.distributed as dist

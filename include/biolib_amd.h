@@ -430,7 +430,7 @@ int bl_expand_super_kmers(bl_ctx* ctx, const uint64_t* d_records, uint64_t n_gro
 
 /* ---- the same pipeline for k up to 64: 32-byte records, 128-bit k-mers -----------------------------------------------------------
  * bl_scan_super_kmers has no upper limit on k (1 <= m <= 32, w = k - m + 1 <= 64): it is the reference's own super-k-mer driver
- * instantiation, KmerType = __uint128_t, MinimizerType = uint64_t.  These four calls take its groups on.  The 64-bit calls above keep
+ * instantiation, KmerType = __uint128_t, MinimizerType = uint64_t.  These calls take its groups on.  The 64-bit calls above keep
  * their limits and their 16-byte record.
  * THE RECORD: four 64-bit words per group, d_records[4g .. 4g+3], the array 32-byte aligned (BL_ERR_INVALID otherwise):
  *   words 0, 1, 2   bases 0..31, 32..63, 64..95 of the group's size + k - 1 bases
@@ -443,6 +443,12 @@ int bl_expand_super_kmers(bl_ctx* ctx, const uint64_t* d_records, uint64_t n_gro
  *   origin is honoured; a position in front of the origin (by any distance) or at or behind origin + n_bases packs an EMPTY record (all
  *   base bits zero) with bits 11..0 as given; a group that runs over the end packs code 0 behind the end, bits 11..0 as given; no byte
  *   outside the batch's n_bases is read.  d_mm_pos is required.
+ * bl_scan_super_kmer_records128: bl_scan_super_kmers + bl_pack_super_kmers128 in one scan — the record is built inside the scan's record
+ *   pass from the 2-bit codes the tile holds; no per-group arrays are written and read back and the bases are not read a second time.
+ *   The output is exactly what the two calls give for the same arguments: d_records[4r .. 4r+3] as above, d_hashes[r] the minimizer's
+ *   hash (8-byte key).  The batch's origin does not change the records.  Either output may be NULL (both NULL: count only); nothing is
+ *   written at or beyond `capacity`; the result always carries the full count, with BL_ERR_CAPACITY when it exceeds `capacity`;
+ *   `result` is bl_scan_super_kmers'; ranges concatenate as for every scan; no byte outside the batch's n_bases is read.
  * bl_partition_records128: bl_partition_records for 32-byte records (d_out 32-byte aligned too).
  * bl_expand_super_kmers128: records -> their k-mers, group after group, two words per k-mer (low, high; d_kmers 16-byte aligned).
  *   BL_ERR_CAPACITY with *n_kmers = need when d_kmers is too small; nothing is written then.  Only 1 <= k <= 64 is checked (no m).
@@ -453,8 +459,9 @@ int bl_expand_super_kmers(bl_ctx* ctx, const uint64_t* d_records, uint64_t n_gro
  *   taken, k = 64 without the canonical flag (the all-T 64-mer is all ones) included.  Oversized buckets take expand + 128-bit sort +
  *   run-length; bl_ctx_set_option("count128_tables", 0) sends every bucket that way (same result).  Terminates on any record bits.
  *   (bl_sort_u128 / bl_count_sorted_u128 put the distinct k-mers in order.)
- * NOT provided for k > 32: the fused in-scan record variant (bl_scan_super_kmer_records; records come from scan + pack here),
- *   biolib_amd::read_pool for wide views, and any multi-GPU measurement of this path. */
+ * NOT provided for k > 32: biolib_amd::read_pool for wide views, and any multi-GPU measurement of this path. */
+int bl_scan_super_kmer_records128(bl_ctx* ctx, const bl_batch* batch, uint64_t first, uint64_t n, uint32_t k, uint32_t m, uint64_t seed, uint32_t flags,
+                                  uint64_t* d_records /* 4 per group, 32-byte aligned */, uint64_t* d_hashes, uint64_t capacity, bl_result* result);
 int bl_pack_super_kmers128(bl_ctx* ctx, const bl_batch* batch, const uint64_t* d_first_pos, const uint8_t* d_sizes, const uint8_t* d_mm_pos, uint64_t n_groups,
                            uint32_t k, uint32_t m, uint64_t* d_records /* 4 per group */);
 int bl_partition_records128(bl_ctx* ctx, const uint64_t* d_hashes, const uint64_t* d_records, uint64_t n, uint32_t parts, uint64_t* d_out, uint64_t* counts);
