@@ -108,6 +108,7 @@ struct bl_ctx {
     int jaccard128_path = 0;     // bl_ctx_set_option("jaccard128_path"): 0 = bl_jaccard_sorted_u128 chooses, 1 = merge kernel, 2 = search kernel
     bool count128_tables = true; // bl_ctx_set_option("count128_tables"): 0 = bl_count_super_kmers128 counts every bucket by sort + run-length
     bool ktiming = false;
+    bl::LaunchLog last_kernels{};  // names of the kernels the last window scan launched (bl_ctx_last_scan_kernels)
     std::vector<hipEvent_t> ev_pool;                       // free events
     std::vector<std::pair<hipEvent_t, hipEvent_t>> ev_open;  // recorded, not yet read
     double kernel_ms = 0.0;
@@ -1065,6 +1066,7 @@ static int scan_windows(int mode, bl_ctx* c, const bl_batch* b, uint64_t first, 
                         uint32_t flags, bl::ScanParams& p, uint64_t capacity, bl_result* result)
 {
     if (!c || !b || b->ctx != c) return fail(BL_ERR_INVALID, "ctx/batch is NULL or the batch belongs to another context");
+    c->last_kernels.n = 0;
     if (unit < 1 || unit > bl::MAX_UNIT) return fail(BL_ERR_INVALID, "hashed unit length must be in [1, 32]");
     if (w < 1 || w > bl::MAX_W) return fail(BL_ERR_INVALID, "window must be in [1, 64]");
     uint64_t end;
@@ -1128,7 +1130,7 @@ static int scan_windows(int mode, bl_ctx* c, const bl_batch* b, uint64_t first, 
     }
     rc = kernel_event(c, true);
     if (rc != BL_OK) return rc;
-    hipError_t e = bl::launch_scan_count(mode, p, all, c->stream);  // pass 1: the dominant kernel (timed alone)
+    hipError_t e = bl::launch_scan_count(mode, p, all, c->stream, &c->last_kernels);  // pass 1: the dominant kernel (timed alone)
     if (e != hipSuccess) return fail(BL_ERR_HIP, std::string("scan_count_kernel: ") + hipGetErrorString(e));
     if (staggered) {
         BL_HIP(hipEventRecord(c->cur->ev_count_done, c->stream));
@@ -1143,7 +1145,7 @@ static int scan_windows(int mode, bl_ctx* c, const bl_batch* b, uint64_t first, 
     // (super-k-mer scans: 8 K since their pass 1 is compiled for five waves per SIMD and holds 5 x 28.7 KB of a CU's 160: 393 / 396 / 394 / 390 / 382 Gbp/s
     // at 4 / 8 / 12 / 16 / 24 K on one box, C4 at 24 Gbp)
     const uint32_t emit_lds_default = mode == bl::MODE_SUPERKMER ? 8192u : 28672u;
-    e = bl::launch_scan_emit(mode, p, all, c->stream, staggered ? (c->emit_lds_per_wg ? c->emit_lds_per_wg : emit_lds_default) : 0);  // pass 2
+    e = bl::launch_scan_emit(mode, p, all, c->stream, staggered ? (c->emit_lds_per_wg ? c->emit_lds_per_wg : emit_lds_default) : 0, &c->last_kernels);  // pass 2
     if (e != hipSuccess) return fail(BL_ERR_HIP, std::string("scan_emit_kernel: ") + hipGetErrorString(e));
     return BL_OK;
 }
@@ -1238,6 +1240,37 @@ int bl_scan_syncmers(bl_ctx* c, const bl_batch* b, uint64_t first, uint64_t n, u
     int rc = scan_windows(bl::MODE_SYNCMER, c, b, first, n, s, k - s + 1, seed, flags, p, d_positions ? capacity : 0, result);
     if (rc != BL_OK || p.n_tiles == 0) return rc;
     return end_scan(c, 1u << 0, result, d_positions != nullptr, capacity, flags);
+}
+
+// names, one per line, into a caller's buffer: *needed = bytes with the terminating NUL; BL_ERR_CAPACITY (nothing written) when they do not fit
+static int copy_names(const char* const* names, int n, char* buf, uint64_t capacity, uint64_t* needed)
+{
+    uint64_t bytes = 1;
+    for (int i = 0; i < n; ++i) bytes += std::strlen(names[i]) + 1;
+    if (needed) *needed = bytes;
+    if (!buf || capacity < bytes) return fail(BL_ERR_CAPACITY, "the buffer is too small for the kernel names");
+    char* o = buf;
+    for (int i = 0; i < n; ++i) {
+        const size_t len = std::strlen(names[i]);
+        std::memcpy(o, names[i], len);
+        o[len] = '\n';
+        o += len + 1;
+    }
+    *o = 0;
+    return BL_OK;
+}
+
+int bl_ctx_last_scan_kernels(bl_ctx* c, char* buf, uint64_t capacity, uint64_t* needed)
+{
+    if (!c) return fail(BL_ERR_INVALID, "ctx is NULL");
+    return copy_names(c->last_kernels.names, c->last_kernels.n, buf, capacity, needed);
+}
+
+int bl_scan_kernel_names(char* buf, uint64_t capacity, uint64_t* needed)
+{
+    int n = 0;
+    const char* const* names = bl::scan_kernel_names(&n);
+    return copy_names(names, n, buf, capacity, needed);
 }
 
 // ---------------------------------------------------------------------------------------- helpers

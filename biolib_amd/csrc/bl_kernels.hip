@@ -699,15 +699,72 @@ __global__ void start_bits_offsets_kernel(uint32_t* bits, const uint64_t* offset
 // ------------------------------------------------------------------------------------------------
 // launchers
 
-static hipError_t launch_count_frl(int mode, const ScanParams& p, GroupRange g, hipStream_t stream)
+// Every launch of a scan kernel goes through BL_LAUNCH: it records the kernel's name in the caller's LaunchLog (bl_launch.hpp; a pointer
+// store on the host) and launches.  The names are listed once more in SCAN_KERNEL_NAMES below, which bl_scan_kernel_names hands out:
+// tests/test_gpu_kernel_census.py launches every one of them and fails on a name that is recorded but not listed, or listed and never seen.
+// MM / SK / SY: minimizer, super-k-mer, syncmer scans.  `frl`: the read-tiled pass 1; `approx`: windows decided on murmur64_top, followed
+// by the `redo` kernel of the same shape.
+#define BL_LAUNCH(NAME, KERNEL, GRID, BLOCK, LDS, ...)                          \
+    do {                                                                       \
+        if (log) log->add(NAME);                                               \
+        hipLaunchKernelGGL(KERNEL, GRID, BLOCK, LDS, stream, __VA_ARGS__);     \
+    } while (0)
+// the name of a kernel all three modes instantiate
+#define BL_MODE_NAME(HEAD, TAIL) (MODE == MODE_MINIMIZER ? HEAD "MM" TAIL : MODE == MODE_SUPERKMER ? HEAD "SK" TAIL : HEAD "SY" TAIL)
+
+#define BL_W_ALL(X)                                                                                                                      \
+    X(2) X(3) X(4) X(5) X(6) X(7) X(8) X(9) X(10) X(11) X(12) X(13) X(14) X(15) X(16) X(17) X(18) X(19) X(20) X(21) X(22) X(23) X(24)    \
+    X(25) X(26) X(27) X(28) X(29) X(30) X(31) X(32)
+
+static const char* const SCAN_KERNEL_NAMES[] = {
+    // launch_count_frl
+    "frl<MM,W=11,NS=15,U=31,L=150,approx>", "frl_redo<MM,W=11,NS=15,U=31,L=150>", "frl<MM,W=11,NS=15,U=31,L=150>",
+    "frl<MM,W=11,NS=14,U=31,approx>", "frl_redo<MM,W=11,NS=14,U=31>", "frl<MM,W=11,NS=14,U=31>",
+    "frl<MM,W=11,NS=15,U=31,approx>", "frl_redo<MM,W=11,NS=15,U=31>", "frl<MM,W=11,NS=15,U=31>",
+    "frl<MM,W=11,NS=16,U=31,approx>", "frl_redo<MM,W=11,NS=16,U=31>", "frl<MM,W=11,NS=16,U=31>",
+    "frl<MM,W=5>", "frl<MM,W=10>", "frl<MM,W=11>", "frl<MM,W=19>", "frl<SK,W=17>",
+    // launch_count_mode: the specialised shapes
+#ifndef BL_NO_POSAX
+    "count<MM,W=11,U=31,C=1,approx>", "redo<MM,W=11,U=31,C=1>",
+#endif
+    "count<MM,W=11,U=31,C=1>",
+#ifdef BL_SKAX
+    "count<SK,W=17,U=15,C=1,approx>", "redo<SK,W=17,U=15,C=1>",
+#endif
+    "count<SK,W=17,U=15,C=1>",
+    "count<SY,W=21,U=11,C=1,closed>", "redo<SY,W=21,U=11,C=1>",
+#ifndef BL_NO_SY2
+    "count<SY,W=21,U=11,C=1,deferred>",  // (exact_windows included: its exact form is the redo kernel)
+#else
+    "count<SY,W=21,U=11,C=1>",
+#endif
+    "count<SY,closed,W<=17>", "count<SY,closed,W<=32>",
+    // ... a kernel per window width
+#define BL_W(WV) "count<MM,W=" #WV ">", "count<SK,W=" #WV ">",
+    BL_W_ALL(BL_W)
+#undef BL_W
+    // ... the rest.  (count<SY,W>32> is launched by no call the C ABI accepts, k <= 32 bounds a syncmer scan's width: not listed)
+    "count<MM,W=1>", "count<SK,W=1>", "count<SY,W=1>", "count<SY,W=11>", "count<SY,W=17>", "count<SY,W=21>",
+    "count<SY,W<=16>", "count<SY,W<=32>", "count<MM,W>32>", "count<SK,W>32>",
+    // launch_emit_mode
+    "emit<MM>", "emit<SK>", "emit<SY>", "emit<MM,C3>", "emit<SK,wide>",
+};
+
+const char* const* scan_kernel_names(int* count)
+{
+    *count = (int)(sizeof(SCAN_KERNEL_NAMES) / sizeof(SCAN_KERNEL_NAMES[0]));
+    return SCAN_KERNEL_NAMES;
+}
+
+static hipError_t launch_count_frl(int mode, const ScanParams& p, GroupRange g, hipStream_t stream, LaunchLog* log)
 {
     const dim3 grid(g.count), block(TPB);
     if (mode == MODE_MINIMIZER && p.w == 11 && p.unit == 31 && p.canonical && p.read_len == 150 && p.ns == 15 && p.rpw == 8) {
         if (p.redo_list && g.first == 0 && !p.exact_windows) {  // BASELINE C3 (exact_windows, bl_ctx_set_exact_windows: windows decided on the hashes themselves)
-            hipLaunchKernelGGL((scan_count_frl_kernel<MODE_MINIMIZER, 11, 15, 31, 150, 1, true>), grid, block, 0, stream, p, g);
-            hipLaunchKernelGGL((scan_redo_frl_kernel<MODE_MINIMIZER, 11, 15, 31, 150, 1>), dim3(g.count < 512u ? g.count : 512u), block, 0, stream, p);
+            BL_LAUNCH("frl<MM,W=11,NS=15,U=31,L=150,approx>", (scan_count_frl_kernel<MODE_MINIMIZER, 11, 15, 31, 150, 1, true>), grid, block, 0, p, g);
+            BL_LAUNCH("frl_redo<MM,W=11,NS=15,U=31,L=150>", (scan_redo_frl_kernel<MODE_MINIMIZER, 11, 15, 31, 150, 1>), dim3(g.count < 512u ? g.count : 512u), block, 0, p);
         } else {
-            hipLaunchKernelGGL((scan_count_frl_kernel<MODE_MINIMIZER, 11, 15, 31, 150, 1>), grid, block, 0, stream, p, g);
+            BL_LAUNCH("frl<MM,W=11,NS=15,U=31,L=150>", (scan_count_frl_kernel<MODE_MINIMIZER, 11, 15, 31, 150, 1>), grid, block, 0, p, g);
         }
         return hipGetLastError();
     }
@@ -716,12 +773,12 @@ static hipError_t launch_count_frl(int mode, const ScanParams& p, GroupRange g, 
     if (mode == MODE_MINIMIZER && p.w == 11 && p.unit == 31 && p.canonical && p.ns >= 14 && p.ns <= 16) {
         const bool approx = p.redo_list && g.first == 0 && !p.exact_windows;
         const dim3 redo_grid(g.count < 512u ? g.count : 512u);
-#define BL_FRL_SHAPE(NSV)                                                                                                                \
-    if (approx) {                                                                                                                        \
-        hipLaunchKernelGGL((scan_count_frl_kernel<MODE_MINIMIZER, 11, NSV, 31, 0, 1, true>), grid, block, 0, stream, p, g);               \
-        hipLaunchKernelGGL((scan_redo_frl_kernel<MODE_MINIMIZER, 11, NSV, 31, 0, 1>), redo_grid, block, 0, stream, p);                    \
-    } else {                                                                                                                             \
-        hipLaunchKernelGGL((scan_count_frl_kernel<MODE_MINIMIZER, 11, NSV, 31, 0, 1>), grid, block, 0, stream, p, g);                     \
+#define BL_FRL_SHAPE(NSV)                                                                                                                                    \
+    if (approx) {                                                                                                                                            \
+        BL_LAUNCH("frl<MM,W=11,NS=" #NSV ",U=31,approx>", (scan_count_frl_kernel<MODE_MINIMIZER, 11, NSV, 31, 0, 1, true>), grid, block, 0, p, g);            \
+        BL_LAUNCH("frl_redo<MM,W=11,NS=" #NSV ",U=31>", (scan_redo_frl_kernel<MODE_MINIMIZER, 11, NSV, 31, 0, 1>), redo_grid, block, 0, p);                   \
+    } else {                                                                                                                                                 \
+        BL_LAUNCH("frl<MM,W=11,NS=" #NSV ",U=31>", (scan_count_frl_kernel<MODE_MINIMIZER, 11, NSV, 31, 0, 1>), grid, block, 0, p, g);                         \
     }
         if (p.ns == 14) { BL_FRL_SHAPE(14) } else if (p.ns == 15) { BL_FRL_SHAPE(15) } else { BL_FRL_SHAPE(16) }
 #undef BL_FRL_SHAPE
@@ -730,14 +787,14 @@ static hipError_t launch_count_frl(int mode, const ScanParams& p, GroupRange g, 
     if (p.ns != S) return hipErrorInvalidValue;  // the general kernels give every lane S unit starts
     if (mode == MODE_MINIMIZER) {
         switch (p.w) {
-            case 5: hipLaunchKernelGGL((scan_count_frl_kernel<MODE_MINIMIZER, 5, S, 0, 0, -1>), grid, block, 0, stream, p, g); break;
-            case 10: hipLaunchKernelGGL((scan_count_frl_kernel<MODE_MINIMIZER, 10, S, 0, 0, -1>), grid, block, 0, stream, p, g); break;
-            case 11: hipLaunchKernelGGL((scan_count_frl_kernel<MODE_MINIMIZER, 11, S, 0, 0, -1>), grid, block, 0, stream, p, g); break;
-            case 19: hipLaunchKernelGGL((scan_count_frl_kernel<MODE_MINIMIZER, 19, S, 0, 0, -1>), grid, block, 0, stream, p, g); break;
+            case 5: BL_LAUNCH("frl<MM,W=5>", (scan_count_frl_kernel<MODE_MINIMIZER, 5, S, 0, 0, -1>), grid, block, 0, p, g); break;
+            case 10: BL_LAUNCH("frl<MM,W=10>", (scan_count_frl_kernel<MODE_MINIMIZER, 10, S, 0, 0, -1>), grid, block, 0, p, g); break;
+            case 11: BL_LAUNCH("frl<MM,W=11>", (scan_count_frl_kernel<MODE_MINIMIZER, 11, S, 0, 0, -1>), grid, block, 0, p, g); break;
+            case 19: BL_LAUNCH("frl<MM,W=19>", (scan_count_frl_kernel<MODE_MINIMIZER, 19, S, 0, 0, -1>), grid, block, 0, p, g); break;
             default: return hipErrorInvalidValue;
         }
     } else if (mode == MODE_SUPERKMER && p.w == 17) {
-        hipLaunchKernelGGL((scan_count_frl_kernel<MODE_SUPERKMER, 17, S, 0, 0, -1>), grid, block, 0, stream, p, g);
+        BL_LAUNCH("frl<SK,W=17>", (scan_count_frl_kernel<MODE_SUPERKMER, 17, S, 0, 0, -1>), grid, block, 0, p, g);
     } else {
         return hipErrorInvalidValue;
     }
@@ -745,54 +802,54 @@ static hipError_t launch_count_frl(int mode, const ScanParams& p, GroupRange g, 
 }
 
 template <int MODE>
-static hipError_t launch_count_mode(const ScanParams& p, GroupRange g, hipStream_t stream)
+static hipError_t launch_count_mode(const ScanParams& p, GroupRange g, hipStream_t stream, LaunchLog* log)
 {
     const dim3 grid(g.count), block(TPB);
     // the BASELINE.json configurations, fully specialised
     if (MODE == MODE_MINIMIZER && p.w == 11 && p.unit == 31 && p.canonical) {
 #ifndef BL_NO_POSAX
         if (p.redo_list && g.first == 0 && !p.exact_windows) {  // long reads, contigs, reads of mixed lengths: windows decided on murmur64_top here too
-            hipLaunchKernelGGL((scan_count_kernel<MODE_MINIMIZER, 11, 31, 1, 2>), grid, block, 0, stream, p, g);
-            hipLaunchKernelGGL((scan_redo_kernel<MODE_MINIMIZER, 11, 31, 1>), dim3(g.count < 512u ? g.count : 512u), block, 0, stream, p);
+            BL_LAUNCH("count<MM,W=11,U=31,C=1,approx>", (scan_count_kernel<MODE_MINIMIZER, 11, 31, 1, 2>), grid, block, 0, p, g);
+            BL_LAUNCH("redo<MM,W=11,U=31,C=1>", (scan_redo_kernel<MODE_MINIMIZER, 11, 31, 1>), dim3(g.count < 512u ? g.count : 512u), block, 0, p);
             return hipGetLastError();
         }
 #endif
-        hipLaunchKernelGGL((scan_count_kernel<MODE, 11, 31, 1>), grid, block, 0, stream, p, g);
+        BL_LAUNCH("count<MM,W=11,U=31,C=1>", (scan_count_kernel<MODE, 11, 31, 1>), grid, block, 0, p, g);
         return hipGetLastError();
     }
     if (MODE == MODE_SUPERKMER && p.w == 17 && p.unit == 15 && p.canonical) {
 #ifdef BL_SKAX  // measured twice (rounds 3 and 4; this form: 112 registers, no spills, 17 % fewer static instructions): 398.5 / 399.9 against 399.0 / 401.6
                // Gbp/s for the exact kernel, A/B on one box — the super-k-mer scan is not limited by the hash's four instructions.  Not built by default.
         if (p.redo_list && g.first == 0 && !p.exact_windows) {  // BASELINE C4: windows decided on murmur64_top, the listed tiles again on the hashes
-            hipLaunchKernelGGL((scan_count_kernel<MODE_SUPERKMER, 17, 15, 1, 2>), grid, block, 0, stream, p, g);
-            hipLaunchKernelGGL((scan_redo_kernel<MODE_SUPERKMER, 17, 15, 1>), dim3(g.count < 512u ? g.count : 512u), block, 0, stream, p);
+            BL_LAUNCH("count<SK,W=17,U=15,C=1,approx>", (scan_count_kernel<MODE_SUPERKMER, 17, 15, 1, 2>), grid, block, 0, p, g);
+            BL_LAUNCH("redo<SK,W=17,U=15,C=1>", (scan_redo_kernel<MODE_SUPERKMER, 17, 15, 1>), dim3(g.count < 512u ? g.count : 512u), block, 0, p);
             return hipGetLastError();
         }
 #endif
-        hipLaunchKernelGGL((scan_count_kernel<MODE, 17, 15, 1>), grid, block, 0, stream, p, g);
+        BL_LAUNCH("count<SK,W=17,U=15,C=1>", (scan_count_kernel<MODE, 17, 15, 1>), grid, block, 0, p, g);
         return hipGetLastError();
     }
     if (MODE == MODE_SYNCMER && p.w == 21 && p.unit == 11 && p.canonical) {
         const bool closed = (p.soff == 0 && p.eoff == 20) || (p.soff == 20 && p.eoff == 0);
         const unsigned redo_grid = g.count < 512u ? g.count : 512u;
         if (closed && !p.exact_windows && p.redo_list && g.first == 0) {  // BASELINE C5 (exact_windows: the argmin form)
-            hipLaunchKernelGGL((scan_count_kernel<MODE_SYNCMER, 21, 11, 1, 1>), grid, block, 0, stream, p, g);
-            hipLaunchKernelGGL((scan_redo_kernel<MODE_SYNCMER, 21, 11, 1>), dim3(redo_grid), block, 0, stream, p);
+            BL_LAUNCH("count<SY,W=21,U=11,C=1,closed>", (scan_count_kernel<MODE_SYNCMER, 21, 11, 1, 1>), grid, block, 0, p, g);
+            BL_LAUNCH("redo<SY,W=21,U=11,C=1>", (scan_redo_kernel<MODE_SYNCMER, 21, 11, 1>), dim3(redo_grid), block, 0, p);
 #ifndef BL_NO_SY2
         } else if (p.redo_list && g.first == 0) {  // any other pair of offsets: argmins, the exact form in the redo kernel
-            hipLaunchKernelGGL((scan_count_kernel<MODE_SYNCMER, 21, 11, 1, 2>), grid, block, 0, stream, p, g);
-            hipLaunchKernelGGL((scan_redo_kernel<MODE_SYNCMER, 21, 11, 1>), dim3(redo_grid), block, 0, stream, p);
+            BL_LAUNCH("count<SY,W=21,U=11,C=1,deferred>", (scan_count_kernel<MODE_SYNCMER, 21, 11, 1, 2>), grid, block, 0, p, g);
+            BL_LAUNCH("redo<SY,W=21,U=11,C=1>", (scan_redo_kernel<MODE_SYNCMER, 21, 11, 1>), dim3(redo_grid), block, 0, p);
 #endif
         } else {
-            hipLaunchKernelGGL((scan_count_kernel<MODE, 21, 11, 1>), grid, block, 0, stream, p, g);
+            BL_LAUNCH("count<SY,W=21,U=11,C=1>", (scan_count_kernel<MODE, 21, 11, 1>), grid, block, 0, p, g);
         }
         return hipGetLastError();
     }
     if (MODE == MODE_SYNCMER && p.w <= 32 && !p.exact_windows && ((p.soff == 0 && p.eoff == p.w - 1) || (p.soff == p.w - 1 && p.eoff == 0))) {
         // closed syncmers of any (k, s): sliding minima over the hashes' high dwords, w by run time; a k-mer whose comparison meets equal
         // dwords is decided on the 64-bit hashes inside the kernel (short s-mers repeat within a window: no second kernel, no listed tiles)
-        if (p.w <= 17) hipLaunchKernelGGL((scan_count_kernel<MODE_SYNCMER, -8, 0, -1, 1>), grid, block, 0, stream, p, g);
-        else hipLaunchKernelGGL((scan_count_kernel<MODE_SYNCMER, -16, 0, -1, 1>), grid, block, 0, stream, p, g);
+        if (p.w <= 17) BL_LAUNCH("count<SY,closed,W<=17>", (scan_count_kernel<MODE_SYNCMER, -8, 0, -1, 1>), grid, block, 0, p, g);
+        else BL_LAUNCH("count<SY,closed,W<=32>", (scan_count_kernel<MODE_SYNCMER, -16, 0, -1, 1>), grid, block, 0, p, g);
         return hipGetLastError();
     }
     if (MODE != MODE_SYNCMER && p.w >= 2 && p.w <= 32) {
@@ -801,40 +858,38 @@ static hipError_t launch_count_mode(const ScanParams& p, GroupRange g, hipStream
         // time, ran these widths at 220-340 Gbp/s where a width of its own gives 340-420; 2 x 27 more kernels cost the build half a minute.)
         constexpr int MM = MODE == MODE_SYNCMER ? MODE_MINIMIZER : MODE;  // never instantiated for syncmers
         switch (p.w) {
-#define BL_W(WV) case WV: hipLaunchKernelGGL((scan_count_kernel<MM, WV, 0, -1>), grid, block, 0, stream, p, g); return hipGetLastError();
-            BL_W(2) BL_W(3) BL_W(4) BL_W(5) BL_W(6) BL_W(7) BL_W(8) BL_W(9) BL_W(10) BL_W(11) BL_W(12) BL_W(13) BL_W(14) BL_W(15) BL_W(16)
-            BL_W(17) BL_W(18) BL_W(19) BL_W(20) BL_W(21) BL_W(22) BL_W(23) BL_W(24) BL_W(25) BL_W(26) BL_W(27) BL_W(28) BL_W(29) BL_W(30)
-            BL_W(31) BL_W(32)
+#define BL_W(WV) case WV: BL_LAUNCH(BL_MODE_NAME("count<", ",W=" #WV ">"), (scan_count_kernel<MM, WV, 0, -1>), grid, block, 0, p, g); return hipGetLastError();
+            BL_W_ALL(BL_W)
 #undef BL_W
         }
     }
     switch (p.w) {
-        case 1: hipLaunchKernelGGL((scan_count_kernel<MODE, 1, 0, -1>), grid, block, 0, stream, p, g); break;
-        case 11: hipLaunchKernelGGL((scan_count_kernel<MODE, 11, 0, -1>), grid, block, 0, stream, p, g); break;
-        case 17: hipLaunchKernelGGL((scan_count_kernel<MODE, 17, 0, -1>), grid, block, 0, stream, p, g); break;
-        case 21: hipLaunchKernelGGL((scan_count_kernel<MODE, 21, 0, -1>), grid, block, 0, stream, p, g); break;
+        case 1: BL_LAUNCH(BL_MODE_NAME("count<", ",W=1>"), (scan_count_kernel<MODE, 1, 0, -1>), grid, block, 0, p, g); break;
+        case 11: BL_LAUNCH(BL_MODE_NAME("count<", ",W=11>"), (scan_count_kernel<MODE, 11, 0, -1>), grid, block, 0, p, g); break;
+        case 17: BL_LAUNCH(BL_MODE_NAME("count<", ",W=17>"), (scan_count_kernel<MODE, 17, 0, -1>), grid, block, 0, p, g); break;
+        case 21: BL_LAUNCH(BL_MODE_NAME("count<", ",W=21>"), (scan_count_kernel<MODE, 21, 0, -1>), grid, block, 0, p, g); break;
         default:
             // runtime window size: sparse-table argmin in registers, one kernel per size group (minimizer and super-k-mer scans come
             // here with widths beyond 32 only)
             if constexpr (MODE == MODE_SYNCMER) {
-                if (p.w <= 16) { hipLaunchKernelGGL((scan_count_kernel<MODE, -8, 0, -1>), grid, block, 0, stream, p, g); break; }
-                if (p.w <= 32) { hipLaunchKernelGGL((scan_count_kernel<MODE, -16, 0, -1>), grid, block, 0, stream, p, g); break; }
+                if (p.w <= 16) { BL_LAUNCH("count<SY,W<=16>", (scan_count_kernel<MODE, -8, 0, -1>), grid, block, 0, p, g); break; }
+                if (p.w <= 32) { BL_LAUNCH("count<SY,W<=32>", (scan_count_kernel<MODE, -16, 0, -1>), grid, block, 0, p, g); break; }
             }
-            hipLaunchKernelGGL((scan_count_kernel<MODE, -32, 0, -1>), grid, block, 0, stream, p, g);
+            BL_LAUNCH(BL_MODE_NAME("count<", ",W>32>"), (scan_count_kernel<MODE, -32, 0, -1>), grid, block, 0, p, g);
             break;
     }
     return hipGetLastError();
 }
 
 // pass 1 over the tiles of group g
-hipError_t launch_scan_count(int mode, const ScanParams& p, GroupRange g, hipStream_t stream)
+hipError_t launch_scan_count(int mode, const ScanParams& p, GroupRange g, hipStream_t stream, LaunchLog* log)
 {
     if (g.count == 0) return hipSuccess;
-    if (p.frl) return launch_count_frl(mode, p, g, stream);
+    if (p.frl) return launch_count_frl(mode, p, g, stream, log);
     switch (mode) {
-        case MODE_MINIMIZER: return launch_count_mode<MODE_MINIMIZER>(p, g, stream);
-        case MODE_SUPERKMER: return launch_count_mode<MODE_SUPERKMER>(p, g, stream);
-        case MODE_SYNCMER: return launch_count_mode<MODE_SYNCMER>(p, g, stream);
+        case MODE_MINIMIZER: return launch_count_mode<MODE_MINIMIZER>(p, g, stream, log);
+        case MODE_SUPERKMER: return launch_count_mode<MODE_SUPERKMER>(p, g, stream, log);
+        case MODE_SYNCMER: return launch_count_mode<MODE_SYNCMER>(p, g, stream, log);
     }
     return hipErrorInvalidValue;
 }
@@ -844,7 +899,7 @@ hipError_t launch_scan_count(int mode, const ScanParams& p, GroupRange g, hipStr
 // purpose is to cap how many emit workgroups a CU holds when the pass runs beside the next scan's pass 1 (two-lane
 // contexts): uncapped, the memory-bound emit waves crowd the ALU-bound pass out of the SIMDs (349 vs 364 Gbp/s measured).
 template <int MODE>
-static void launch_emit_mode(const ScanParams& p, GroupRange g, hipStream_t stream, uint32_t lds_per_wg)
+static void launch_emit_mode(const ScanParams& p, GroupRange g, hipStream_t stream, uint32_t lds_per_wg, LaunchLog* log)
 {
     constexpr int K = emit_tiles<MODE>();
     const uint32_t have = (uint32_t)(((K > 1 ? 2 : 1) * NCHUNK + (K > 1 ? 6 * TPB : 0)) * sizeof(uint32_t));  // the kernel's static LDS: code buffers, digest words
@@ -852,27 +907,30 @@ static void launch_emit_mode(const ScanParams& p, GroupRange g, hipStream_t stre
     const dim3 grid((g.count + K - 1) / K), block(TPB);
     if (MODE == MODE_MINIMIZER && p.frl && p.unit == 31 && p.canonical) {  // BASELINE C3: code buffers of two strands (emit_c3)
         const uint32_t have_c3 = (uint32_t)(((K > 1 ? 2 : 1) * 2 * C3_RC + (K > 1 ? 6 * TPB : 0)) * sizeof(uint32_t));
-        hipLaunchKernelGGL((scan_emit_kernel<MODE_MINIMIZER, 31, 1, 1>), grid, block, lds_per_wg > have_c3 ? lds_per_wg - have_c3 : 0, stream, p, g);
+        BL_LAUNCH("emit<MM,C3>", (scan_emit_kernel<MODE_MINIMIZER, 31, 1, 1>), grid, block, lds_per_wg > have_c3 ? lds_per_wg - have_c3 : 0, p, g);
         return;
     }
     if (MODE == MODE_SUPERKMER && p.records128) {  // 32-byte records: the instantiation that packs them (same LDS footprint)
-        hipLaunchKernelGGL((scan_emit_kernel<MODE_SUPERKMER, 0, -1, -1, true>), grid, block, pad, stream, p, g);
+        BL_LAUNCH("emit<SK,wide>", (scan_emit_kernel<MODE_SUPERKMER, 0, -1, -1, true>), grid, block, pad, p, g);
         return;
     }
-    hipLaunchKernelGGL((scan_emit_kernel<MODE>), grid, block, pad, stream, p, g);
+    BL_LAUNCH(BL_MODE_NAME("emit<", ">"), (scan_emit_kernel<MODE>), grid, block, pad, p, g);
 }
 
-hipError_t launch_scan_emit(int mode, const ScanParams& p, GroupRange g, hipStream_t stream, uint32_t lds_per_wg)
+hipError_t launch_scan_emit(int mode, const ScanParams& p, GroupRange g, hipStream_t stream, uint32_t lds_per_wg, LaunchLog* log)
 {
     if (g.count == 0) return hipSuccess;
     switch (mode) {
-        case MODE_MINIMIZER: launch_emit_mode<MODE_MINIMIZER>(p, g, stream, lds_per_wg); break;
-        case MODE_SUPERKMER: launch_emit_mode<MODE_SUPERKMER>(p, g, stream, lds_per_wg); break;
-        case MODE_SYNCMER: launch_emit_mode<MODE_SYNCMER>(p, g, stream, lds_per_wg); break;
+        case MODE_MINIMIZER: launch_emit_mode<MODE_MINIMIZER>(p, g, stream, lds_per_wg, log); break;
+        case MODE_SUPERKMER: launch_emit_mode<MODE_SUPERKMER>(p, g, stream, lds_per_wg, log); break;
+        case MODE_SYNCMER: launch_emit_mode<MODE_SYNCMER>(p, g, stream, lds_per_wg, log); break;
         default: return hipErrorInvalidValue;
     }
     return hipGetLastError();
 }
+#undef BL_LAUNCH
+#undef BL_MODE_NAME
+#undef BL_W_ALL
 
 // prefix scan of the tile counts of group g (first tile must be a multiple of SCAN_BLK)
 hipError_t launch_tile_scan(const ScanParams& p, GroupRange g, unsigned long long* block_tot, unsigned long long* carry, hipStream_t stream)

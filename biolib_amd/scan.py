@@ -27,6 +27,14 @@ def _flags(canonical=False, drop_last=False, sync=False):
     return (FLAG_CANONICAL if canonical else 0) | (FLAG_DROP_LAST if drop_last else 0) | (FLAG_SYNC if sync else 0)
 
 
+def _names(call):
+    need = C.c_uint64()
+    call(None, 0, C.byref(need))  # BL_ERR_CAPACITY: how many bytes
+    buf = C.create_string_buffer(int(need.value))
+    check(call(buf, len(buf), C.byref(need)))
+    return buf.value.decode().split()
+
+
 class Context:
     """One context per (process, GPU): owns the stream-ordered workspace of the scans."""
 
@@ -100,6 +108,15 @@ class Context:
         """tuning / test switches by name (bl_ctx_set_option: "exact_windows", "lanes", "position_tiled", "emit_lds_bytes", "count128_tables",
         "jaccard128_path")"""
         check(self._lib.bl_ctx_set_option(self._h, name.encode(), int(value)))
+
+    def last_scan_kernels(self):
+        """names of the kernels the most recent window scan on this context launched, in launch order (bl_ctx_last_scan_kernels)"""
+        return _names(lambda buf, cap, need: self._lib.bl_ctx_last_scan_kernels(self._h, buf, cap, need))
+
+    @staticmethod
+    def scan_kernel_names():
+        """every name a scan's launch can record (bl_scan_kernel_names)"""
+        return _names(capi.lib().bl_scan_kernel_names)
 
     def kernel_timing(self, enable=True):
         check(self._lib.bl_ctx_kernel_timing(self._h, 1 if enable else 0))

@@ -274,6 +274,16 @@ int bl_ctx_set_exact_windows(bl_ctx* ctx, int on);
  *                                 merge kernel when the larger set is less than 4 times the smaller one
  * The library reads no environment variable on the scan path. */
 int bl_ctx_set_option(bl_ctx* ctx, const char* name, int64_t value);
+/* Which kernels ran.  The window scans (bl_scan_minimizers, bl_scan_hash_sample, bl_scan_super_kmers, bl_scan_super_kmer_records,
+ * bl_scan_super_kmer_records128, bl_scan_syncmers) choose among about a hundred kernel instantiations by mode, window width, unit length,
+ * strand flag, batch layout, syncmer offsets and the exact_windows switch.  Every launch records a short stable name, e.g.
+ * "count<MM,W=7>" (pass 1), "frl<MM,W=11,NS=15,U=31,L=150,approx>" followed by "frl_redo<MM,W=11,NS=15,U=31,L=150>" (read-tiled pass 1
+ * on the approximate dword and its second run), "emit<SK,wide>" (pass 2).  bl_ctx_last_scan_kernels copies the names of the most recent
+ * window scan issued on the context, in launch order, one per line, NUL-terminated, into buf; bl_scan_kernel_names copies every name a
+ * launch can record.  *needed (nullable) takes the bytes required; BL_ERR_CAPACITY, with nothing written, when capacity is smaller.
+ * For tests and diagnostics: a call that scanned nothing (an empty range) recorded nothing.  Neither call synchronises. */
+int bl_ctx_last_scan_kernels(bl_ctx* ctx, char* buf, uint64_t capacity, uint64_t* needed);
+int bl_scan_kernel_names(char* buf, uint64_t capacity, uint64_t* needed);
 
 /* Elapsed GPU time of the most recent scan call on this context, from HIP events recorded on the
  * context's stream around its kernels (milliseconds).  Synchronises. */
