@@ -2,14 +2,25 @@
 // a batch THERE (newline index -> line classification -> prefix sums -> gather of the sequence lines), so ingest
 // runs at PCIe speed instead of at the speed of one host thread (the host reader of
 // bl_ingest.cpp stays the general path and the semantic reference, itself pinned against the reference's kseq).
-// Accepted on this path: FASTQ with exactly four lines per record, FASTA with any line wrapping; LF or CRLF.
-// Anything irregular is refused with BL_ERR_INVALID (never silently mis-parsed): use bl_reader_* for those files.
+// Accepted on this path: FASTQ with exactly four lines per record (at most three blank lines behind the last one), FASTA with
+// any line wrapping; LF or CRLF; the last line may lack its terminator.
+// Anything irregular is refused with BL_ERR_INVALID (never silently mis-parsed): use bl_reader_* for those files.  Refused are
+//   * a text that starts with neither '>' nor '@'; FASTQ whose lines are not '@' header, sequence, '+' separator, quality of
+//     the sequence's length, four by four
+//   * a FASTQ sequence line, or a FASTA line that is no header, that opens with a byte which ends the sequence in the
+//     reference reader: '>', '@' or '+' in FASTQ, '@' or '+' in FASTA
+//   * a line that is a lone '\r' where the reference reader counts it as a base (it drops a trailing '\r' only from more than
+//     one gathered byte): a FASTQ sequence or quality line, and a FASTA line with nothing of its record gathered in front of it
+//     (after the scans: its dst equals its record's offset).  The same FASTA line behind bases vanishes there as it does here.
+// The per-thread bodies of the kernels and the host's decisions on the text's ends are in bl_parse_core.hpp, which also compiles
+// for the host: tests/emu/emu_parse.cpp runs them under the sanitizers on the texts of tests/parse_cases.py.
 #include <hip/hip_runtime.h>
 #include <cstring>
 #include <rocprim/device/device_scan.hpp>
 #include <string>
 
 #include "../../include/biolib_amd.h"
+#include "bl_parse_core.hpp"
 
 extern int bl_set_error(int code, const char* msg);
 extern hipStream_t bl_ctx_stream(bl_ctx* ctx);
@@ -22,33 +33,12 @@ extern int bl_batch_adopt_device(bl_ctx* ctx, void* d_bases, uint64_t n_bases, u
 
 namespace {
 
-constexpr int PB = 256;          // threads per block
-constexpr int BYTES_PER_BLOCK = PB * 16;
-
-__device__ __forceinline__ uint32_t newline_mask16(const uint8_t* text, uint64_t n, uint64_t at)
-{
-    uint32_t m = 0;
-    if (at + 16 <= n) {
-        const uint4 v = *reinterpret_cast<const uint4*>(text + at);  // text is 16-byte aligned, at is a multiple of 16
-        const uint32_t d[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const uint32_t x = d[i] ^ 0x0a0a0a0au;                                        // zero byte <=> '\n'
-            const uint32_t z = ~(((x & 0x7f7f7f7fu) + 0x7f7f7f7fu) | x) & 0x80808080u;  // bit 7 of every zero byte
-            m |= (((z >> 7) * 0x00204081u >> 21) & 0xfu) << (4 * i);
-        }
-    } else {
-        for (int b = 0; b < 16 && at + b < n; ++b)
-            if (text[at + b] == '\n') m |= 1u << b;
-    }
-    return m;
-}
+using namespace bl_parse;
 
 __global__ __launch_bounds__(PB) void count_newlines_kernel(const uint8_t* text, uint64_t n, unsigned long long* block_count)
 {
     __shared__ unsigned int wsum[PB / 64];
-    const uint64_t at = ((uint64_t)blockIdx.x * PB + threadIdx.x) * 16;
-    unsigned int c = at < n ? __builtin_popcount(newline_mask16(text, n, at)) : 0;
+    unsigned int c = __builtin_popcount(chunk_mask(text, n, chunk_at(blockIdx.x, threadIdx.x)));
     for (int d = 32; d >= 1; d >>= 1) c += __shfl_xor(c, d, 64);
     if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = c;
     __syncthreads();
@@ -61,34 +51,16 @@ __global__ __launch_bounds__(PB) void newline_positions_kernel(const uint8_t* te
 {
     __shared__ unsigned int wsum[PB / 64];
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    const uint64_t at = ((uint64_t)blockIdx.x * PB + threadIdx.x) * 16;
-    uint32_t m = at < n ? newline_mask16(text, n, at) : 0;
+    const uint64_t at = chunk_at(blockIdx.x, threadIdx.x);
+    const uint32_t m = chunk_mask(text, n, at);
     const unsigned int c = __builtin_popcount(m);
     unsigned int incl = c;
-    for (int d = 1; d < 64; d <<= 1) {
-        const unsigned int o = __shfl_up(incl, d, 64);
-        if (lane >= d) incl += o;
-    }
+    for (int d = 1; d < 64; d <<= 1) incl = scan_step(incl, __shfl_up(incl, d, 64), lane, d);
     if (lane == 63) wsum[wv] = incl;
     __syncthreads();
     unsigned int before = 0;
     for (int i = 0; i < wv; ++i) before += wsum[i];
-    unsigned long long idx = block_base[blockIdx.x] + before + incl - c;
-    while (m) {
-        const int b = __builtin_ctz(m);
-        m &= m - 1;
-        line_end[idx++] = at + b;
-    }
-}
-
-enum { KIND_OTHER = 0, KIND_SEQ = 1, KIND_HEADER = 2 };
-enum { ERR_FASTQ_HEADER = 1, ERR_FASTQ_PLUS = 2, ERR_FASTQ_QUAL = 4, ERR_FASTA_SEQLINE = 8 };
-
-__device__ __forceinline__ void line_span(const uint8_t* text, const unsigned long long* line_end, uint64_t li, uint64_t& start, uint64_t& end)
-{
-    start = li ? line_end[li - 1] + 1 : 0;
-    end = line_end[li];
-    if (end > start && text[end - 1] == '\r') --end;
+    write_newline_positions(m, at, block_base[blockIdx.x] + before + incl - c, line_end);
 }
 
 // one thread per line: kind, sequence length (0 unless a sequence line), header flag; format checks
@@ -97,31 +69,9 @@ __global__ void classify_lines_kernel(const uint8_t* text, const unsigned long l
 {
     const uint64_t li = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (li >= n_lines) return;
-    uint64_t s, e;
-    line_span(text, line_end, li, s, e);
-    const uint8_t first = e > s ? text[s] : 0;
-    unsigned long long len = 0, h = 0;
-    if (fastq) {
-        const int f = (int)(li & 3);
-        if (f == 0) {
-            h = 1;
-            if (first != '@') atomicOr(err, (unsigned)ERR_FASTQ_HEADER);
-        } else if (f == 1) {
-            len = e - s;
-        } else if (f == 2) {
-            if (first != '+') atomicOr(err, (unsigned)ERR_FASTQ_PLUS);
-        } else {
-            uint64_t s2, e2;
-            line_span(text, line_end, li - 2, s2, e2);
-            if (e - s != e2 - s2) atomicOr(err, (unsigned)ERR_FASTQ_QUAL);
-        }
-    } else {
-        if (first == '>') h = 1;
-        else {
-            len = e - s;  // masked later for lines in front of the first header
-            if (first == '@' || first == '+') atomicOr(err, (unsigned)ERR_FASTA_SEQLINE);  // would end the record in the reference reader
-        }
-    }
+    unsigned long long len, h;
+    const unsigned int e = classify_line(text, line_end, li, fastq, len, h);
+    if (e) atomicOr(err, e);
     seq_len[li] = len;
     hdr[li] = h;
 }
@@ -130,54 +80,37 @@ __global__ void classify_lines_kernel(const uint8_t* text, const unsigned long l
 __global__ void mask_leading_lines_kernel(const unsigned long long* rec_incl, unsigned long long* seq_len, uint64_t n_lines)
 {
     const uint64_t li = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (li < n_lines && rec_incl[li] == 0) seq_len[li] = 0;
+    if (li < n_lines) mask_leading_line(rec_incl, seq_len, li);
 }
 
 // offsets[r] = first base of record r (r = rec_incl - 1 at its header line); offsets[n_records] = total
 __global__ void record_offsets_kernel(const unsigned long long* hdr, const unsigned long long* rec_incl, const unsigned long long* dst,
                                       uint64_t n_lines, unsigned long long* offsets, uint64_t n_records, uint64_t total)
 {
+    record_offset_line(hdr, rec_incl, dst, n_lines, offsets, n_records, total, (uint64_t)blockIdx.x * blockDim.x + threadIdx.x);
+}
+
+// FASTA texts that hold a lone-'\r' line (rare: launched only then, after record_offsets_kernel): refuse where it opens a record
+__global__ void lone_cr_lines_kernel(const uint8_t* text, const unsigned long long* line_end, const unsigned long long* hdr,
+                                     const unsigned long long* rec_incl, const unsigned long long* dst, const unsigned long long* offsets,
+                                     uint64_t n_lines, unsigned int* err)
+{
     const uint64_t li = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (li == 0) offsets[n_records] = total;
-    if (li < n_lines && hdr[li]) offsets[rec_incl[li] - 1] = dst[li];
+    if (li < n_lines && lone_cr_opens_record(text, line_end, hdr, rec_incl, dst, offsets, li)) atomicOr(err, (unsigned)ERR_LONE_CR);
 }
 
 // do all records hold exactly `len` bases?  (flag |= 1 where one does not)
 __global__ void uniform_length_kernel(const unsigned long long* offsets, uint64_t n_records, uint64_t len, unsigned int* flag)
 {
-    const uint64_t r = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (r <= n_records && offsets[r] != r * len) atomicOr(flag, 1u);
+    if (breaks_uniform_length(offsets, n_records, len, (uint64_t)blockIdx.x * blockDim.x + threadIdx.x)) atomicOr(flag, 1u);
 }
 
-// one thread per 16 output bytes: find the sequence line that holds output byte x (last line with dst <= x), gather
+// one thread per 16 output bytes
 __global__ void gather_bases_kernel(const uint8_t* text, const unsigned long long* line_end, const unsigned long long* dst,
                                     const unsigned long long* seq_len, uint64_t n_lines, uint8_t* bases, uint64_t total)
 {
     const uint64_t x0 = ((uint64_t)blockIdx.x * blockDim.x + threadIdx.x) * 16;
-    if (x0 >= total) return;
-    uint64_t lo = 0, hi = n_lines;  // first line with dst > x0
-    while (lo < hi) {
-        const uint64_t mid = (lo + hi) >> 1;
-        if (dst[mid] <= x0) lo = mid + 1;
-        else hi = mid;
-    }
-    uint64_t li = lo - 1;  // dst[0] = 0 <= x0, so lo >= 1; this line has seq_len > 0
-    uint32_t w[4] = {0, 0, 0, 0};
-    uint64_t x = x0;
-    int filled = 0;
-    while (filled < 16 && x < total) {
-        while (li < n_lines && seq_len[li] == 0) ++li;  // header / quality lines in between
-        if (li >= n_lines) break;                        // cannot happen while x < total; keeps a logic error from running away
-        const uint64_t ls = li ? line_end[li - 1] + 1 : 0;
-        const uint64_t in_line = x - dst[li];
-        uint64_t take = seq_len[li] - in_line;
-        if (take > (uint64_t)(16 - filled)) take = 16 - filled;
-        const uint8_t* src = text + ls + in_line;
-        for (uint64_t b = 0; b < take; ++b, ++filled) w[filled >> 2] |= (uint32_t)src[b] << (8 * (filled & 3));
-        x += take;
-        if (in_line + take == seq_len[li]) ++li;
-    }
-    *reinterpret_cast<uint4*>(bases + x0) = make_uint4(w[0], w[1], w[2], w[3]);  // bases has >= 16 bytes of slack
+    if (x0 < total) gather16(text, line_end, dst, seq_len, n_lines, bases, total, x0);
 }
 
 #define P_HIP(call)                                                                                                       \
@@ -222,9 +155,7 @@ int bl_parse_device_text(bl_ctx* ctx, const uint8_t* d_text_in, uint64_t n_bytes
     // the format is decided by the first character
     const bool fastq = first_byte == '@';
     if (!fastq && first_byte != '>') return bl_set_error(BL_ERR_INVALID, "text starts with neither '>' nor '@': use bl_reader_* for irregular files");
-    // a '>' that is the very last byte of the file and alone on its line opens no record in the reference reader (kseq meets
-    // end of file while looking for the name and reports end of input): drop it
-    if (!fastq && last(0) == '>' && (n_bytes == 1 || last(1) == '\n')) {
+    if (drops_trailing_marker(fastq, ends, ends_n, n_bytes)) {
         --n_bytes;
         --ends_n;
         if (n_bytes == 0) return bl_batch_upload(ctx, "", 0, nullptr, 0, out);
@@ -284,19 +215,11 @@ int bl_parse_device_text(bl_ctx* ctx, const uint8_t* d_text_in, uint64_t n_bytes
     const uint64_t n_lines_raw = n_newlines + (open_last_line ? 1 : 0);
     uint64_t n_lines = n_lines_raw;
     if (fastq && (n_lines & 3)) {  // blank lines after the last record are tolerated, anything else is not 4-line FASTQ
-        uint64_t excess = n_lines & 3, blank = 0, pos = ends_n;  // positions inside `ends`; running out of it means "not blank"
-        while (blank < excess && pos > 0) {  // walk back over empty lines ("\n" or "\r\n")
-            if (open_last_line && blank == 0) break;  // the last line is not empty
-            if (ends[pos - 1] != '\n') break;
-            uint64_t q = pos - 1;
-            if (q > 0 && ends[q - 1] == '\r') --q;
-            if (q == 0 && ends_n < n_bytes) break;     // cannot see the byte in front
-            if (q > 0 && ends[q - 1] != '\n') break;  // the line ending here has content
-            ++blank;
-            pos = q;
-        }
-        if (blank < excess) return fail_free(BL_ERR_INVALID, "FASTQ text is not made of 4-line records: use bl_reader_*");
+        const uint64_t excess = n_lines & 3;
+        if (!trailing_lines_blank(ends, ends_n, n_bytes, open_last_line, excess))
+            return fail_free(BL_ERR_INVALID, "FASTQ text is not made of 4-line records: use bl_reader_*");
         n_lines -= excess;
+        if (n_lines == 0) return bl_batch_upload(ctx, "", 0, nullptr, 0, out);  // a span of the blank lines behind a file's last record
     }
 
     {
@@ -339,13 +262,8 @@ int bl_parse_device_text(bl_ctx* ctx, const uint8_t* d_text_in, uint64_t n_bytes
     P_HIP(hipMemcpyAsync(&n_records, d_rec + (n_lines - 1), sizeof(n_records), hipMemcpyDeviceToHost, s));
     P_HIP(hipMemcpyAsync(&err, d_err, sizeof(err), hipMemcpyDeviceToHost, s));
     P_HIP(hipStreamSynchronize(s));
-    if (err) {
-        const char* msg = (err & ERR_FASTQ_HEADER) ? "FASTQ record does not start with '@' every 4 lines: use bl_reader_*"
-                          : (err & ERR_FASTQ_PLUS) ? "FASTQ separator line does not start with '+': use bl_reader_*"
-                          : (err & ERR_FASTQ_QUAL) ? "FASTQ quality length differs from the sequence length"
-                                                   : "FASTA sequence line starts with '@' or '+': use bl_reader_*";
-        return fail_free(BL_ERR_INVALID, msg);
-    }
+    if (err & ERR_MASK) return fail_free(BL_ERR_INVALID, refusal_message(err));
+    const bool lone_cr_seen = (err & NOTE_FASTA_LONE_CR) != 0;  // FASTA only: refused where such a line opens its record
 
     d_bases = static_cast<uint8_t*>(bl_ctx_pool_alloc(ctx, total + 64));
     d_offsets = static_cast<unsigned long long*>(bl_ctx_pool_alloc(ctx, (n_records + 1) * sizeof(unsigned long long)));
@@ -358,15 +276,20 @@ int bl_parse_device_text(bl_ctx* ctx, const uint8_t* d_text_in, uint64_t n_bytes
     }
     hipLaunchKernelGGL(record_offsets_kernel, dim3(lb), dim3(256), 0, s, d_hdr, d_rec, d_dst, n_lines, d_offsets, (uint64_t)n_records, (uint64_t)total);
     // reads of one length (the usual short-read file) make a fixed-length batch: the read-tiled scan kernels, no start-bit vector
+    if (lone_cr_seen) {
+        hipLaunchKernelGGL(lone_cr_lines_kernel, dim3(lb), dim3(256), 0, s, d_text, d_line_end, d_hdr, d_rec, d_dst, d_offsets, n_lines, d_err);
+        P_HIP(hipMemcpyAsync(&err, d_err, sizeof(err), hipMemcpyDeviceToHost, s));
+    }
     uint64_t fixed_len = n_records > 1 && total % n_records == 0 ? total / n_records : 0;
     unsigned int ragged = 0;
     if (fixed_len) {
         P_HIP(hipMemsetAsync(d_err + 1, 0, sizeof(unsigned int), s));
-        hipLaunchKernelGGL(uniform_length_kernel, dim3((unsigned)((n_records + 256) / 256)), dim3(256), 0, s, d_offsets, (uint64_t)n_records, fixed_len, d_err + 1);
+        hipLaunchKernelGGL(uniform_length_kernel, dim3(uniform_length_blocks(n_records)), dim3(256), 0, s, d_offsets, (uint64_t)n_records, fixed_len, d_err + 1);
         P_HIP(hipMemcpyAsync(&ragged, d_err + 1, sizeof(ragged), hipMemcpyDeviceToHost, s));
     }
     P_HIP(hipGetLastError());
     P_HIP(hipStreamSynchronize(s));
+    if (err & ERR_MASK) return fail_free(BL_ERR_INVALID, refusal_message(err));
     if (ragged) fixed_len = 0;
     handed_over = true;
     cleanup();

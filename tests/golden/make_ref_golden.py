@@ -2,7 +2,8 @@
 """Record what the REFERENCE returns on the inputs of the tests that compare against it, so that they run where the
 reference is not built: its reader (tests/kseq.h through oracle/ref_kseq_shim.cpp) on the fuzz texts of
 test_ingest.py and on its padded gzip files, and its library (oracle/ref_shim.cpp) on the inputs of
-test_oracle_golden.py::test_live_against_reference_library.  Those tests build their inputs with the same
+test_oracle_golden.py::test_live_against_reference_library, and its reader on the hand-built texts of parse_cases.py
+(test_parse_cases.py, test_gpu_parse_cases.py).  Those tests build their inputs with the same
 functions used here and still compare live where oracle/_ref exists.
 Build container only:  make -C oracle ref && python tests/golden/make_ref_golden.py   -> tests/golden/ref_verdicts.json"""
 import hashlib
@@ -20,6 +21,7 @@ if not O.have_ref():
 
 import test_ingest as TI  # noqa: E402
 import test_oracle_golden as TO  # noqa: E402
+import parse_cases as PC  # noqa: E402
 from ingest_fuzz import cases  # noqa: E402
 
 out = {}
@@ -35,6 +37,8 @@ with tempfile.TemporaryDirectory() as d:
     for key, seed, n in (("reader_fuzz_host", 11, 600), ("reader_fuzz_device", 12, 400)):
         out[key] = [{"text": hashlib.sha256(t).hexdigest()[:16], "ref": read(t)} for t in cases(seed, n)]
     out["reader_padded_gzip"] = {name: read(data) for name, data in TI.padded_gzip_files()[1].items()}
+    # name -> the text's digest and the reader's verdict (past 64 records: the count and a digest of the lengths, parse_cases.compact)
+    out["parser_cases"] = {name: {"text": PC.text_sha(t), "ref": PC.compact(read(t))} for name, t in PC.CASES.items()}
 out["reference_library"] = TO.library_record(O.ref())
 
 with open(os.path.join(HERE, "ref_verdicts.json"), "w") as f:
