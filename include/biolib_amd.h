@@ -176,6 +176,9 @@ int bl_scan_kmers128(bl_ctx* ctx, const bl_batch* batch, uint64_t first, uint64_
  * sequence and one break-free run, leftmost minimum hash; one record each time the minimizer
  * occurrence changes (or a run begins):
  *   d_values[r] unit value, d_positions[r] global start position of the unit, d_hashes[r] its hash.
+ * Range: [first, first+n) takes the windows whose first base lies in it; units behind the range are read as needed, and window
+ * first-1 in front of it.  An occurrence belongs to the range in which its FIRST electing window starts: one that window first-1
+ * elects too is reported by the range before and not again, so consecutive ranges concatenate exactly to the scan of their union.
  * In biolib's naming this is minimizer_view(k = unit + w - 1, m = unit).  1 <= unit <= 32, 1 <= w <= 64. */
 int bl_scan_minimizers(bl_ctx* ctx, const bl_batch* batch, uint64_t first, uint64_t n, uint32_t unit, uint32_t w, uint64_t seed,
                        uint32_t flags, uint64_t* d_values, uint64_t* d_positions, uint64_t* d_hashes, uint64_t capacity,
@@ -229,7 +232,11 @@ int bl_scan_minimizers128(bl_ctx* ctx, const bl_batch* batch, uint64_t first, ui
  * (m-mer, w = k - m + 1):
  *   d_minimizers[r] m-mer value, d_first_pos[r] global position of the group's first k-mer,
  *   d_mm_pos[r] minimizer offset inside that k-mer, d_sizes[r] number of k-mers (<= w),
- *   d_hashes[r] hash of the minimizer.  Any of the arrays may be NULL. */
+ *   d_hashes[r] hash of the minimizer.  Any of the arrays may be NULL.
+ * Range: [first, first+n) takes the k-mers whose first base lies in it.  A group that straddles an end of the range is CLIPPED to the
+ * range: d_first_pos is the first of its k-mers inside the range, d_sizes the number of them inside it, and d_mm_pos the minimizer's
+ * offset in that first k-mer (the minimizer's own position, d_first_pos + d_mm_pos, does not change).  The sizes of consecutive ranges
+ * therefore sum to the k-mers of their union, and their records are the union's with every straddling group in two pieces. */
 int bl_scan_super_kmers(bl_ctx* ctx, const bl_batch* batch, uint64_t first, uint64_t n, uint32_t k, uint32_t m, uint64_t seed,
                         uint32_t flags, uint64_t* d_minimizers, uint64_t* d_first_pos, uint8_t* d_mm_pos, uint8_t* d_sizes,
                         uint64_t* d_hashes, uint64_t capacity, bl_result* result);
@@ -422,7 +429,10 @@ int bl_pack_super_kmers(bl_ctx* ctx, const bl_batch* batch, const uint64_t* d_fi
 /* bl_scan_super_kmer_records: bl_scan_super_kmers + bl_pack_super_kmers in one scan — the groups leave the scan as packed records
  *   (d_records[2r], d_records[2r+1] as above, with mm_pos) beside the hashes of their minimizers (d_hashes[r]: the owner of the
  *   record), built from the 2-bit codes the scan holds anyway: no position / size arrays written and read back, no second pass
- *   over the bases.  Needs 2k - m <= 59.  result as bl_scan_super_kmers. */
+ *   over the bases.  Needs 2k - m <= 59.  result as bl_scan_super_kmers.
+ *   Range: the groups are bl_scan_super_kmers' of the same range, clipped to it in the same way: a record packs the size + k - 1 bases of
+ *   the clipped piece, from the first k-mer inside the range, with mm_pos counted in that k-mer and size the k-mers inside the range.
+ *   Expanding the records of consecutive ranges gives every k-mer of their union exactly once. */
 int bl_scan_super_kmer_records(bl_ctx* ctx, const bl_batch* batch, uint64_t first, uint64_t n, uint32_t k, uint32_t m, uint64_t seed, uint32_t flags,
                                uint64_t* d_records, uint64_t* d_hashes, uint64_t capacity, bl_result* result);
 /* bl_count_super_kmers: the exact multiplicity of every (canonical) k-mer of the packed records WITHOUT a global sort: records are

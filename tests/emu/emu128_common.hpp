@@ -100,3 +100,26 @@ static void stage_all(const bl::Kmer128Params& km, std::vector<uint32_t>& codes,
     const bl::ScanParams lp = bl::kmer128_staging_params(km);
     for (int c = 0; c < (int)codes.size(); ++c) bl::stage_chunk(lp, codes.data(), flags.data(), c, r0);
 }
+
+// A list of ranges in one run: where the program takes <first> <n>, "@FILE 0" names a text file of "first n" pairs, one range per line.
+// `one` is the program's single-range body; before each range's lines a line "range <first> <n>" is printed.  at: index of <first> in argv.
+static int run_ranges(int argc, char** argv, int at, int (*one)(int, char**))
+{
+    if (argc <= at + 1 || argv[at][0] != '@') return one(argc, argv);
+    FILE* f = std::fopen(argv[at] + 1, "r");
+    CHECK(f, "cannot open %s", argv[at] + 1);
+    std::vector<char*> args(argv, argv + argc);
+    unsigned long long first, n;
+    char a[32], b[32];
+    while (std::fscanf(f, "%llu %llu", &first, &n) == 2) {
+        std::snprintf(a, sizeof a, "%llu", first);
+        std::snprintf(b, sizeof b, "%llu", n);
+        args[at] = a;
+        args[at + 1] = b;
+        std::printf("range %llu %llu\n", first, n);
+        const int rc = one(argc, args.data());
+        if (rc != 0) return rc;
+    }
+    std::fclose(f);
+    return 0;
+}

@@ -42,7 +42,7 @@ static Plain plain_scan(const std::vector<uint8_t>& seq, const std::vector<uint6
     return r;
 }
 
-int main(int argc, char** argv)
+static int scan_one(int argc, char** argv)
 {
     CHECK(argc == 6, "usage: emu_kmers128 <batch file> <k> <first> <n> <threshold>");
     const EmuBatch batch(argv[1]);
@@ -59,7 +59,11 @@ int main(int argc, char** argv)
 
     for (int canonical = 0; canonical < 2; ++canonical) {
         for (int drop_last = 0; drop_last < 2; ++drop_last) {
-            const Plain want = plain_scan(seq, offs, k, seed, canonical, drop_last);
+            static Plain plain[4];  // (a list of ranges: the batch and k stay, the plain loop runs once per strand and drop_last)
+            static bool have[4];
+            Plain& want = plain[2 * canonical + drop_last];
+            if (!have[2 * canonical + drop_last]) want = plain_scan(seq, offs, k, seed, canonical, drop_last);
+            have[2 * canonical + drop_last] = true;
             bl::Kmer128Params p{};
             batch.describe(p);
             p.pos_base = (int64_t)origin;
@@ -162,3 +166,6 @@ int main(int argc, char** argv)
     }
     return 0;
 }
+
+// <first> = @FILE: every range of FILE in one run (emu128_common.hpp: run_ranges)
+int main(int argc, char** argv) { return run_ranges(argc, argv, 3, scan_one); }

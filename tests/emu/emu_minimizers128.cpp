@@ -51,7 +51,7 @@ static Plain plain_scan(const std::vector<uint8_t>& seq, const std::vector<uint6
     return r;
 }
 
-int main(int argc, char** argv)
+static int scan_one(int argc, char** argv)
 {
     CHECK(argc == 6, "usage: emu_minimizers128 <batch file> <unit> <w> <first> <n>");
     const EmuBatch batch(argv[1]);
@@ -67,7 +67,11 @@ int main(int argc, char** argv)
 
     for (int canonical = 0; canonical < 2; ++canonical) {
         for (int drop_last = 0; drop_last < 2; ++drop_last) {
-            const Plain want = plain_scan(seq, offs, k, w, seed, canonical, drop_last);
+            static Plain plain[4];  // (a list of ranges: the batch, unit and w stay, the plain evaluation runs once per strand and drop_last)
+            static bool have[4];
+            Plain& want = plain[2 * canonical + drop_last];
+            if (!have[2 * canonical + drop_last]) want = plain_scan(seq, offs, k, w, seed, canonical, drop_last);
+            have[2 * canonical + drop_last] = true;
             auto is_record = [&](int64_t q) {
                 if (q < (int64_t)first || q >= (int64_t)end || want.occ[q] < 0) return false;
                 return q == 0 || want.occ[q - 1] != want.occ[q];
@@ -164,3 +168,6 @@ int main(int argc, char** argv)
     }
     return 0;
 }
+
+// <first> = @FILE: every range of FILE in one run (emu128_common.hpp: run_ranges)
+int main(int argc, char** argv) { return run_ranges(argc, argv, 4, scan_one); }

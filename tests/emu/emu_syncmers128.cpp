@@ -43,7 +43,7 @@ static std::vector<int> plain_offsets(const std::vector<uint8_t>& seq, const std
     return r;
 }
 
-int main(int argc, char** argv)
+static int scan_one(int argc, char** argv)
 {
     CHECK(argc == 8, "usage: emu_syncmers128 <batch file> <k> <s> <first> <n> <start_offset> <end_offset>");
     const EmuBatch batch(argv[1]);
@@ -60,17 +60,23 @@ int main(int argc, char** argv)
 
     // the six-multiply form of the hash is bit-identical to the general one with a zero high word, and to the plain one
     uint64_t x = 0x243f6a8885a308d3ULL;
-    for (int i = 0; i < 20000; ++i) {
+    static bool hash_checked;  // (once per run, not once per range of a list)
+    for (int i = 0; i < 20000 && !hash_checked; ++i) {
         x = x * 6364136223846793005ULL + 1442695040888963407ULL;
         const uint64_t key = i < 70 ? (i < 64 ? 1ULL << i : (i == 64 ? 0 : ~0ULL >> (i - 65))) : x >> (x & 31);
         const uint32_t sd = i % 5 == 0 ? 0u : (i % 5 == 1 ? ~0u : (uint32_t)(x >> 17));
         const uint64_t got = bl::murmur64_u128_lo(key, sd);
         CHECK(got == bl::murmur64_u128(key, 0, sd) && got == plain_hash(key, sd), "murmur64_u128_lo(%llx, %x)", (unsigned long long)key, sd);
     }
+    hash_checked = true;
 
     for (int canonical = 0; canonical < 2; ++canonical) {
         for (int drop_last = 0; drop_last < 2; ++drop_last) {
-            const std::vector<int> want = plain_offsets(seq, offs, k, s, seed, canonical, drop_last);
+            static std::vector<int> plain[4];  // (a list of ranges: the batch, k and s stay, the plain evaluation runs once per strand and drop_last)
+            static bool have[4];
+            std::vector<int>& want = plain[2 * canonical + drop_last];
+            if (!have[2 * canonical + drop_last]) want = plain_offsets(seq, offs, k, s, seed, canonical, drop_last);
+            have[2 * canonical + drop_last] = true;
             bl::Sync128Params p{};
             batch.describe(p.km);
             p.km.pos_base = (int64_t)origin;
@@ -152,3 +158,6 @@ int main(int argc, char** argv)
     }
     return 0;
 }
+
+// <first> = @FILE: every range of FILE in one run (emu128_common.hpp: run_ranges)
+int main(int argc, char** argv) { return run_ranges(argc, argv, 4, scan_one); }

@@ -10,6 +10,7 @@ import numpy as np
 import pytest
 
 import minimizers128_model as M
+from range_cases import batch128
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CXX = "/opt/rocm/lib/llvm/bin/clang++"
@@ -30,20 +31,7 @@ def exe():
     return out
 
 
-def make_batch(k, rng):
-    """two tiles and 1,007 bases; reads of length k-1, k, k+1 (and 1, 150); breaks at the first and the last base of a tile; bytes >= 0x80"""
-    n = 2 * H + 1007
-    seq = rng.choice(np.frombuffer(b"ACGTacgtUu", np.uint8), n)
-    lens = [k + 1, k, max(k - 1, 1), 1, 150]
-    offs = [0]
-    for length in lens:
-        offs.append(offs[-1] + length)
-    offs += [H - 3, H + k, 2 * H - 1, 2 * H + 500, n]
-    offs = np.array(sorted(set(offs)), np.uint64)
-    seq[[H, 2 * H - 1, 2 * H, 3000, 3001, n - 1 - 2 * k]] = ord("N")  # tile 1's first and last base, tile 2's first
-    seq[5000] = 0x80
-    seq[5200] = 0xFF
-    return seq, offs
+make_batch = batch128  # (shared with the range sweep: tests/range_cases.py)
 
 
 @pytest.mark.parametrize("unit,w", SHAPES)
