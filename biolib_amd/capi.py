@@ -25,6 +25,8 @@ SYMBOLS = [
     "bl_scan_super_kmer_records128", "bl_pack_super_kmers128", "bl_partition_records128", "bl_expand_super_kmers128", "bl_count_super_kmers128",
     "bl_sort_u128", "bl_sort_unique_u128", "bl_count_sorted_u128", "bl_jaccard_sorted_u128", "bl_partition_u128",
     "bl_write_run_u128", "bl_write_vector_u128", "bl_file_count_u128", "bl_read_file_u128_host", "bl_read_file_u128", "bl_merge_runs_u128",
+    "bl_table_build_u64", "bl_table_build_u128", "bl_table_destroy", "bl_table_info", "bl_table_arrays", "bl_table_lookup_u64", "bl_table_lookup_u128",
+    "bl_table_histogram", "bl_scan_kmer_counts",
 ]
 
 
@@ -171,6 +173,16 @@ def lib():
     L.bl_merge_runs_u128.argtypes = [vp, C.POINTER(C.c_char_p), u32, vp, u64, C.POINTER(u64)]
     L.bl_hash64_u128.restype = u64
     L.bl_hash64_u128.argtypes = [u64, u64, u64]
+    if "BIOLIB_AMD_LIB" not in os.environ or hasattr(L, "bl_table_build_u64"):  # (an A/B build of an older revision lacks them)
+        L.bl_table_build_u64.argtypes = [vp, vp, vp, u64, u32, C.POINTER(vp)]
+        L.bl_table_build_u128.argtypes = [vp, vp, vp, u64, u32, C.POINTER(vp)]
+        L.bl_table_destroy.argtypes = [vp]
+        L.bl_table_info.argtypes = [vp, C.POINTER(u64), C.POINTER(u32), C.POINTER(u32), C.POINTER(u32)]
+        L.bl_table_arrays.argtypes = [vp, C.POINTER(vp), C.POINTER(vp)]
+        L.bl_table_lookup_u64.argtypes = [vp, vp, vp, u64, vp]
+        L.bl_table_lookup_u128.argtypes = [vp, vp, vp, u64, vp]
+        L.bl_table_histogram.argtypes = [vp, vp, vp, u32]
+        L.bl_scan_kmer_counts.argtypes = [vp, vp, u64, u64, u32, u32, vp, vp, vp, C.POINTER(Result)]
     _lib = L
     return L
 

@@ -15,6 +15,7 @@
 
 #include "../../include/biolib_amd.h"
 #include "bl_launch.hpp"
+#include "bl_lookup_launch.hpp"
 #include "bl_scan128_launch.hpp"
 
 namespace {
@@ -107,6 +108,7 @@ struct bl_ctx {
     bool position_tiled = false; // bl_ctx_set_option("position_tiled"): never the read-tiled layout
     int jaccard128_path = 0;     // bl_ctx_set_option("jaccard128_path"): 0 = bl_jaccard_sorted_u128 chooses, 1 = merge kernel, 2 = search kernel
     bool count128_tables = true; // bl_ctx_set_option("count128_tables"): 0 = bl_count_super_kmers128 counts every bucket by sort + run-length
+    int table_prefix_bits = -1;  // bl_ctx_set_option("table_prefix_bits"): -1 = bl_table_build_* chooses the width of the prefix index, 0 .. 24 forces it
     bool ktiming = false;
     bl::LaunchLog last_kernels{};  // names of the kernels the last window scan launched (bl_ctx_last_scan_kernels)
     std::vector<hipEvent_t> ev_pool;                       // free events
@@ -356,6 +358,7 @@ int bl_batch_adopt_device(bl_ctx* ctx, void* d_bases, uint64_t n_bases, uint64_t
 int bl_ctx_device(bl_ctx* c) { return c->device; }
 int bl_ctx_count128_tables(bl_ctx* c) { return c->count128_tables ? 1 : 0; }  // bl_superkmer128.hip
 int bl_ctx_jaccard128_path(bl_ctx* c) { return c->jaccard128_path; }            // bl_setops128.hip
+int bl_ctx_table_prefix_bits(bl_ctx* c) { return c->table_prefix_bits; }        // bl_lookup.hip
 
 // Device scratch that lives with the context (slot 0..7), grown on demand and never shrunk: the set operations and the
 // bucketed counter need gigabytes of temporary space per call, and hipMalloc / hipFree of that size costs more than their
@@ -586,6 +589,10 @@ int bl_ctx_set_option(bl_ctx* c, const char* name, int64_t value)
     }
     if (n == "jaccard128_path" && value >= 0 && value <= 2) {
         c->jaccard128_path = (int)value;
+        return BL_OK;
+    }
+    if (n == "table_prefix_bits" && value >= -1 && value <= bllk::MAX_PREFIX_BITS) {
+        c->table_prefix_bits = (int)value;
         return BL_OK;
     }
     if (n == "emit_lds_bytes" && value >= 0 && value <= 160 * 1024) {
@@ -1003,6 +1010,34 @@ int bl_scan_kmers128(bl_ctx* c, const bl_batch* b, uint64_t first, uint64_t n, u
     rc = kernel_event(c, false);
     if (rc != BL_OK) return rc;
     return end_scan(c, /*add_mask: count, sum*/ (1u << 0) | (1u << 3), result, false, 0, flags);
+}
+
+// the k-mers of bl_scan_kmers128 looked up in a count table inside the scan: bl_lookup.hip
+int bl_scan_kmer_counts(bl_ctx* c, const bl_batch* b, uint64_t first, uint64_t n, uint32_t k, uint32_t flags, const bl_table* table, uint32_t* d_counts,
+                        uint8_t* d_valid, bl_result* result)
+{
+    if (!table) return fail(BL_ERR_INVALID, "table is NULL");
+    if (c && table->ctx != c) return fail(BL_ERR_INVALID, "the table belongs to another context");
+    if (table->view.key_words == 1 && k > 32) return fail(BL_ERR_INVALID, "a table of one-word keys takes k <= 32");
+    if (k >= 1 && 2 * k > table->view.key_bits)
+        return fail(BL_ERR_INVALID, "2k = " + std::to_string(2 * k) + " exceeds the table's key_bits = " + std::to_string(table->view.key_bits));
+    bllk::ScanCountParams p{};
+    bool empty;
+    int rc = prepare_kmers128(c, b, first, n, k, 0, flags, nullptr, p.km, result, empty);
+    if (rc != BL_OK || empty) return rc;
+    p.table = table->view;
+    p.out_counts = d_counts;
+    p.out_valid = d_valid;
+    rc = begin_scan(c);
+    if (rc != BL_OK) return rc;
+    p.km.shards = c->shards();
+    rc = kernel_event(c, true);
+    if (rc != BL_OK) return rc;
+    hipError_t e = bllk::launch_scan_counts(p, c->stream);
+    if (e != hipSuccess) return fail(BL_ERR_HIP, std::string("scan_counts_kernel: ") + hipGetErrorString(e));
+    rc = kernel_event(c, false);
+    if (rc != BL_OK) return rc;
+    return end_scan(c, /*add_mask: count, found, sum*/ (1u << 0) | (1u << 2) | (1u << 3), result, false, 0, flags);
 }
 
 int bl_scan_hash_sample128(bl_ctx* c, const bl_batch* b, uint64_t first, uint64_t n, uint32_t k, uint64_t seed, uint64_t threshold, uint32_t flags,

@@ -50,6 +50,7 @@ class Context:
         check(self._lib.bl_ctx_create(self.device, C.byref(h)))
         self._h = h
         self._batches = weakref.WeakSet()
+        self._tables = weakref.WeakSet()
         self._pending = []  # Result structs of asynchronous scans: the library fills them at the next sync
         self._borrowed = bool(torch_stream)
         if torch_stream:
@@ -81,6 +82,8 @@ class Context:
         if getattr(self, "_h", None):
             for b in list(self._batches):
                 b.close()
+            for t in list(self._tables):
+                t.close()
             self._lib.bl_ctx_destroy(self._h)
             self._h = None
 
@@ -106,7 +109,7 @@ class Context:
 
     def set_option(self, name, value):
         """tuning / test switches by name (bl_ctx_set_option: "exact_windows", "lanes", "position_tiled", "emit_lds_bytes", "count128_tables",
-        "jaccard128_path")"""
+        "jaccard128_path", "table_prefix_bits")"""
         check(self._lib.bl_ctx_set_option(self._h, name.encode(), int(value)))
 
     def last_scan_kernels(self):
@@ -375,6 +378,31 @@ class Context:
         check(self._lib.bl_count_sorted_u128(self._h, C.c_void_p(keys.data_ptr()), n, C.c_void_p(uniq.data_ptr()), C.c_void_p(mult.data_ptr()), C.byref(runs)))
         return uniq[: runs.value], mult[: runs.value]
 
+    # ---- the count table: what takes the (keys, counts) pairs of the counters on
+    def count_table(self, keys, counts=None, key_bits=None, n=None):
+        """A CountTable of keys[:n] with counts[:n] (None: every entry counts 1).  An int64[n] tensor gives one-word keys, an int64[n, 2]
+        tensor two-word keys (low, high), as sort128 takes them.  Any order, duplicates allowed: equal keys are merged, their counts added
+        (saturating at 2^32 - 1).  key_bits: the number of low bits that can be non-zero (2k for k-mers; default: the full width).
+        The inputs are not modified."""
+        if keys.dim() == 2:
+            n = self._keys128(keys, n)
+            key_words = 2
+        else:
+            if keys.dim() != 1 or keys.element_size() != 8 or not keys.is_contiguous():
+                raise ValueError("keys are a contiguous int64[n] or int64[n, 2] tensor")
+            n = keys.numel() if n is None else int(n)
+            if n > keys.numel():
+                raise ValueError("n exceeds the tensor")
+            self._inputs_ready()
+            key_words = 1
+        if counts is not None and (counts.element_size() != 4 or not counts.is_contiguous() or counts.numel() < n):
+            raise ValueError("counts are a contiguous int32 tensor of at least n entries")
+        key_bits = 64 * key_words if key_bits is None else int(key_bits)
+        h = C.c_void_p()
+        build = self._lib.bl_table_build_u128 if key_words == 2 else self._lib.bl_table_build_u64
+        check(build(self._h, C.c_void_p(keys.data_ptr()), _ptr(counts), n, key_bits, C.byref(h)))
+        return CountTable(self, h)
+
     def read_file_u128(self, path, with_count=False):
         """a run file (raw sorted 16-byte keys) or, with_count, an io::basic_store'd vector<__uint128_t> of biolib -> int64[n, 2] device tensor"""
         n = C.c_uint64()
@@ -493,6 +521,89 @@ def _host_u64(t, n):
     return t[:n].cpu().numpy().view(np.uint64).copy()
 
 
+class _DeviceArray:
+    """carrier of a __cuda_array_interface__ description (torch.as_tensor reads it without copying)"""
+
+
+class CountTable:
+    """Sorted distinct keys with 32-bit counts and a prefix index on the device (bl_table).  Close it (or its context) when done; it
+    must outlive every asynchronous kmer_counts that reads it."""
+
+    def __init__(self, ctx, handle):
+        self.ctx = ctx
+        self._h = handle
+        self._lib = ctx._lib
+        n, kw, kb, pb = C.c_uint64(), C.c_uint32(), C.c_uint32(), C.c_uint32()
+        check(self._lib.bl_table_info(handle, C.byref(n), C.byref(kw), C.byref(kb), C.byref(pb)))
+        self.n_distinct, self.key_words, self.key_bits, self.prefix_bits = int(n.value), int(kw.value), int(kb.value), int(pb.value)
+        ctx._tables.add(self)
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._lib.bl_table_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _arrays(self):
+        k, c = C.c_void_p(), C.c_void_p()
+        check(self._lib.bl_table_arrays(self._h, C.byref(k), C.byref(c)))
+        return k.value, c.value
+
+    def _view(self, ptr, shape, dtype):
+        """a tensor over the table's own memory (no copy): valid while the table is open"""
+        import torch
+
+        if self.n_distinct == 0:
+            return torch.empty(shape, dtype=dtype, device=self.ctx.torch_device)
+        holder = _DeviceArray()
+        holder.__cuda_array_interface__ = dict(shape=tuple(shape), typestr="<i8" if dtype == torch.int64 else "<i4", data=(int(ptr), False), version=2,
+                                               strides=None)
+        return torch.as_tensor(holder, device=self.ctx.torch_device)
+
+    @property
+    def keys(self):
+        """the sorted distinct keys: int64[n_distinct] or int64[n_distinct, 2] (low, high), a view of the table's array"""
+        import torch
+
+        shape = (self.n_distinct, 2) if self.key_words == 2 else (self.n_distinct,)
+        return self._view(self._arrays()[0], shape, torch.int64)
+
+    @property
+    def counts(self):
+        """int32[n_distinct] holding the uint32 counts, a view of the table's array"""
+        import torch
+
+        return self._view(self._arrays()[1], (self.n_distinct,), torch.int32)
+
+    def lookup(self, keys, n=None):
+        """int32 tensor (uint32 bits) of the stored count of every key of keys[:n], 0 for a key that is not in the table"""
+        import torch
+
+        c = self.ctx
+        if self.key_words == 2:
+            n = c._keys128(keys, n)
+        else:
+            if keys.dim() != 1 or keys.element_size() != 8 or not keys.is_contiguous():
+                raise ValueError("one-word keys are a contiguous int64[n] tensor")
+            n = keys.numel() if n is None else int(n)
+            c._inputs_ready()
+        out = torch.empty(max(n, 1), dtype=torch.int32, device=c.torch_device)
+        call = self._lib.bl_table_lookup_u128 if self.key_words == 2 else self._lib.bl_table_lookup_u64
+        check(call(c._h, self._h, C.c_void_p(keys.data_ptr()), n, C.c_void_p(out.data_ptr())))
+        return out[:n]
+
+    def histogram(self, n_bins):
+        """numpy uint64[n_bins]: hist[c] = distinct keys with count c, the last bin those with count >= n_bins - 1"""
+        hist = np.zeros(max(int(n_bins), 1), np.uint64)
+        check(self._lib.bl_table_histogram(self.ctx._h, self._h, hist.ctypes.data_as(C.c_void_p), int(n_bins)))
+        return hist
+
+
 class Batch:
     """Device-resident sequences (bl_batch)."""
 
@@ -561,6 +672,13 @@ class Batch:
         result = result if result is not None else Result()
         self.ctx._hold(result, flags)
         check(self._lib.bl_scan_kmers128(self.ctx._h, self._h, first, n, k, seed, flags, _ptr(values), _ptr(hashes), _ptr(valid), C.byref(result)))
+        return result
+
+    def kmer_counts_raw(self, table, k, flags, first=0, n=0, counts=None, valid=None, result=None):
+        """bl_scan_kmer_counts: `counts` takes one uint32 per position of the range; the table must stay open until the sync"""
+        result = result if result is not None else Result()
+        self.ctx._hold(result, flags)
+        check(self._lib.bl_scan_kmer_counts(self.ctx._h, self._h, first, n, k, flags, table._h, _ptr(counts), _ptr(valid), C.byref(result)))
         return result
 
     def hash_sample128_raw(self, k, seed, threshold, flags, first=0, n=0, values=None, positions=None, hashes=None, capacity=0, result=None):
@@ -633,6 +751,23 @@ class Batch:
         if arrays:
             out.update(values=v[:span].cpu().numpy().view(np.uint64).copy(), hashes=_host_u64(h, span), valid=ok[:span].cpu().numpy().copy())
         return out
+
+    def kmer_counts(self, table, k, canonical=False, drop_last=False, first=0, n=0, valid=False):
+        """The table's count of the k-mer at every position of the range (k <= 64; 0 where no k-mer starts or the key is absent), looked
+        up inside the scan: (counts, result) or, with valid=True, (counts, valid, result).  counts is an int32 device tensor holding the
+        uint32 counts, valid a uint8 device tensor; result carries count, xor_value, aux as kmers128 and found (valid k-mers whose key is
+        in the table) and sum_counts (wrapping sum of the counts looked up)."""
+        import torch
+
+        span = self._span(first, n)
+        c = self.ctx
+        counts = torch.empty(max(span, 1), dtype=torch.int32, device=c.torch_device)
+        ok = c.empty_u8(span) if valid else None
+        r = self.kmer_counts_raw(table, k, _flags(canonical, drop_last, True), first, n, counts, ok)
+        out = r.as_dict()
+        out["found"] = out.pop("xor_hash")
+        out["sum_counts"] = out.pop("xor_pos")
+        return (counts[:span], ok[:span], out) if valid else (counts[:span], out)
 
     def hash_sample128(self, k, seed=0, threshold=2**64 - 1, canonical=False, drop_last=False, first=0, n=0, capacity=None, device=False):
         """k-mers up to k = 64 with hash64_u128(value, seed) < threshold, in position order; values has shape (count, 2) as in kmers128.

@@ -167,7 +167,8 @@ int bl_scan_kmers(bl_ctx* ctx, const bl_batch* batch, uint64_t first, uint64_t n
  * 1 <= k <= 64 (bl_scan_kmers keeps its own limit of 32).
  * What takes these values on: bl_sort_u128 / bl_sort_unique_u128 / bl_count_sorted_u128 / bl_jaccard_sorted_u128 / bl_partition_u128 and
  * the run-file calls bl_write_run_u128 .. bl_merge_runs_u128 (16-byte keys in this layout); syncmers: bl_scan_syncmers128; window
- * minimizers: bl_scan_minimizers128; super-k-mer records and the exact counter: bl_pack_super_kmers128 .. bl_count_super_kmers128.
+ * minimizers: bl_scan_minimizers128; super-k-mer records and the exact counter: bl_pack_super_kmers128 .. bl_count_super_kmers128;
+ * the count of every position's k-mer in a table of counted k-mers, without writing the values at all: bl_scan_kmer_counts.
  * NOT covered for k > 32: biolib_amd::read_pool. */
 int bl_scan_kmers128(bl_ctx* ctx, const bl_batch* batch, uint64_t first, uint64_t n, uint32_t k, uint64_t seed, uint32_t flags,
                      uint64_t* d_values /* 2 per position: lo, hi */, uint64_t* d_hashes, uint8_t* d_valid, bl_result* result);
@@ -279,6 +280,9 @@ int bl_ctx_set_exact_windows(bl_ctx* ctx, int on);
  *                                 (default 1)
  *   "jaccard128_path" 0 / 1 / 2   which kernel bl_jaccard_sorted_u128 runs: 1 the merge kernel, 2 the search kernel, 0 (default) the
  *                                 merge kernel when the larger set is less than 4 times the smaller one
+ *   "table_prefix_bits" -1 / 0..24  the width P of the prefix index of tables built LATER (bl_table_build_*): -1 (default) the library
+ *                                 chooses from the number of distinct keys, 0 .. 24 forces it, clamped to the table's key_bits
+ *                                 
  * The library reads no environment variable on the scan path. */
 int bl_ctx_set_option(bl_ctx* ctx, const char* name, int64_t value);
 /* Which kernels ran.  The window scans (bl_scan_minimizers, bl_scan_hash_sample, bl_scan_super_kmers, bl_scan_super_kmer_records,
@@ -404,6 +408,58 @@ int bl_jaccard_sorted_u128(bl_ctx* ctx, const uint64_t* d_a, uint64_t na, const 
                            uint64_t* union_size);
 int bl_partition_u128(bl_ctx* ctx, const uint64_t* d_keys, uint64_t n, uint32_t parts, uint64_t seed, uint64_t* d_out, uint64_t* counts);
 
+/* ---- the count table: what consumes (key, multiplicity) arrays ------------------------------------------------------------------------
+ * bl_count_super_kmers, bl_count_super_kmers128, bl_count_sorted_u64 / _u128 return distinct k-mers with their multiplicities (the
+ * super-k-mer counters in no particular order).  A bl_table holds such a list so that it can be asked: the count of any key
+ * (bl_table_lookup_*), the count of every k-mer of a batch (bl_scan_kmer_counts), the spectrum (bl_table_histogram).  The object is
+ * opaque, owned by the library and tied to the context it was built on (every call that takes a context and a table refuses a table of
+ * another context); destroy it with bl_table_destroy — before or after its context, but not while a scan that reads it is in flight.
+ *
+ * bl_table_build_u64 / _u128: n keys of one word, or of two words (low, high: the KEY LAYOUT and ALIGNMENT above), in ANY order, with
+ *   duplicates allowed — the outputs of several counting calls can be concatenated.  Equal keys are merged and their counts added,
+ *   saturating at 2^32 - 1.  d_counts == NULL: every entry counts 1 (a membership set; the multiplicities of a raw key list).  The
+ *   table copies what it needs: the caller's arrays are not modified and may be freed afterwards.  key_bits is the number of low bits
+ *   that can be non-zero (1 .. 64, 1 .. 128; 2k for k-mers, as in bl_sort_u128); the build checks the promise with an OR over all keys:
+ *   a key with a bit at or above key_bits gives BL_ERR_INVALID.  n = 0 builds an empty table in which every lookup answers 0.
+ *   n >= 2^32 and a misaligned 128-bit array give BL_ERR_INVALID.  Synchronous; temporaries from the context's scratch, as the set
+ *   operations.
+ * STORAGE  sorted distinct keys (128-bit ORDER as above), uint32_t counts, and a prefix index of 2^P + 1 uint32_t words: index[j] is
+ *   the first slot whose key has key >> (key_bits - P) >= j.  A search reads two neighbouring index words and bisects only between
+ *   them.  No answer depends on P.  The library chooses P from the number of distinct keys, 0 <= P <= min(key_bits, 24);
+ *   bl_ctx_set_option(ctx, "table_prefix_bits", v) forces it for later builds.
+ * bl_table_info: the number of distinct keys, words per key (1 or 2), key_bits and P (any pointer may be NULL).
+ * bl_table_arrays: the table's own sorted keys (n_distinct * key_words words) and counts, device pointers valid until bl_table_destroy
+ *   (NULL for an empty table).
+ * bl_table_lookup_u64 / _u128: d_counts_out[i] = the stored count of d_queries[i], 0 if the key is not in the table.  Queries may come in
+ *   any order and may repeat; a query with a bit at or above the table's key_bits is absent.  The width must match the table
+ *   (BL_ERR_INVALID otherwise).  Synchronous; n = 0 touches nothing.
+ * bl_table_histogram: hist[c] (HOST, n_bins words) = the number of distinct keys with count c for c < n_bins - 1, hist[n_bins - 1] =
+ *   those with count >= n_bins - 1.  1 <= n_bins <= 65536.  Synchronous. */
+typedef struct bl_table bl_table;
+int bl_table_build_u64(bl_ctx* ctx, const uint64_t* d_keys, const uint32_t* d_counts, uint64_t n, uint32_t key_bits, bl_table** out);
+int bl_table_build_u128(bl_ctx* ctx, const uint64_t* d_keys /* 2 per key: lo, hi */, const uint32_t* d_counts, uint64_t n, uint32_t key_bits,
+                        bl_table** out);
+int bl_table_destroy(bl_table* table);
+int bl_table_info(const bl_table* table, uint64_t* n_distinct, uint32_t* key_words, uint32_t* key_bits, uint32_t* prefix_bits);
+int bl_table_arrays(const bl_table* table, const uint64_t** d_keys, const uint32_t** d_counts);
+int bl_table_lookup_u64(bl_ctx* ctx, const bl_table* table, const uint64_t* d_queries, uint64_t n, uint32_t* d_counts_out);
+int bl_table_lookup_u128(bl_ctx* ctx, const bl_table* table, const uint64_t* d_queries /* 2 per key */, uint64_t n, uint32_t* d_counts_out);
+int bl_table_histogram(bl_ctx* ctx, const bl_table* table, uint64_t* hist, uint32_t n_bins);
+
+/* The fused scan: the table's count of the k-mer at every position of a range, without the k-mers ever being written.
+ * The k-mers, their validity, the canonical form, BL_FLAG_DROP_LAST and the range rules (at most 2^31 positions, n = 0: to the end,
+ * consecutive ranges concatenate) are exactly bl_scan_kmers128's; no hash is computed.  1 <= k <= 64; a table of one-word keys takes
+ * k <= 32 (the high word is 0); 2k <= the table's key_bits, otherwise BL_ERR_INVALID with a message.
+ *   d_counts[p-first]  the table's count of the k-mer at p; 0 where no k-mer starts or the key is absent.  Every position of the range
+ *                      is written.  NULL: digest only
+ *   d_valid[p-first]   as bl_scan_kmers128 (may be NULL)
+ * result: count := valid k-mers in the range, xor_value := XOR of their low words, aux := XOR of their high words (all three as
+ * bl_scan_kmers128), and — the two hash words have no hash to carry here and are REUSED, both as sums —
+ *   xor_hash := the NUMBER of valid k-mers whose key is in the table, xor_pos := the wrapping SUM of the counts looked up; redone = 0.
+ * Asynchronous like every scan (BL_FLAG_SYNC applies): the table must stay alive until the sync. */
+int bl_scan_kmer_counts(bl_ctx* ctx, const bl_batch* batch, uint64_t first, uint64_t n, uint32_t k, uint32_t flags, const bl_table* table,
+                        uint32_t* d_counts, uint8_t* d_valid, bl_result* result);
+
 /* Count reduction across the GPUs of one node: ctxs[g] is the context of device g (all distinct devices),
  * counters holds n_gpu rows of n 64-bit counters — row g = GPU g's local counts in, the column sums out (in every row).  One
  * ncclAllReduce(sum, uint64) per GPU over RCCL / xGMI, called on RCCL's C API directly (librccl.so.1 is loaded on first use);
@@ -478,7 +534,8 @@ int bl_expand_super_kmers(bl_ctx* ctx, const uint64_t* d_records, uint64_t n_gro
  *   each in an LDS table of 16-byte keys whose empty slots are marked by an owner word, not by a key value: every k and strand mode is
  *   taken, k = 64 without the canonical flag (the all-T 64-mer is all ones) included.  Oversized buckets take expand + 128-bit sort +
  *   run-length; bl_ctx_set_option("count128_tables", 0) sends every bucket that way (same result).  Terminates on any record bits.
- *   (bl_sort_u128 / bl_count_sorted_u128 put the distinct k-mers in order.)
+ *   (bl_sort_u128 / bl_count_sorted_u128 put the distinct k-mers in order; bl_table_build_u128 takes the two arrays as they are and
+ *   answers lookups, bl_scan_kmer_counts and the spectrum from them.)
  * NOT provided for k > 32: biolib_amd::read_pool for wide views, and any multi-GPU measurement of this path. */
 int bl_scan_super_kmer_records128(bl_ctx* ctx, const bl_batch* batch, uint64_t first, uint64_t n, uint32_t k, uint32_t m, uint64_t seed, uint32_t flags,
                                   uint64_t* d_records /* 4 per group, 32-byte aligned */, uint64_t* d_hashes, uint64_t capacity, bl_result* result);
