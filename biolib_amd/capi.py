@@ -26,7 +26,7 @@ SYMBOLS = [
     "bl_sort_u128", "bl_sort_unique_u128", "bl_count_sorted_u128", "bl_jaccard_sorted_u128", "bl_partition_u128",
     "bl_write_run_u128", "bl_write_vector_u128", "bl_file_count_u128", "bl_read_file_u128_host", "bl_read_file_u128", "bl_merge_runs_u128",
     "bl_table_build_u64", "bl_table_build_u128", "bl_table_destroy", "bl_table_info", "bl_table_arrays", "bl_table_lookup_u64", "bl_table_lookup_u128",
-    "bl_table_histogram", "bl_scan_kmer_counts",
+    "bl_table_histogram", "bl_scan_kmer_counts", "bl_scan_read_counts",
 ]
 
 
@@ -44,6 +44,14 @@ class Result(C.Structure):
         return dict(count=int(self.count), xor_value=int(self.xor_value), xor_hash=int(self.xor_hash), xor_pos=int(self.xor_pos),
                     aux=int(self.aux), status=int(self.status))
 
+
+class ReadCountsRecord(C.Structure):
+    """bl_read_counts: one per sequence (48 bytes)"""
+    _fields_ = [("n_kmers", C.c_uint32), ("n_found", C.c_uint32), ("n_solid", C.c_uint32), ("min_count", C.c_uint32), ("max_count", C.c_uint32),
+                ("reserved", C.c_uint32), ("sum_counts", C.c_uint64), ("weak_begin", C.c_uint64), ("weak_end", C.c_uint64)]
+
+
+READ_COUNTS_INIT, READ_COUNTS_ACCUMULATE = 0, 1
 
 _lib = None
 
@@ -183,6 +191,8 @@ def lib():
         L.bl_table_lookup_u128.argtypes = [vp, vp, vp, u64, vp]
         L.bl_table_histogram.argtypes = [vp, vp, vp, u32]
         L.bl_scan_kmer_counts.argtypes = [vp, vp, u64, u64, u32, u32, vp, vp, vp, C.POINTER(Result)]
+    if "BIOLIB_AMD_LIB" not in os.environ or hasattr(L, "bl_scan_read_counts"):
+        L.bl_scan_read_counts.argtypes = [vp, vp, u64, u64, u32, u32, vp, u32, vp, u32, vp, C.POINTER(Result)]
     _lib = L
     return L
 

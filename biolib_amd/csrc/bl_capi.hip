@@ -16,6 +16,7 @@
 #include "../../include/biolib_amd.h"
 #include "bl_launch.hpp"
 #include "bl_lookup_launch.hpp"
+#include "bl_read_counts_launch.hpp"
 #include "bl_scan128_launch.hpp"
 
 namespace {
@@ -1035,6 +1036,46 @@ int bl_scan_kmer_counts(bl_ctx* c, const bl_batch* b, uint64_t first, uint64_t n
     if (rc != BL_OK) return rc;
     hipError_t e = bllk::launch_scan_counts(p, c->stream);
     if (e != hipSuccess) return fail(BL_ERR_HIP, std::string("scan_counts_kernel: ") + hipGetErrorString(e));
+    rc = kernel_event(c, false);
+    if (rc != BL_OK) return rc;
+    return end_scan(c, /*add_mask: count, found, sum*/ (1u << 0) | (1u << 2) | (1u << 3), result, false, 0, flags);
+}
+
+// bl_scan_kmer_counts reduced per sequence inside the scan: bl_read_counts.hip
+int bl_scan_read_counts(bl_ctx* c, const bl_batch* b, uint64_t first, uint64_t n, uint32_t k, uint32_t flags, const bl_table* table, uint32_t min_count,
+                        const uint64_t* d_offsets, uint32_t mode, bl_read_counts* d_records, bl_result* result)
+{
+    static_assert(sizeof(bl_read_counts) == sizeof(blrc::Record) && alignof(blrc::Record) == 16, "the kernel's record is the header's");
+    if (!table) return fail(BL_ERR_INVALID, "table is NULL");
+    if (c && table->ctx != c) return fail(BL_ERR_INVALID, "the table belongs to another context");
+    if (table->view.key_words == 1 && k > 32) return fail(BL_ERR_INVALID, "a table of one-word keys takes k <= 32");
+    if (k >= 1 && 2 * k > table->view.key_bits)
+        return fail(BL_ERR_INVALID, "2k = " + std::to_string(2 * k) + " exceeds the table's key_bits = " + std::to_string(table->view.key_bits));
+    if (min_count == 0) return fail(BL_ERR_INVALID, "min_count must be at least 1");
+    if (mode != BL_READ_COUNTS_INIT && mode != BL_READ_COUNTS_ACCUMULATE) return fail(BL_ERR_INVALID, "mode is BL_READ_COUNTS_INIT or BL_READ_COUNTS_ACCUMULATE");
+    if (!d_records) return fail(BL_ERR_INVALID, "d_records is NULL");
+    if (reinterpret_cast<uintptr_t>(d_records) % 16 != 0) return fail(BL_ERR_INVALID, "d_records must be 16-byte aligned");
+    if (b && !d_offsets && b->n_seqs > 1 && b->read_len == 0)
+        return fail(BL_ERR_INVALID, "d_offsets is NULL: only a single-sequence or a fixed-read-length batch finds its sequences without the offsets");
+    blrc::ReadCountParams p{};
+    bool empty;
+    int rc = prepare_kmers128(c, b, first, n, k, 0, flags, nullptr, p.km, result, empty);
+    if (rc != BL_OK || empty) return rc;
+    p.table = table->view;
+    p.min_count = min_count;
+    p.offsets = d_offsets;
+    p.n_seqs = b->n_seqs;  // >= 1: the range is not empty
+    p.read_len = d_offsets ? 0 : b->read_len;
+    p.records = reinterpret_cast<blrc::Record*>(d_records);
+    rc = begin_scan(c);
+    if (rc != BL_OK) return rc;
+    p.km.shards = c->shards();
+    rc = kernel_event(c, true);
+    if (rc != BL_OK) return rc;
+    hipError_t e = mode == BL_READ_COUNTS_INIT ? blrc::launch_read_counts_init(p, c->stream) : hipSuccess;
+    if (e != hipSuccess) return fail(BL_ERR_HIP, std::string("read_counts_init_kernel: ") + hipGetErrorString(e));
+    e = blrc::launch_read_counts(p, c->stream);
+    if (e != hipSuccess) return fail(BL_ERR_HIP, std::string("read_counts_kernel: ") + hipGetErrorString(e));
     rc = kernel_event(c, false);
     if (rc != BL_OK) return rc;
     return end_scan(c, /*add_mask: count, found, sum*/ (1u << 0) | (1u << 2) | (1u << 3), result, false, 0, flags);

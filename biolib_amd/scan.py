@@ -9,7 +9,7 @@ import weakref
 import numpy as np
 
 from . import capi
-from .capi import FLAG_CANONICAL, FLAG_DROP_LAST, FLAG_SYNC, BiolibError, Result, check
+from .capi import FLAG_CANONICAL, FLAG_DROP_LAST, FLAG_SYNC, READ_COUNTS_ACCUMULATE, READ_COUNTS_INIT, BiolibError, Result, check
 
 
 def hash64(value, seed=0):
@@ -160,17 +160,17 @@ class Context:
         if read_len:
             h = C.c_void_p()
             check(self._lib.bl_batch_upload_reads(self._h, arr.ctypes.data_as(C.c_void_p) if arr.size else None, arr.size, int(read_len), C.byref(h)))
-            return Batch(self, h)
+            return Batch(self, h, read_len=int(read_len))
         offs = None if offsets is None else np.ascontiguousarray(offsets, dtype=np.uint64)
         h = C.c_void_p()
         check(self._lib.bl_batch_upload(self._h, arr.ctypes.data_as(C.c_void_p) if arr.size else None, arr.size,
                                         None if offs is None else offs.ctypes.data_as(C.c_void_p), 0 if offs is None else len(offs) - 1, C.byref(h)))
-        return Batch(self, h)
+        return Batch(self, h, offsets=offs)
 
     def synth(self, seed, n_bases, read_len=0):
         h = C.c_void_p()
         check(self._lib.bl_batch_synth(self._h, int(seed), int(n_bases), int(read_len), C.byref(h)))
-        return Batch(self, h)
+        return Batch(self, h, read_len=int(read_len))
 
     def from_text(self, text):
         """Parse raw FASTA / 4-line FASTQ text on the device (bl_batch_from_text).  text: bytes or a uint8 numpy array."""
@@ -188,7 +188,7 @@ class Context:
         check(self._lib.bl_batch_from_device(self._h, C.c_void_p(t.data_ptr()), t.numel(),
                                              None if offs is None else offs.ctypes.data_as(C.c_void_p), 0 if offs is None else len(offs) - 1,
                                              int(read_len), C.byref(h)))
-        b = Batch(self, h)
+        b = Batch(self, h, offsets=offs, read_len=0 if offs is not None else int(read_len))
         b._keep = t
         return b
 
@@ -604,14 +604,41 @@ class CountTable:
         return hist
 
 
+class ReadCounts:
+    """The records of bl_scan_read_counts, one per sequence: `records` is the raw device buffer, int64[n_seqs, 6]; the fields are views
+    of it (no copy).  The 32-bit fields are int32 tensors holding uint32 bits, the 64-bit ones int64 holding uint64 bits: min_count is
+    -1 (0xFFFFFFFF) and weak_begin -1 (UINT64_MAX) where the sequence has no k-mer / no weak k-mer."""
+
+    def __init__(self, ctx, n_seqs):
+        import torch
+
+        self.n_seqs = int(n_seqs)
+        self.records = torch.zeros((max(self.n_seqs, 1), 6), dtype=torch.int64, device=ctx.torch_device)  # (torch allocations are 16-byte aligned)
+        words = self.records.view(torch.int32)  # [n_seqs, 12]
+        words[:, 3] = -1      # min_count: the identity record
+        self.records[:, 4] = -1  # weak_begin
+        n = self.n_seqs
+        self.n_kmers, self.n_found, self.n_solid, self.min_count, self.max_count = (words[:n, i] for i in range(5))
+        self.sum_counts, self.weak_begin, self.weak_end = (self.records[:n, i] for i in (3, 4, 5))
+
+    def host(self):
+        """a numpy structured array of the records (field names as the attributes, plus `reserved`)"""
+        dt = np.dtype([("n_kmers", "<u4"), ("n_found", "<u4"), ("n_solid", "<u4"), ("min_count", "<u4"), ("max_count", "<u4"), ("reserved", "<u4"),
+                       ("sum_counts", "<u8"), ("weak_begin", "<u8"), ("weak_end", "<u8")])
+        return self.records[:self.n_seqs].cpu().numpy().view(dt).reshape(-1).copy()
+
+
 class Batch:
     """Device-resident sequences (bl_batch)."""
 
-    def __init__(self, ctx, handle):
+    def __init__(self, ctx, handle, offsets=None, read_len=0):
         self.ctx = ctx
         self._h = handle
         self._lib = ctx._lib
         self._keep = None
+        self.offsets = offsets     # the host offsets the batch was made from (uint64 numpy array), None where it was made without
+        self.read_len = read_len   # != 0: made as reads of this length laid end to end
+        self._d_offsets = None     # read_counts: the device copy, uploaded once
         ctx._batches.add(self)
 
     def close(self):
@@ -679,6 +706,14 @@ class Batch:
         result = result if result is not None else Result()
         self.ctx._hold(result, flags)
         check(self._lib.bl_scan_kmer_counts(self.ctx._h, self._h, first, n, k, flags, table._h, _ptr(counts), _ptr(valid), C.byref(result)))
+        return result
+
+    def read_counts_raw(self, table, k, flags, min_count, records, first=0, n=0, offsets=None, mode=READ_COUNTS_INIT, result=None):
+        """bl_scan_read_counts: `records` takes 48 bytes per sequence of the batch (16-byte aligned), `offsets` is the device copy of the
+        batch's n_seqs + 1 offsets (None: a single-sequence or fixed-read-length batch); the table must stay open until the sync"""
+        result = result if result is not None else Result()
+        self.ctx._hold(result, flags)
+        check(self._lib.bl_scan_read_counts(self.ctx._h, self._h, first, n, k, flags, table._h, min_count, _ptr(offsets), mode, _ptr(records), C.byref(result)))
         return result
 
     def hash_sample128_raw(self, k, seed, threshold, flags, first=0, n=0, values=None, positions=None, hashes=None, capacity=0, result=None):
@@ -768,6 +803,43 @@ class Batch:
         out["found"] = out.pop("xor_hash")
         out["sum_counts"] = out.pop("xor_pos")
         return (counts[:span], ok[:span], out) if valid else (counts[:span], out)
+
+    def _device_offsets(self, offsets):
+        """the offsets read_counts hands to the scan: the caller's, or the batch's own uploaded once; None where the batch needs none"""
+        import torch
+
+        if offsets is not None:
+            if isinstance(offsets, torch.Tensor):
+                if not (offsets.is_cuda and offsets.element_size() == 8 and offsets.is_contiguous() and offsets.numel() == self.n_seqs + 1):
+                    raise ValueError("offsets: a contiguous 64-bit device tensor of n_seqs + 1 entries")
+                return offsets
+            host = np.ascontiguousarray(offsets, dtype=np.uint64)
+            if len(host) != self.n_seqs + 1:
+                raise ValueError("offsets: n_seqs + 1 entries")
+            return torch.from_numpy(host.view(np.int64)).to(self.ctx.torch_device)
+        if self._d_offsets is None and self.offsets is not None and len(self.offsets) == self.n_seqs + 1:
+            self._d_offsets = torch.from_numpy(self.offsets.view(np.int64)).to(self.ctx.torch_device)
+        return self._d_offsets  # None on a batch that is neither fixed-length nor a single sequence: the library refuses with a message
+
+    def read_counts(self, table, k, min_count=1, canonical=False, drop_last=False, first=0, n=0, offsets=None, into=None):
+        """The counts kmer_counts looks up, reduced per sequence inside the scan: (ReadCounts, result).  One 48-byte record per sequence
+        of the batch — n_kmers, n_found, n_solid (count >= min_count), min_count, max_count, sum_counts and the span of the weak
+        k-mers (count < min_count) — instead of five bytes per base.  The scan writes the records of the sequences the range
+        [first, first + n) meets; every other record of a new buffer is the identity (no k-mers).  into= an earlier ReadCounts merges
+        into its records (BL_READ_COUNTS_ACCUMULATE): ranges that cut a read anywhere add up to the whole-batch answer.  offsets: the
+        batch's n_seqs + 1 offsets (host array or device tensor), needed only where the batch was not made from offsets by upload /
+        from_tensor and is neither fixed-length nor a single sequence (the device parser's batches).  result as kmer_counts."""
+        d_offsets = self._device_offsets(offsets)
+        rc = into if into is not None else ReadCounts(self.ctx, self.n_seqs)
+        if rc.n_seqs != self.n_seqs:
+            raise ValueError("into= holds the records of another batch")
+        self.ctx._inputs_ready()
+        r = self.read_counts_raw(table, k, _flags(canonical, drop_last, True), int(min_count), rc.records, first, n, d_offsets,
+                                 READ_COUNTS_ACCUMULATE if into is not None else READ_COUNTS_INIT)
+        out = r.as_dict()
+        out["found"] = out.pop("xor_hash")
+        out["sum_counts"] = out.pop("xor_pos")
+        return rc, out
 
     def hash_sample128(self, k, seed=0, threshold=2**64 - 1, canonical=False, drop_last=False, first=0, n=0, capacity=None, device=False):
         """k-mers up to k = 64 with hash64_u128(value, seed) < threshold, in position order; values has shape (count, 2) as in kmers128.

@@ -460,6 +460,36 @@ int bl_table_histogram(bl_ctx* ctx, const bl_table* table, uint64_t* hist, uint3
 int bl_scan_kmer_counts(bl_ctx* ctx, const bl_batch* batch, uint64_t first, uint64_t n, uint32_t k, uint32_t flags, const bl_table* table,
                         uint32_t* d_counts, uint8_t* d_valid, bl_result* result);
 
+/* The same scan reduced per sequence on the chip: one 48-byte record per read instead of five bytes per base.  The k-mers, their
+ * validity, the canonical form, BL_FLAG_DROP_LAST, 1 <= k <= 64, the table rules, the range rules and the asynchrony are exactly
+ * bl_scan_kmer_counts's, and `result` is word for word what that call returns for the same arguments.
+ *   min_count   >= 1 (0: BL_ERR_INVALID): a k-mer is solid if its count >= min_count, weak otherwise (an absent key counts 0)
+ *   d_offsets   DEVICE copy of the n_seqs + 1 offsets the batch was made from: the sequence of position p is the last one whose offset
+ *               is <= p.  May be NULL for a single-sequence batch and for a fixed-read-length batch (sequence = p / read_len); NULL on
+ *               any other batch is BL_ERR_INVALID.  The array is trusted for content, not for safety: every search in it stays inside
+ *               [0, n_seqs], so a wrong array gives wrong statistics but no access outside d_offsets or d_records.
+ *   d_records   bl_batch_n_seqs(batch) records, indexed by sequence, 16-byte aligned (NULL or misaligned: BL_ERR_INVALID)
+ * The call touches only the records of the sequences from the one that holds `first` to the one that holds the range's last position,
+ * empty sequences between them included (they keep the identity record); no other record is written.
+ *   BL_READ_COUNTS_INIT        the touched records are first set to the identity — zeros, min_count 0xFFFFFFFF, weak_begin
+ *                              UINT64_MAX, weak_end 0 — and then filled
+ *   BL_READ_COUNTS_ACCUMULATE  they are merged into as they stand: ranges that cut a read anywhere add up to the whole-batch answer
+ * An empty range succeeds and writes nothing.  The records are integer sums, minima and maxima: bit-reproducible. */
+typedef struct bl_read_counts {
+    uint32_t n_kmers;    /* valid k-mers of the read inside the range */
+    uint32_t n_found;    /* ... whose key is in the table (a stored count of 0 is found) */
+    uint32_t n_solid;    /* ... whose count >= min_count */
+    uint32_t min_count;  /* smallest count over the valid k-mers (absent = 0); 0xFFFFFFFF if n_kmers == 0 */
+    uint32_t max_count;  /* largest; 0 if n_kmers == 0 */
+    uint32_t reserved;   /* 0 */
+    uint64_t sum_counts; /* exact sum of the counts */
+    uint64_t weak_begin; /* read-relative position of the first valid k-mer with count < min_count; UINT64_MAX if none */
+    uint64_t weak_end;   /* 1 + read-relative position of the last such k-mer; 0 if none */
+} bl_read_counts;
+enum { BL_READ_COUNTS_INIT = 0, BL_READ_COUNTS_ACCUMULATE = 1 };
+int bl_scan_read_counts(bl_ctx* ctx, const bl_batch* batch, uint64_t first, uint64_t n, uint32_t k, uint32_t flags, const bl_table* table,
+                        uint32_t min_count, const uint64_t* d_offsets, uint32_t mode, bl_read_counts* d_records, bl_result* result);
+
 /* Count reduction across the GPUs of one node: ctxs[g] is the context of device g (all distinct devices),
  * counters holds n_gpu rows of n 64-bit counters — row g = GPU g's local counts in, the column sums out (in every row).  One
  * ncclAllReduce(sum, uint64) per GPU over RCCL / xGMI, called on RCCL's C API directly (librccl.so.1 is loaded on first use);
