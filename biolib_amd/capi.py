@@ -26,7 +26,7 @@ SYMBOLS = [
     "bl_sort_u128", "bl_sort_unique_u128", "bl_count_sorted_u128", "bl_jaccard_sorted_u128", "bl_partition_u128",
     "bl_write_run_u128", "bl_write_vector_u128", "bl_file_count_u128", "bl_read_file_u128_host", "bl_read_file_u128", "bl_merge_runs_u128",
     "bl_table_build_u64", "bl_table_build_u128", "bl_table_destroy", "bl_table_info", "bl_table_arrays", "bl_table_lookup_u64", "bl_table_lookup_u128",
-    "bl_table_histogram", "bl_scan_kmer_counts", "bl_scan_read_counts",
+    "bl_table_histogram", "bl_scan_kmer_counts", "bl_scan_read_counts", "bl_table_combine", "bl_table_filter",
 ]
 
 
@@ -52,6 +52,18 @@ class ReadCountsRecord(C.Structure):
 
 
 READ_COUNTS_INIT, READ_COUNTS_ACCUMULATE = 0, 1
+
+
+class TableStats(C.Structure):
+    """bl_table_stats"""
+    _fields_ = [(name, C.c_uint64) for name in ("n_a_only", "n_b_only", "n_both", "n_out", "sum_min", "sum_max", "sum_out", "reserved")]
+
+    def as_dict(self):
+        return {name: int(getattr(self, name)) for name, _ in self._fields_ if name != "reserved"}
+
+
+TABLE_UNION, TABLE_INTERSECT, TABLE_SUBTRACT, TABLE_COUNT_SUBTRACT = 0, 1, 2, 3
+COUNT_SUM, COUNT_MIN, COUNT_MAX, COUNT_LEFT, COUNT_RIGHT = 0, 1, 2, 3, 4
 
 _lib = None
 
@@ -193,6 +205,9 @@ def lib():
         L.bl_scan_kmer_counts.argtypes = [vp, vp, u64, u64, u32, u32, vp, vp, vp, C.POINTER(Result)]
     if "BIOLIB_AMD_LIB" not in os.environ or hasattr(L, "bl_scan_read_counts"):
         L.bl_scan_read_counts.argtypes = [vp, vp, u64, u64, u32, u32, vp, u32, vp, u32, vp, C.POINTER(Result)]
+    if "BIOLIB_AMD_LIB" not in os.environ or hasattr(L, "bl_table_combine"):
+        L.bl_table_combine.argtypes = [vp, vp, vp, u32, u32, u32, u32, C.POINTER(vp), C.POINTER(TableStats)]
+        L.bl_table_filter.argtypes = [vp, vp, u32, u32, C.POINTER(vp)]
     _lib = L
     return L
 

@@ -114,6 +114,29 @@ __global__ __launch_bounds__(bl::TPB) void scan_counts_kernel(const ScanCountPar
 
 hipError_t launch_scan_counts(const ScanCountParams& p, hipStream_t stream) { return bl::launch_tiles128(scan_counts_kernel, p, p.km.n_tiles, stream); }
 
+void free_table(bl_table* t)
+{
+    if (t->view.keys) (void)hipFree(const_cast<uint64_t*>(t->view.keys));
+    if (t->view.counts) (void)hipFree(const_cast<uint32_t*>(t->view.counts));
+    if (t->view.index) (void)hipFree(const_cast<uint32_t*>(t->view.index));
+    delete t;
+}
+
+hipError_t finish_table(bl_ctx* ctx, bl_table* t, hipStream_t s)
+{
+    t->view.prefix_bits = choose_prefix_bits(bl_ctx_table_prefix_bits(ctx), t->view.n, t->view.key_bits);
+    const ull words = (1ull << t->view.prefix_bits) + 1;
+    void* index = nullptr;
+    hipError_t e = hipMalloc(&index, words * sizeof(uint32_t));
+    if (e == hipSuccess) {
+        t->view.index = static_cast<uint32_t*>(index);
+        hipLaunchKernelGGL(index_fill_kernel, dim3((unsigned)((words + LTPB - 1) / LTPB)), dim3(LTPB), 0, s, t->view, static_cast<uint32_t*>(index));
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipStreamSynchronize(s);
+    return e;
+}
+
 namespace {
 
 struct SatAdd {
@@ -128,14 +151,6 @@ int hip_rc(hipError_t e) { return bl_set_error(e == hipErrorOutOfMemory ? BL_ERR
 bool misaligned(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) != 0; }
 size_t round16(size_t b) { return (b + 15) & ~(size_t)15; }
 unsigned blocks_for(ull n) { return (unsigned)((n + LTPB - 1) / LTPB < 256 * 16 ? (n + LTPB - 1) / LTPB : 256 * 16); }
-
-void free_table(bl_table* t)
-{
-    if (t->view.keys) (void)hipFree(const_cast<uint64_t*>(t->view.keys));
-    if (t->view.counts) (void)hipFree(const_cast<uint32_t*>(t->view.counts));
-    if (t->view.index) (void)hipFree(const_cast<uint32_t*>(t->view.index));
-    delete t;
-}
 
 // KeyT: unsigned long long or __uint128_t — what rocPRIM sorts; the bytes are the table's
 template <typename KeyT>
@@ -217,16 +232,7 @@ int build(bl_ctx* ctx, const uint64_t* d_keys, const uint32_t* d_counts, uint64_
         if (e != hipSuccess) { free_table(t); return hip_rc(e); }
     }
     t->view.n = (uint32_t)distinct;
-    t->view.prefix_bits = choose_prefix_bits(bl_ctx_table_prefix_bits(ctx), distinct, key_bits);
-    const ull words = (1ull << t->view.prefix_bits) + 1;
-    void* index = nullptr;
-    e = hipMalloc(&index, words * sizeof(uint32_t));
-    if (e == hipSuccess) {
-        t->view.index = static_cast<uint32_t*>(index);
-        hipLaunchKernelGGL(index_fill_kernel, dim3((unsigned)((words + LTPB - 1) / LTPB)), dim3(LTPB), 0, s, t->view, static_cast<uint32_t*>(index));
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = hipStreamSynchronize(s);
+    e = finish_table(ctx, t, s);
     if (e != hipSuccess) { free_table(t); return hip_rc(e); }
     *out = t;
     return BL_OK;

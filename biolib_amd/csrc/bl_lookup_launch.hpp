@@ -1,4 +1,5 @@
-// bl_lookup_launch.hpp — what bl_capi.hip needs of bl_lookup.hip for bl_scan_kmer_counts: the table object and the scan's launcher.
+// bl_lookup_launch.hpp — what the other translation units need of bl_lookup.hip: the table object, the scan's launcher
+// (bl_scan_kmer_counts, bl_capi.hip) and the last step of making a table (bl_table_combine, bl_table_ops.hip).
 #pragma once
 #include <hip/hip_runtime.h>
 #include "bl_lookup_core.hpp"
@@ -14,4 +15,9 @@ struct bl_table {
 
 namespace bllk {
 hipError_t launch_scan_counts(const ScanCountParams& p, hipStream_t stream);
+// The last step of making a table: view.keys / counts / n / key_words / key_bits are set (sorted distinct keys in exact-size allocations
+// of the table's own); chooses P under the context's "table_prefix_bits", allocates the index, fills it with index_fill_kernel and waits
+// for the stream.  On an error the caller frees the table.
+hipError_t finish_table(bl_ctx* ctx, bl_table* t, hipStream_t stream);
+void free_table(bl_table* t);  // the three arrays and the object
 }

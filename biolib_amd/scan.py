@@ -603,6 +603,57 @@ class CountTable:
         check(self._lib.bl_table_histogram(self.ctx._h, self._h, hist.ctypes.data_as(C.c_void_p), int(n_bins)))
         return hist
 
+    # ---- table algebra (bl_table_combine): one merge of the two sorted tables, no rebuild
+    _COUNT_MODES = dict(sum=capi.COUNT_SUM, min=capi.COUNT_MIN, max=capi.COUNT_MAX, left=capi.COUNT_LEFT, right=capi.COUNT_RIGHT)
+
+    def combine_raw(self, other, op, mode, min_count=0, max_count=2**32 - 1, table=True):
+        """bl_table_combine: (CountTable or None, stats dict); other None: the empty table.  The library checks op, mode and bounds."""
+        if not 0 <= int(min_count) < 2**32 or not 0 <= int(max_count) < 2**32:
+            raise ValueError("count bounds are 32-bit unsigned")
+        h, st = C.c_void_p(), capi.TableStats()
+        check(self._lib.bl_table_combine(self.ctx._h, self._h, other._h if other is not None else None, int(op), int(mode), int(min_count),
+                                         int(max_count), C.byref(h) if table else None, C.byref(st)))
+        return (CountTable(self.ctx, h) if table else None), st.as_dict()
+
+    def _combine(self, other, op, count, min_count, max_count):
+        if count not in self._COUNT_MODES:
+            raise ValueError(f"count is one of {sorted(self._COUNT_MODES)}")
+        return self.combine_raw(other, op, self._COUNT_MODES[count], min_count, max_count)[0]
+
+    def union(self, other, count="sum", min_count=0, max_count=2**32 - 1):
+        """The keys of either table; where both hold a key its count is count(a, b): "sum" (saturating at 2^32 - 1), "min", "max", "left"
+        (this table's) or "right".  Then only the keys with min_count <= count <= max_count are kept.  A new CountTable; the inputs stay."""
+        return self._combine(other, capi.TABLE_UNION, count, min_count, max_count)
+
+    def intersect(self, other, count="min", min_count=0, max_count=2**32 - 1):
+        """The keys of both tables with count(a, b), bounded as in union"""
+        return self._combine(other, capi.TABLE_INTERSECT, count, min_count, max_count)
+
+    def subtract(self, other, min_count=0, max_count=2**32 - 1):
+        """The keys of this table that `other` lacks, with their counts, bounded as in union"""
+        return self._combine(other, capi.TABLE_SUBTRACT, "left", min_count, max_count)
+
+    def subtract_counts(self, other, min_count=0, max_count=2**32 - 1):
+        """Every key of this table whose count a exceeds its count b in `other` (0 where absent), with a - b, bounded as in union"""
+        return self._combine(other, capi.TABLE_COUNT_SUBTRACT, "left", min_count, max_count)
+
+    def filter(self, min_count=0, max_count=2**32 - 1):
+        """The keys with min_count <= count <= max_count: filter(2) is the table of the solid k-mers"""
+        if not 0 <= int(min_count) < 2**32 or not 0 <= int(max_count) < 2**32:
+            raise ValueError("count bounds are 32-bit unsigned")
+        h = C.c_void_p()
+        check(self._lib.bl_table_filter(self.ctx._h, self._h, int(min_count), int(max_count), C.byref(h)))
+        return CountTable(self.ctx, h)
+
+    def compare(self, other):
+        """The statistics of the pair without building a table: n_a_only, n_b_only, n_both, sum_min, sum_max (and n_out, sum_out of the
+        plain sum union), plus jaccard = n_both / |A u B| and weighted_jaccard = sum_min / sum_max (0.0 where the denominator is 0)"""
+        st = self.combine_raw(other, capi.TABLE_UNION, capi.COUNT_SUM, table=False)[1]
+        union = st["n_a_only"] + st["n_b_only"] + st["n_both"]
+        st["jaccard"] = st["n_both"] / union if union else 0.0
+        st["weighted_jaccard"] = st["sum_min"] / st["sum_max"] if st["sum_max"] else 0.0
+        return st
+
 
 class ReadCounts:
     """The records of bl_scan_read_counts, one per sequence: `records` is the raw device buffer, int64[n_seqs, 6]; the fields are views

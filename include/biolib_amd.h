@@ -446,6 +446,37 @@ int bl_table_lookup_u64(bl_ctx* ctx, const bl_table* table, const uint64_t* d_qu
 int bl_table_lookup_u128(bl_ctx* ctx, const bl_table* table, const uint64_t* d_queries /* 2 per key */, uint64_t n, uint32_t* d_counts_out);
 int bl_table_histogram(bl_ctx* ctx, const bl_table* table, uint64_t* hist, uint32_t n_bins);
 
+/* Table algebra: a new table from two tables A and B of the same context, key_words and key_bits (the kmc_tools simple operations), in
+ * one linear merge of the two sorted arrays — no sort, no rebuild.  For a key x with stored count a in A and b in B:
+ *   BL_TABLE_UNION           x in A or B; c = f(a, b) where both hold it, else the count of the table that holds it
+ *   BL_TABLE_INTERSECT       x in both; c = f(a, b)
+ *   BL_TABLE_SUBTRACT        x in A and not in B; c = a
+ *   BL_TABLE_COUNT_SUBTRACT  x in A and a > b, with b = 0 where B lacks x; c = a - b
+ * f is count_mode: BL_COUNT_SUM (saturating at 2^32 - 1, as the build), _MIN, _MAX, _LEFT (a) or _RIGHT (b); the two subtractions take
+ * BL_COUNT_LEFT only.  After the op a key is kept iff count_lo <= c <= count_hi ((0, UINT32_MAX): all).  b == NULL is the empty table;
+ * a == b is legal.  The inputs are not modified.  *out is an ordinary table (sorted distinct keys, exact-size arrays, a prefix index
+ * chosen under the current "table_prefix_bits"): every bl_table_* call and both scans take it; an empty result is the n = 0 table.
+ * Results are bit-reproducible.
+ * stats (nullable) — everything but n_out and sum_out is independent of op, mode and bounds:
+ *   n_a_only, n_b_only, n_both   |A \ B|, |B \ A|, |A n B|: Jaccard = n_both / (n_a_only + n_b_only + n_both)
+ *   sum_min                      sum of min(a, b) over the common keys   }  wrapping 64-bit sums;
+ *   sum_max                      sum of max(a, b) over the union, an absent count being 0   }  weighted Jaccard = sum_min / sum_max
+ *   n_out, sum_out               the size of the result and the sum of its counts
+ * out == NULL: only the counting pass runs, nothing is allocated (a comparison of two tables).
+ * BL_ERR_INVALID with a message: NULL ctx or a, a table of another context, tables of different key_words or key_bits, an unknown op or
+ * mode, a mode the op does not take, count_lo > count_hi.  BL_ERR_CAPACITY: the result would have 2^32 entries or more (stats filled,
+ * nothing allocated).  Synchronous; temporaries from the context's scratch, as the set operations.
+ * bl_table_filter(ctx, a, lo, hi, out) is bl_table_combine(ctx, a, NULL, BL_TABLE_UNION, BL_COUNT_LEFT, lo, hi, out, NULL): the solid
+ * table (lo = 2) or a table without its repeat tail (hi). */
+enum { BL_TABLE_UNION = 0, BL_TABLE_INTERSECT = 1, BL_TABLE_SUBTRACT = 2, BL_TABLE_COUNT_SUBTRACT = 3 };
+enum { BL_COUNT_SUM = 0, BL_COUNT_MIN = 1, BL_COUNT_MAX = 2, BL_COUNT_LEFT = 3, BL_COUNT_RIGHT = 4 };
+typedef struct {
+    uint64_t n_a_only, n_b_only, n_both, n_out, sum_min, sum_max, sum_out, reserved;
+} bl_table_stats;
+int bl_table_combine(bl_ctx* ctx, const bl_table* a, const bl_table* b /* NULL = empty */, uint32_t op, uint32_t count_mode, uint32_t count_lo,
+                     uint32_t count_hi, bl_table** out /* NULL = stats only */, bl_table_stats* stats /* nullable */);
+int bl_table_filter(bl_ctx* ctx, const bl_table* a, uint32_t count_lo, uint32_t count_hi, bl_table** out);
+
 /* The fused scan: the table's count of the k-mer at every position of a range, without the k-mers ever being written.
  * The k-mers, their validity, the canonical form, BL_FLAG_DROP_LAST and the range rules (at most 2^31 positions, n = 0: to the end,
  * consecutive ranges concatenate) are exactly bl_scan_kmers128's; no hash is computed.  1 <= k <= 64; a table of one-word keys takes
