@@ -27,6 +27,7 @@ SYMBOLS = [
     "bl_write_run_u128", "bl_write_vector_u128", "bl_file_count_u128", "bl_read_file_u128_host", "bl_read_file_u128", "bl_merge_runs_u128",
     "bl_table_build_u64", "bl_table_build_u128", "bl_table_destroy", "bl_table_info", "bl_table_arrays", "bl_table_lookup_u64", "bl_table_lookup_u128",
     "bl_table_histogram", "bl_scan_kmer_counts", "bl_scan_read_counts", "bl_table_combine", "bl_table_filter",
+    "bl_select_read_counts",
 ]
 
 
@@ -208,6 +209,8 @@ def lib():
     if "BIOLIB_AMD_LIB" not in os.environ or hasattr(L, "bl_table_combine"):
         L.bl_table_combine.argtypes = [vp, vp, vp, u32, u32, u32, u32, C.POINTER(vp), C.POINTER(TableStats)]
         L.bl_table_filter.argtypes = [vp, vp, u32, u32, C.POINTER(vp)]
+    if "BIOLIB_AMD_LIB" not in os.environ or hasattr(L, "bl_select_read_counts"):
+        L.bl_select_read_counts.argtypes = [vp, vp, u64, u64, vp, vp, vp, C.POINTER(u32), C.POINTER(u32), u32, vp, vp]
     _lib = L
     return L
 

@@ -360,6 +360,15 @@ int bl_ctx_device(bl_ctx* c) { return c->device; }
 int bl_ctx_count128_tables(bl_ctx* c) { return c->count128_tables ? 1 : 0; }  // bl_superkmer128.hip
 int bl_ctx_jaccard128_path(bl_ctx* c) { return c->jaccard128_path; }            // bl_setops128.hip
 int bl_ctx_table_prefix_bits(bl_ctx* c) { return c->table_prefix_bits; }        // bl_lookup.hip
+// what bl_read_quantiles.hip needs of a batch
+int bl_batch_describe(const bl_batch* b, bl_ctx** ctx, uint64_t* n_bases, uint64_t* n_seqs, uint64_t* read_len)
+{
+    *ctx = b->ctx;
+    *n_bases = b->n_bases;
+    *n_seqs = b->n_seqs;
+    *read_len = b->read_len;
+    return BL_OK;
+}
 
 // Device scratch that lives with the context (slot 0..7), grown on demand and never shrunk: the set operations and the
 // bucketed counter need gigabytes of temporary space per call, and hipMalloc / hipFree of that size costs more than their

@@ -892,6 +892,93 @@ class Batch:
         out["sum_counts"] = out.pop("xor_pos")
         return rc, out
 
+    def select_read_counts_raw(self, counts, valid, quantiles, out_quantiles, out_n_kmers=None, first=0, n=0, offsets=None):
+        """bl_select_read_counts: `counts` / `valid` are what kmer_counts_raw wrote for the range, `quantiles` a sequence of (num, den)
+        pairs (1 .. 4 of them), `out_quantiles` takes n_seqs * len(quantiles) uint32 words, `out_n_kmers` n_seqs (or None), `offsets` as
+        read_counts_raw.  Synchronous; it waits for the scans in flight itself.  The library checks every argument."""
+        n_q = len(quantiles)
+        num = (C.c_uint32 * max(n_q, 1))(*[int(q[0]) for q in quantiles])
+        den = (C.c_uint32 * max(n_q, 1))(*[int(q[1]) for q in quantiles])
+        check(self._lib.bl_select_read_counts(self.ctx._h, self._h, first, n, _ptr(counts), _ptr(valid), _ptr(offsets), num, den, n_q,
+                                              _ptr(out_quantiles), _ptr(out_n_kmers)))
+
+    # positions per chunk of read_quantiles: 2^26 positions are 320 MB of reused buffers (5 bytes per position), and a scan of that many
+    # takes milliseconds, so that the chunk's two launches and its sync are noise; a larger chunk buys nothing but memory
+    QUANTILE_CHUNK = 1 << 26
+
+    def _sequence_chunks(self, offsets, chunk_positions):
+        """[first, end) ranges that end on sequence boundaries and hold at most chunk_positions (a longer sequence: a range of its own)"""
+        n_bases, limit = self.n_bases, 1 << 31
+        if offsets is None and (self.read_len or self.n_seqs <= 1):
+            length = int(self.read_len) or n_bases
+            if min(length, n_bases) > limit:
+                raise ValueError("a sequence is longer than 2^31 positions: bl_select_read_counts takes a whole sequence in one range")
+            step = max(1, chunk_positions // max(length, 1)) * max(length, 1)
+            return [(b, min(b + step, n_bases)) for b in range(0, n_bases, step)]
+        if offsets is None:
+            raise ValueError("offsets: the batch keeps none and is neither fixed-length nor a single sequence; pass offsets=")
+        if hasattr(offsets, "cpu"):  # a device tensor: the chunks are cut on the host
+            bounds = offsets.cpu().numpy().view(np.uint64)
+        else:
+            bounds = np.ascontiguousarray(offsets, dtype=np.uint64)
+        if len(bounds) != self.n_seqs + 1:
+            raise ValueError("offsets: n_seqs + 1 entries")
+        out, s, last = [], 0, len(bounds) - 1
+        while s < last:
+            e = int(np.searchsorted(bounds, bounds[s] + np.uint64(chunk_positions), side="right")) - 1
+            e = min(max(e, s + 1), last)
+            if int(bounds[e] - bounds[s]) > limit:
+                raise ValueError("a sequence is longer than 2^31 positions: bl_select_read_counts takes a whole sequence in one range")
+            if bounds[e] > bounds[s]:
+                out.append((int(bounds[s]), int(bounds[e])))
+            s = e
+        return out
+
+    def read_quantiles(self, table, k, quantiles=((1, 2),), canonical=False, drop_last=False, offsets=None, chunk_positions=None):
+        """Per-sequence quantiles of the counts kmer_counts looks up — ((1, 2),) is the median k-mer abundance of every read, khmer's
+        get_median_count: (quantiles, n_kmers, result).  quantiles is an int32 device tensor [n_seqs, n_q] holding the uint32 values
+        sorted[min(m - 1, m * num // den)] of the read's m valid k-mers (0 where m = 0), n_kmers an int32 device tensor [n_seqs].  The
+        batch is processed in chunks that end on sequence boundaries (the batch's own host offsets, offsets=, or multiples of read_len):
+        each chunk runs kmer_counts_raw into ONE reused pair of buffers and then the selection, so that the caller never holds five
+        bytes per base of the whole batch.  chunk_positions (default Batch.QUANTILE_CHUNK) bounds a chunk; a longer sequence gets a chunk
+        of its own, one longer than 2^31 positions raises ValueError.  result: the chunks' digests folded — sums added, XOR words XORed —
+        which is kmer_counts's over the whole batch, word for word."""
+        import torch
+
+        quantiles = tuple((int(a), int(b)) for a, b in quantiles)
+        chunk = int(chunk_positions) if chunk_positions else self.QUANTILE_CHUNK
+        if chunk < 1:
+            raise ValueError("chunk_positions must be positive")
+        host_offsets = offsets if offsets is not None else (self.offsets if self.offsets is not None and len(self.offsets) == self.n_seqs + 1 else None)
+        chunks = self._sequence_chunks(host_offsets, chunk)
+        d_offsets = self._device_offsets(offsets)
+        n_seqs, dev = self.n_seqs, self.ctx.torch_device
+        out_q = torch.zeros((max(n_seqs, 1), max(len(quantiles), 1)), dtype=torch.int32, device=dev)
+        out_m = torch.zeros(max(n_seqs, 1), dtype=torch.int32, device=dev)
+        widest = max((e - b for b, e in chunks), default=0)
+        counts = torch.empty(max(widest, 1), dtype=torch.int32, device=dev)
+        valid = torch.empty(max(widest, 1), dtype=torch.uint8, device=dev)
+        self.ctx._inputs_ready()
+        flags = _flags(canonical, drop_last, True)
+        total = dict(count=0, xor_value=0, xor_hash=0, xor_pos=0, aux=0, status=0)
+        if not chunks:  # no position at all: the library still checks the arguments
+            self.select_read_counts_raw(counts, valid, quantiles, out_q, out_m, 0, 0, d_offsets)
+        for b, e in chunks:
+            r = self.kmer_counts_raw(table, k, flags, b, e - b, counts, valid).as_dict()
+            self.select_read_counts_raw(counts, valid, quantiles, out_q, out_m, b, e - b, d_offsets)
+            for word in ("count", "xor_hash", "xor_pos"):  # sums (xor_hash: found, xor_pos: sum_counts)
+                total[word] = (total[word] + r[word]) & (2**64 - 1)
+            for word in ("xor_value", "aux"):
+                total[word] ^= r[word]
+        total["found"] = total.pop("xor_hash")
+        total["sum_counts"] = total.pop("xor_pos")
+        return out_q[:n_seqs], out_m[:n_seqs], total
+
+    def read_medians(self, table, k, canonical=False, drop_last=False, offsets=None, chunk_positions=None):
+        """The median k-mer abundance of every sequence, sorted[m // 2] of its m valid k-mers' counts: an int32 device tensor [n_seqs]
+        holding the uint32 values.  read_quantiles with ((1, 2),)."""
+        return self.read_quantiles(table, k, ((1, 2),), canonical, drop_last, offsets, chunk_positions)[0][:, 0]
+
     def hash_sample128(self, k, seed=0, threshold=2**64 - 1, canonical=False, drop_last=False, first=0, n=0, capacity=None, device=False):
         """k-mers up to k = 64 with hash64_u128(value, seed) < threshold, in position order; values has shape (count, 2) as in kmers128.
         Run again with the count the scan reports when `capacity` (default: the expected number of records) was too small.

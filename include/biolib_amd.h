@@ -521,6 +521,31 @@ enum { BL_READ_COUNTS_INIT = 0, BL_READ_COUNTS_ACCUMULATE = 1 };
 int bl_scan_read_counts(bl_ctx* ctx, const bl_batch* batch, uint64_t first, uint64_t n, uint32_t k, uint32_t flags, const bl_table* table,
                         uint32_t min_count, const uint64_t* d_offsets, uint32_t mode, bl_read_counts* d_records, bl_result* result);
 
+/* Per-sequence quantiles of the k-mer counts — the median k-mer abundance of a read among them — by exact selection on the device.
+ * The one per-read statistic that is not associative and so cannot ride the scan: it is taken from the arrays bl_scan_kmer_counts wrote.
+ *   d_counts[p-first], d_valid[p-first]   what bl_scan_kmer_counts wrote for the range [first, first + n); both required, at any
+ *               element alignment.  The range rules are that call's (n = 0: to the end, at most 2^31 positions).  The call knows nothing
+ *               of k, strand, BL_FLAG_DROP_LAST or the table: a position takes part iff d_valid is non-zero.
+ *   d_offsets   as bl_scan_read_counts: the device copy of the n_seqs + 1 offsets; NULL for a single-sequence or fixed-read-length
+ *               batch, BL_ERR_INVALID on any other.  Trusted for content, not for safety: whatever it holds, no access leaves
+ *               d_counts, d_valid, d_offsets, d_quantiles or d_n_kmers.
+ *   q_num, q_den   HOST arrays of n_q quantiles q_num[j] / q_den[j]; 1 <= n_q <= 4, q_den >= 1, q_num <= q_den
+ *   d_quantiles    bl_batch_n_seqs(batch) rows of n_q words, indexed by sequence
+ *   d_n_kmers      bl_batch_n_seqs(batch) words (may be NULL)
+ * For a sequence with m valid positions, their counts sorted ascending as unsigned 32-bit words (an absent key counts 0):
+ *   d_quantiles[seq * n_q + j] = sorted[min(m - 1, floor(m * q_num[j] / q_den[j]))]   (the product in 64 bits), 0 where m = 0
+ *   d_n_kmers[seq] = m
+ * so (1, 2) is the median sorted[m / 2], (0, 1) the minimum and (1, 1) the maximum.
+ * A sequence is written iff it lies whole inside the range: first <= offsets[i] and offsets[i + 1] <= first + n, empty sequences by
+ * the same rule.  A sequence cut by either end of the range is not touched: a median does not add up across ranges.
+ * The call first waits for the context's scans in flight (a preceding bl_scan_kmer_counts needs no BL_FLAG_SYNC) and returns when the
+ * results are written.  They are exact: bit-reproducible.  An empty range succeeds and writes nothing.
+ * One wave selects inside a sequence of up to 1,024 positions, one workgroup inside a longer one: a whole chromosome as ONE sequence
+ * is correct but served by a single workgroup. */
+int bl_select_read_counts(bl_ctx* ctx, const bl_batch* batch, uint64_t first, uint64_t n, const uint32_t* d_counts, const uint8_t* d_valid,
+                          const uint64_t* d_offsets, const uint32_t* q_num, const uint32_t* q_den, uint32_t n_q, uint32_t* d_quantiles,
+                          uint32_t* d_n_kmers);
+
 /* Count reduction across the GPUs of one node: ctxs[g] is the context of device g (all distinct devices),
  * counters holds n_gpu rows of n 64-bit counters — row g = GPU g's local counts in, the column sums out (in every row).  One
  * ncclAllReduce(sum, uint64) per GPU over RCCL / xGMI, called on RCCL's C API directly (librccl.so.1 is loaded on first use);
