@@ -27,7 +27,7 @@ SYMBOLS = [
     "bl_write_run_u128", "bl_write_vector_u128", "bl_file_count_u128", "bl_read_file_u128_host", "bl_read_file_u128", "bl_merge_runs_u128",
     "bl_table_build_u64", "bl_table_build_u128", "bl_table_destroy", "bl_table_info", "bl_table_arrays", "bl_table_lookup_u64", "bl_table_lookup_u128",
     "bl_table_histogram", "bl_scan_kmer_counts", "bl_scan_read_counts", "bl_table_combine", "bl_table_filter",
-    "bl_select_read_counts",
+    "bl_select_read_counts", "bl_batch_select", "bl_read_spans",
 ]
 
 
@@ -53,6 +53,15 @@ class ReadCountsRecord(C.Structure):
 
 
 READ_COUNTS_INIT, READ_COUNTS_ACCUMULATE = 0, 1
+SELECT_KEEP_EMPTY = 1
+TRIM_NONE, TRIM_PREFIX, TRIM_SUFFIX, TRIM_LONGER = 0, 1, 2, 3
+
+
+class SpanRule(C.Structure):
+    """bl_span_rule: how bl_read_spans turns a read's bl_read_counts record into a span (48 bytes)"""
+    _fields_ = [("trim", C.c_uint32), ("k", C.c_uint32), ("min_len", C.c_uint64), ("min_kmers", C.c_uint32), ("solid_min_num", C.c_uint32),
+                ("solid_min_den", C.c_uint32), ("solid_max_num", C.c_uint32), ("solid_max_den", C.c_uint32), ("stat_lo", C.c_uint32),
+                ("stat_hi", C.c_uint32), ("reserved", C.c_uint32)]
 
 
 class TableStats(C.Structure):
@@ -211,6 +220,9 @@ def lib():
         L.bl_table_filter.argtypes = [vp, vp, u32, u32, C.POINTER(vp)]
     if "BIOLIB_AMD_LIB" not in os.environ or hasattr(L, "bl_select_read_counts"):
         L.bl_select_read_counts.argtypes = [vp, vp, u64, u64, vp, vp, vp, C.POINTER(u32), C.POINTER(u32), u32, vp, vp]
+    if "BIOLIB_AMD_LIB" not in os.environ or hasattr(L, "bl_batch_select"):
+        L.bl_batch_select.argtypes = [vp, vp, vp, vp, u32, C.POINTER(vp), vp, vp, C.POINTER(u64), C.POINTER(u64)]
+        L.bl_read_spans.argtypes = [vp, vp, vp, vp, vp, C.POINTER(SpanRule), vp]
     _lib = L
     return L
 

@@ -687,10 +687,21 @@ class Batch:
         self._h = handle
         self._lib = ctx._lib
         self._keep = None
+        self._d_offsets = None     # read_counts: the device copy, uploaded once (select: written by the library)
+        self._offsets_from_device = False  # select: the host copy is downloaded when it is first asked for
         self.offsets = offsets     # the host offsets the batch was made from (uint64 numpy array), None where it was made without
         self.read_len = read_len   # != 0: made as reads of this length laid end to end
-        self._d_offsets = None     # read_counts: the device copy, uploaded once
         ctx._batches.add(self)
+
+    @property
+    def offsets(self):
+        if self._host_offsets is None and self._offsets_from_device:
+            self._host_offsets = self._d_offsets.cpu().numpy().view(np.uint64).copy()
+        return self._host_offsets
+
+    @offsets.setter
+    def offsets(self, value):
+        self._host_offsets = value
 
     def close(self):
         if getattr(self, "_h", None):
@@ -978,6 +989,98 @@ class Batch:
         """The median k-mer abundance of every sequence, sorted[m // 2] of its m valid k-mers' counts: an int32 device tensor [n_seqs]
         holding the uint32 values.  read_quantiles with ((1, 2),)."""
         return self.read_quantiles(table, k, ((1, 2),), canonical, drop_last, offsets, chunk_positions)[0][:, 0]
+
+    # ---- select and trim: a new batch from per-read spans
+    def select_raw(self, spans, flags=0, offsets=None, out_offsets=None, source_index=None):
+        """bl_batch_select: `spans` holds n_seqs (begin, end) pairs of 64-bit words (16-byte aligned), `offsets` as read_counts_raw,
+        `out_offsets` / `source_index` (or None) take n_seqs + 1 / n_seqs words.  Synchronous; it waits for the scans in flight itself.
+        Returns (handle, n_seqs, n_bases) of the new batch; the library checks every argument."""
+        h, ns, nb = C.c_void_p(), C.c_uint64(), C.c_uint64()
+        check(self._lib.bl_batch_select(self.ctx._h, self._h, _ptr(offsets), _ptr(spans), int(flags), C.byref(h), _ptr(out_offsets), _ptr(source_index),
+                                        C.byref(ns), C.byref(nb)))
+        return h, int(ns.value), int(nb.value)
+
+    def select(self, spans, keep_empty=False, offsets=None):
+        """A new device-resident batch whose sequences are spans of this one's reads (bl_batch_select): (Batch, source_index).
+        spans: an int64 device tensor [n_seqs, 2] of read-relative (begin, end), clamped to the read; a read whose span is empty is
+        dropped, or, with keep_empty, stays as an empty sequence so that sequence i of the result is read i (paired reads stay in
+        step).  source_index: an int64 device tensor, the read every sequence of the result came from.  The new batch keeps its
+        offsets on the device (`.offsets`, the host copy, is downloaded when first asked for) and `.read_len` where all its sequences
+        are equally long, so read_counts and read_quantiles run on it as they are.  offsets: as read_counts."""
+        import torch
+
+        n_seqs = self.n_seqs
+        if not (isinstance(spans, torch.Tensor) and spans.is_cuda and spans.dtype == torch.int64 and spans.is_contiguous() and spans.numel() == 2 * n_seqs):
+            raise ValueError("spans: a contiguous int64 device tensor [n_seqs, 2]")
+        d_offsets = self._device_offsets(offsets)
+        dev = self.ctx.torch_device
+        out_offsets = torch.empty(n_seqs + 1, dtype=torch.int64, device=dev)
+        source_index = torch.empty(max(n_seqs, 1), dtype=torch.int64, device=dev)
+        if n_seqs == 0:
+            spans = torch.zeros((1, 2), dtype=torch.int64, device=dev)  # (the library wants a pointer)
+        self.ctx._inputs_ready()
+        h, n_out, n_bases = self.select_raw(spans, capi.SELECT_KEEP_EMPTY if keep_empty else 0, d_offsets, out_offsets, source_index)
+        d_out = out_offsets[:n_out + 1]
+        fixed = 0  # the library's rule: more than one sequence, all equally long
+        if n_out > 1 and n_bases and n_bases % n_out == 0 and bool((d_out[1:] - d_out[:-1] == n_bases // n_out).all()):
+            fixed = n_bases // n_out
+        b = Batch(self.ctx, h, read_len=fixed)
+        b._d_offsets = d_out
+        b._offsets_from_device = True
+        return b, source_index[:n_out]
+
+    def read_spans_raw(self, records, rule, spans, stat=None, offsets=None):
+        """bl_read_spans: `records` are the whole-batch records of read_counts_raw, `rule` a capi.SpanRule, `spans` takes n_seqs pairs of
+        64-bit words, `stat` (or None) is a 32-bit word per read.  Asynchronous on the context's stream."""
+        check(self._lib.bl_read_spans(self.ctx._h, self._h, _ptr(offsets), _ptr(records), _ptr(stat), C.byref(rule), _ptr(spans)))
+
+    @staticmethod
+    def _fraction(x, default):
+        if x is None:
+            return default
+        if isinstance(x, (tuple, list)):
+            return int(x[0]), int(x[1])
+        from fractions import Fraction
+
+        f = Fraction(x).limit_denominator(1 << 16)
+        return f.numerator, f.denominator
+
+    def read_spans(self, read_counts, k, trim="prefix", min_len=None, min_kmers=0, solid_min=None, solid_max=None, stat=None, stat_range=None, offsets=None):
+        """One span per read from the ReadCounts of a whole-batch read_counts(table, k, min_count) (bl_read_spans): an int64 device
+        tensor [n_seqs, 2] for select.  trim: "none", "prefix" (khmer's trim-low-abund: cut at the first weak k-mer, keeping all of it
+        but its last base), "suffix" (the mirror image) or "longer".  The span is (0, 0) where it is shorter than min_len (default k),
+        the read has fewer than min_kmers valid k-mers, its solid fraction lies outside [solid_min, solid_max] — (num, den) pairs or
+        numbers in [0, 1] — or stat (an int32 device tensor [n_seqs], e.g. read_medians) lies outside stat_range = (lo, hi)."""
+        import torch
+
+        trims = {"none": capi.TRIM_NONE, "prefix": capi.TRIM_PREFIX, "suffix": capi.TRIM_SUFFIX, "longer": capi.TRIM_LONGER}
+        if trim not in trims:
+            raise ValueError("trim: none, prefix, suffix or longer")
+        if read_counts.n_seqs != self.n_seqs:
+            raise ValueError("read_counts holds the records of another batch")
+        rule = capi.SpanRule()
+        rule.trim, rule.k = trims[trim], int(k)
+        rule.min_len = int(k) if min_len is None else int(min_len)
+        rule.min_kmers = int(min_kmers)
+        rule.solid_min_num, rule.solid_min_den = self._fraction(solid_min, (0, 1))
+        rule.solid_max_num, rule.solid_max_den = self._fraction(solid_max, (1, 1))
+        rule.stat_lo, rule.stat_hi = (0, 2**32 - 1) if stat_range is None else (int(stat_range[0]), int(stat_range[1]))
+        if stat is not None:
+            if not (stat.is_cuda and stat.element_size() == 4 and stat.is_contiguous() and stat.numel() == self.n_seqs):
+                raise ValueError("stat: a contiguous 32-bit device tensor of n_seqs entries")
+        spans = torch.zeros((max(self.n_seqs, 1), 2), dtype=torch.int64, device=self.ctx.torch_device)
+        self.ctx._inputs_ready()
+        self.read_spans_raw(read_counts.records, rule, spans, stat, self._device_offsets(offsets))
+        return spans[:self.n_seqs]
+
+    def trim_by_counts(self, table, k, min_count, trim="prefix", min_len=None, min_kmers=0, solid_min=None, solid_max=None, canonical=False,
+                       drop_last=False, keep_empty=False, offsets=None):
+        """Abundance trimming and filtering in one chain on the device: read_counts(table, k, min_count), read_spans, select.
+        (Batch, source_index, ReadCounts): the trimmed reads as a new batch, where each came from, and the source's records."""
+        rc, _ = self.read_counts(table, k, min_count, canonical, drop_last, offsets=offsets)
+        spans = self.read_spans(rc, k, trim, min_len, min_kmers, solid_min, solid_max, offsets=offsets)
+        out, source_index = self.select(spans, keep_empty, offsets=offsets)
+        return out, source_index, rc
 
     def hash_sample128(self, k, seed=0, threshold=2**64 - 1, canonical=False, drop_last=False, first=0, n=0, capacity=None, device=False):
         """k-mers up to k = 64 with hash64_u128(value, seed) < threshold, in position order; values has shape (count, 2) as in kmers128.

@@ -546,6 +546,61 @@ int bl_select_read_counts(bl_ctx* ctx, const bl_batch* batch, uint64_t first, ui
                           const uint64_t* d_offsets, const uint32_t* q_num, const uint32_t* q_den, uint32_t n_q, uint32_t* d_quantiles,
                           uint32_t* d_n_kmers);
 
+/* Select and trim reads on the device: a NEW batch whose sequences are per-read spans of `batch` — whole-read filtering, trimming at a
+ * weak k-mer, coverage binning — at copy speed, without the bases or an index of them leaving the device.  The result is an ordinary
+ * batch of the same context for every scan; the source batch is not modified.
+ *   d_offsets   as bl_scan_read_counts: the device copy of the source's n_seqs + 1 offsets; NULL for a single-sequence or a
+ *               fixed-read-length batch, BL_ERR_INVALID on any other
+ *   d_spans     bl_batch_n_seqs(batch) pairs, d_spans[2i] = begin, d_spans[2i+1] = end, read-relative; required and 16-byte aligned
+ *               (BL_ERR_INVALID otherwise).  With L the read's length the span is [min(begin, L), min(end, L)), empty when that end <=
+ *               that begin.  A read with an empty span is dropped.
+ *   flags       BL_SELECT_KEEP_EMPTY: a dropped read stays in the result as an empty sequence, so that the result has the source's
+ *               n_seqs and sequence i of the result is read i of the source (mates of paired reads stay aligned).  Without it the kept
+ *               reads are compacted in source order.  Any other bit: BL_ERR_INVALID.
+ *   *out        a batch the library owns (bl_batch_destroy): the kept spans concatenated, every byte copied verbatim (non-ACGT bytes, 0
+ *               and 255 included), origin 0.  It is a fixed-length batch where it holds more than one sequence and all are equally
+ *               long (the text parser's rule: whole-read filtering of 150-bp reads stays on the read-tiled kernels); otherwise it
+ *               carries start bits built from the new offsets.  With every read dropped it is a valid batch of 0 bases: 0 sequences,
+ *               or n_seqs empty ones under BL_SELECT_KEEP_EMPTY.
+ *   d_out_offsets    (nullable) takes the result's n_seqs_out + 1 offsets; room for the SOURCE's n_seqs + 1 entries
+ *   d_source_index   (nullable) takes n_seqs_out entries, the source sequence of every result sequence (the identity under
+ *                    BL_SELECT_KEEP_EMPTY); room for the source's n_seqs entries.  The hook for names and qualities kept on the host.
+ *   n_seqs_out, n_bases_out   (nullable) host words
+ * Synchronous (the total is needed on the host to allocate); the call first waits for the context's scans in flight, so spans made by
+ * bl_read_spans behind a bl_scan_read_counts need no sync.  Temporaries come from the context's scratch.
+ * Offsets and spans are trusted for content, not for safety: every offset is clamped to [0, n_bases] and offsets[i + 1] < offsets[i]
+ * is a read of length 0, so whatever the two arrays hold, no access leaves the batch's bases [0, n_bases), d_offsets[0 .. n_seqs],
+ * d_spans or the outputs.  No byte at or behind n_bases of the source is read (a bl_batch_from_device batch has no slack).
+ * BL_ERR_INVALID with a message, nothing launched: NULL ctx, batch, out or d_spans, a batch of another context, misaligned d_spans,
+ * unknown flag bits. */
+enum { BL_SELECT_KEEP_EMPTY = 1u << 0 };
+int bl_batch_select(bl_ctx* ctx, const bl_batch* batch, const uint64_t* d_offsets, const uint64_t* d_spans, uint32_t flags,
+                    bl_batch** out, uint64_t* d_out_offsets, uint64_t* d_source_index, uint64_t* n_seqs_out, uint64_t* n_bases_out);
+
+/* The decision step in front of bl_batch_select: one span per read from the WHOLE-read records of bl_scan_read_counts (a scan of the
+ * whole batch with the same k).  L is the read's length; a read has no weak k-mer when weak_begin == UINT64_MAX.
+ *   no weak k-mer, or BL_TRIM_NONE   [0, L)
+ *   BL_TRIM_PREFIX                   [0, min(L, weak_begin + k - 1)): khmer's cut — all of the first weak k-mer except its last base
+ *   BL_TRIM_SUFFIX                   [min(L, weak_end), L): the mirror image
+ *   BL_TRIM_LONGER                   the longer of the two, PREFIX on a tie
+ * The span is (0, 0) where it is shorter than min_len or a keep condition fails: n_kmers < min_kmers, the solid fraction outside
+ * [solid_min, solid_max], or (with d_stat) d_stat[i] outside [stat_lo, stat_hi].  d_stat is any per-read 32-bit word, e.g. a column
+ * of bl_select_read_counts's quantiles (n_q = 1) for coverage binning by median.
+ * d_offsets as above; d_records and d_spans 16-byte aligned, bl_batch_n_seqs(batch) entries each.  Asynchronous on the context's
+ * stream, like the scans.  BL_ERR_INVALID for a NULL or misaligned argument, a bad trim, k, fraction or reserved. */
+enum { BL_TRIM_NONE = 0, BL_TRIM_PREFIX = 1, BL_TRIM_SUFFIX = 2, BL_TRIM_LONGER = 3 };
+typedef struct bl_span_rule {
+    uint32_t trim, k;     /* k of the scan that made the records, 1..64 */
+    uint64_t min_len;     /* a span shorter than this becomes empty */
+    uint32_t min_kmers;   /* n_kmers below this: empty */
+    uint32_t solid_min_num, solid_min_den, solid_max_num, solid_max_den; /* keep iff n_solid*min_den >= n_kmers*min_num and
+                             n_solid*max_den <= n_kmers*max_num, products in 64 bits; den >= 1, num <= den; (0,1) and (1,1): no condition */
+    uint32_t stat_lo, stat_hi; /* with d_stat: keep iff stat_lo <= d_stat[i] <= stat_hi */
+    uint32_t reserved;    /* 0 */
+} bl_span_rule;
+int bl_read_spans(bl_ctx* ctx, const bl_batch* batch, const uint64_t* d_offsets, const bl_read_counts* d_records, const uint32_t* d_stat /* nullable */,
+                  const bl_span_rule* rule, uint64_t* d_spans);
+
 /* Count reduction across the GPUs of one node: ctxs[g] is the context of device g (all distinct devices),
  * counters holds n_gpu rows of n 64-bit counters — row g = GPU g's local counts in, the column sums out (in every row).  One
  * ncclAllReduce(sum, uint64) per GPU over RCCL / xGMI, called on RCCL's C API directly (librccl.so.1 is loaded on first use);
