@@ -28,8 +28,6 @@ namespace bllk {
 namespace {
 
 typedef unsigned long long ull;
-constexpr int LTPB = 256;             // threads per workgroup of the table kernels
-constexpr int HIST_LDS_BINS = 8192;   // bins a workgroup keeps in LDS (32 KB)
 
 // OR of all low words into out[0], of all high words into out[1] (one-word keys: every word is a low word)
 __global__ __launch_bounds__(LTPB) void or_reduce_kernel(const uint64_t* __restrict__ keys, ull n, uint32_t key_words, ull* out)
@@ -150,7 +148,7 @@ struct SatAdd {
 int hip_rc(hipError_t e) { return bl_set_error(e == hipErrorOutOfMemory ? BL_ERR_OOM : BL_ERR_HIP, hipGetErrorString(e)); }
 bool misaligned(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) != 0; }
 size_t round16(size_t b) { return (b + 15) & ~(size_t)15; }
-unsigned blocks_for(ull n) { return (unsigned)((n + LTPB - 1) / LTPB < 256 * 16 ? (n + LTPB - 1) / LTPB : 256 * 16); }
+unsigned blocks_for(ull n) { return (unsigned)((n + LTPB - 1) / LTPB < TABLE_GRID_MAX ? (n + LTPB - 1) / LTPB : TABLE_GRID_MAX); }
 
 // KeyT: unsigned long long or __uint128_t — what rocPRIM sorts; the bytes are the table's
 template <typename KeyT>
@@ -249,7 +247,7 @@ int lookup(bl_ctx* ctx, const bl_table* t, const uint64_t* d_queries, uint64_t n
     if (e != hipSuccess) return hip_rc(e);
     hipStream_t s = bl_ctx_stream(ctx);
     const ull groups = (n + (ull)LTPB * G - 1) / ((ull)LTPB * G);
-    hipLaunchKernelGGL(lookup_kernel, dim3((unsigned)(groups < 256 * 32 ? groups : 256 * 32)), dim3(LTPB), 0, s, t->view, d_queries, (ull)n, d_out);
+    hipLaunchKernelGGL(lookup_kernel, dim3((unsigned)(groups < LOOKUP_GRID_MAX ? groups : LOOKUP_GRID_MAX)), dim3(LTPB), 0, s, t->view, d_queries, (ull)n, d_out);
     e = hipGetLastError();
     if (e == hipSuccess) e = hipStreamSynchronize(s);
     return e == hipSuccess ? BL_OK : hip_rc(e);
@@ -324,9 +322,9 @@ int bl_table_histogram(bl_ctx* ctx, const bl_table* t, uint64_t* hist, uint32_t 
     if (e == hipSuccess) {
         if (n_bins <= (uint32_t)HIST_LDS_BINS) {
             // a workgroup clears and flushes n_bins words: give it at least that many keys
-            const ull per = n_bins > 16 * LTPB ? n_bins : 16 * LTPB;
+            const ull per = n_bins > HIST_LDS_KEYS_MIN ? n_bins : HIST_LDS_KEYS_MIN;
             const ull wg = (n + per - 1) / per;
-            hipLaunchKernelGGL(histogram_lds_kernel, dim3((unsigned)(wg < 256 * 8 ? wg : 256 * 8)), dim3(LTPB), 0, s, t->view.counts, n, n_bins, d_hist);
+            hipLaunchKernelGGL(histogram_lds_kernel, dim3((unsigned)(wg < HIST_LDS_GRID_MAX ? wg : HIST_LDS_GRID_MAX)), dim3(LTPB), 0, s, t->view.counts, n, n_bins, d_hist);
         } else {
             hipLaunchKernelGGL(histogram_global_kernel, dim3(blocks_for(n)), dim3(LTPB), 0, s, t->view.counts, n, n_bins, d_hist);
         }

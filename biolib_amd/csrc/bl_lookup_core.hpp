@@ -22,6 +22,14 @@ namespace bllk {
 constexpr int MAX_PREFIX_BITS = 24;
 constexpr int G = 4;  // searches in flight per lane: the scan's 16 positions go in four groups (its position loop stays rolled over the groups)
 
+// The launch shapes of the table kernels (bl_lookup.hip).  Every kernel strides over its input from a capped grid.
+constexpr int LTPB = 256;                    // threads per workgroup of the table kernels
+constexpr int HIST_LDS_BINS = 8192;          // bins a workgroup keeps in LDS (32 KB)
+constexpr int HIST_LDS_KEYS_MIN = 16 * LTPB; // keys a workgroup of the LDS histogram gets at least (and at least n_bins)
+constexpr int LOOKUP_GRID_MAX = 256 * 32;    // workgroups of lookup_kernel at most, LTPB * G queries each per step
+constexpr int HIST_LDS_GRID_MAX = 256 * 8;   // workgroups of histogram_lds_kernel at most
+constexpr int TABLE_GRID_MAX = 256 * 16;     // workgroups of the one-thread-per-key kernels at most (blocks_for): OR reduction, global histogram
+
 struct alignas(16) Key2 {
     uint64_t lo, hi;
 };

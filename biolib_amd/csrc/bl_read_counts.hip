@@ -11,8 +11,6 @@ namespace blrc {
 
 namespace {
 
-constexpr int ITPB = 256;  // threads per workgroup of the identity fill
-
 struct ReadCountShared {
     uint32_t codes[bl::NCHUNK_POS];
     uint32_t flags[bl::NCHUNK_POS];
@@ -84,7 +82,7 @@ __global__ __launch_bounds__(bl::TPB) void read_counts_kernel(const ReadCountPar
 hipError_t launch_read_counts_init(const ReadCountParams& p, hipStream_t stream)
 {
     const uint64_t wg = (p.n_seqs + ITPB - 1) / ITPB;
-    hipLaunchKernelGGL(read_counts_init_kernel, dim3((unsigned)(wg < 2048 ? wg : 2048)), dim3(ITPB), 0, stream, p);
+    hipLaunchKernelGGL(read_counts_init_kernel, dim3((unsigned)(wg < (uint64_t)INIT_GRID_MAX ? wg : (uint64_t)INIT_GRID_MAX)), dim3(ITPB), 0, stream, p);
     return hipGetLastError();
 }
 

@@ -297,11 +297,11 @@ extern "C" int bl_select_read_counts(bl_ctx* ctx, const bl_batch* batch, uint64_
     e = hipMemsetAsync(p.long_count, 0, sizeof(unsigned long long), s);
     if (e != hipSuccess) return hip_rc(e);
     const uint64_t wave_wgs = (n_seqs + WG_TPB / 64 - 1) / (WG_TPB / 64);
-    hipLaunchKernelGGL(select_wave_kernel, dim3((unsigned)(wave_wgs < 2048 ? wave_wgs : 2048)), dim3(WG_TPB), 0, s, p);
+    hipLaunchKernelGGL(select_wave_kernel, dim3((unsigned)(wave_wgs < (uint64_t)WAVE_GRID_MAX ? wave_wgs : (uint64_t)WAVE_GRID_MAX)), dim3(WG_TPB), 0, s, p);
     e = hipGetLastError();
     if (e != hipSuccess) return bl_set_error(BL_ERR_HIP, (std::string("select_wave_kernel: ") + hipGetErrorString(e)).c_str());
     if (p.long_cap) {
-        hipLaunchKernelGGL(select_wg_kernel, dim3((unsigned)(p.long_cap < 1024 ? p.long_cap : 1024)), dim3(WG_TPB), 0, s, p);
+        hipLaunchKernelGGL(select_wg_kernel, dim3((unsigned)(p.long_cap < (uint64_t)WG_GRID_MAX ? p.long_cap : (uint64_t)WG_GRID_MAX)), dim3(WG_TPB), 0, s, p);
         e = hipGetLastError();
         if (e != hipSuccess) return bl_set_error(BL_ERR_HIP, (std::string("select_wg_kernel: ") + hipGetErrorString(e)).c_str());
     }

@@ -29,6 +29,8 @@ constexpr int WAVE_SLOTS_SHORT = 4;            // the wave form's body for seque
 constexpr int WG_TPB = 256;                    // threads of a workgroup, both kernels
 constexpr int WG_UNROLL = 4;                   // loads a thread of the workgroup form has in flight
 constexpr int WG_CHUNK = WG_TPB * WG_UNROLL;   // positions per step of a workgroup-form pass
+constexpr int WAVE_GRID_MAX = 2048;            // workgroups of the wave kernel at most (WG_TPB / 64 waves each): a wave strides over the sequences
+constexpr int WG_GRID_MAX = 1024;              // workgroups of the workgroup kernel at most: a workgroup strides over the listed sequences
 
 struct SelectParams {
     const uint32_t* counts;   // [n]: position p of the batch at p - first

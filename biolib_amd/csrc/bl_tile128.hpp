@@ -140,7 +140,8 @@ __device__ __forceinline__ void fold_digest128(unsigned long long* shards, unsig
 }
 
 // 2,048 workgroups striding over the tiles, as bl_scan_kmers launches kmer_kernel
-inline int grid_for(int n_tiles) { return n_tiles < 256 * 8 ? n_tiles : 256 * 8; }
+constexpr int TILE_GRID_MAX = 256 * 8;
+inline int grid_for(int n_tiles) { return n_tiles < TILE_GRID_MAX ? n_tiles : TILE_GRID_MAX; }
 
 // a kernel that takes one params struct, over n_tiles tiles
 template <typename Params>

@@ -165,6 +165,173 @@ def variants():
     return out
 
 
+# ---- bl_batch_select past the sizes of the cases above: the depth of the wave's search, the switch between its two lookups, runs of
+# empty kept sequences, totals around a wave's bytes.  The two helpers are written from the prose of bl_select_core.hpp ("The gather is
+# output-centric ..", "The wave's search"), not from the kernel.
+
+def _wave_bytes():
+    import os
+    import re
+
+    source = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "biolib_amd", "csrc", "bl_select_core.hpp")
+    with open(source) as f:
+        text = f.read()
+    names = {}
+    for name, expr in re.findall(r"constexpr\s+int\s+(\w+)\s*=\s*([^;]+);", text):
+        names[name] = int(eval(expr, {"__builtins__": {}}, dict(names)))
+    assert "WAVE_BYTES" in names, f"WAVE_BYTES not found in {source}"
+    return names["WAVE_BYTES"]
+
+
+WAVE_BYTES = _wave_bytes()  # output bytes of a wave of the gather
+DEPTH_N_OUT = (1, 2, 63, 64, 65, 66, 4095, 4096, 4097, 4098, 262144, 262145, 262146)
+EMPTY_RUNS = (64, 65, 66, 70, 130, 4097)
+
+
+def search_depth(n_out):
+    """steps of the 64-ary search over [0, n_out): every step narrows an interval of w entries to at most ceil(w / 64)"""
+    depth, w = 0, int(n_out)
+    while w > 1:
+        w = (w + 63) // 64
+        depth += 1
+    return depth
+
+
+def wave_inside(offsets):
+    """per wave of the gather: the number of the 64 offsets after the wave's first sequence that are at or below its last byte.  The
+    first sequence is the LAST one whose offset is <= the wave's first byte; entry n_out (the total) is the last offset there is.
+    Below 64 the wave keeps its sequences in registers, at 64 it looks them up in memory."""
+    offsets = np.asarray(offsets, np.uint64).astype(np.int64)
+    n_out, total = len(offsets) - 1, int(offsets[-1])
+    first = np.arange(0, total, WAVE_BYTES, dtype=np.int64)
+    last = np.minimum(first + WAVE_BYTES - 1, total - 1)
+    lo = np.searchsorted(offsets[:n_out], first, side="right") - 1
+    upto = np.searchsorted(offsets, last, side="right")  # entries 0 .. upto - 1 are <= the last byte
+    return np.clip(upto - (lo + 1), 0, 64)
+
+
+def wave_paths(offsets):
+    """(waves that keep their sequences in registers, waves that look them up in memory)"""
+    inside = wave_inside(offsets)
+    return int((inside < 64).sum()), int((inside == 64).sum())
+
+
+def _ragged(lengths):
+    return np.concatenate([[0], np.cumsum(np.asarray(lengths, np.int64))]).astype(np.uint64)
+
+
+def _empty_runs_lengths():
+    """result lengths, 0 = an empty kept sequence: a run at the result's start, runs whose shared offset is a wave's first byte, runs in
+    the middle of a wave, a run behind the last byte; every length of EMPTY_RUNS occurs"""
+    W = WAVE_BYTES
+    out = [0] * 70 + [W - 100, 100]                      # 70 at byte 0 (the start, and wave 0's first byte); then up to byte W
+    out += [0] * 65 + [500] + [0] * 64 + [300] + [0] * 66 + [200]  # 65 at byte W: wave 1's first byte; 64 and 66 inside wave 1
+    out += [7] * 40 + [0] * 4097 + [33]                   # 4,097 in the middle of wave 1
+    at = sum(out)
+    out += [3 * W - at]                                   # pad onto a later wave boundary ..
+    out += [0] * 130 + [W // 2] + [0] * 70 + [W // 2 + 11]  # .. 130 at wave 3's first byte, 70 in the middle of it
+    out += [0] * 64                                       # behind the last byte
+    assert at < 3 * W and sorted(set(_runs(out))) == sorted(EMPTY_RUNS)
+    return out
+
+
+def _runs(lengths):
+    runs, n = [], 0
+    for x in list(lengths) + [1]:
+        if x == 0:
+            n += 1
+        elif n:
+            runs.append(n)
+            n = 0
+    return runs
+
+
+def scale_variants():
+    """{name: dict(bases, offs | None, read_len, spans, keep_empty)} as variants()"""
+    return _scale_variants()
+
+
+def _memo(f):
+    cache = []
+
+    def g():
+        if not cache:
+            cache.append(f())
+        return cache[0]
+    return g
+
+
+@_memo
+def _scale_variants():
+    rng = np.random.default_rng(20263)
+    out = {}
+    # depth_N: n_out = N fixed-length reads of 6 bases, spans (1, 1 + i % 6), empty ones kept: one sequence in six is empty
+    for n in DEPTH_N_OUT:
+        i = np.arange(n, dtype=np.uint64)
+        spans = np.stack([np.ones(n, np.uint64), np.uint64(1) + i % np.uint64(6)], axis=1)
+        out[f"depth_{n}"] = dict(bases=special_bytes(rng, 6 * n), offs=None, read_len=6 if n > 1 else 0, spans=spans, keep_empty=True)
+    out[f"depth_{DEPTH_N_OUT[-1]}_dropped"] = dict(out[f"depth_{DEPTH_N_OUT[-1]}"], keep_empty=False)
+    # switch: 62, 63 and 64 of a wave's 64 lane offsets at or below its last byte
+    lengths = np.random.default_rng(5).integers(60, 70, 3000)
+    whole = lambda n: np.tile(np.array([[0, U64]], np.uint64), (n, 1))
+    out["switch"] = dict(bases=special_bytes(rng, int(lengths.sum())), offs=_ragged(lengths), read_len=0, spans=whole(3000), keep_empty=False)
+    for first in (0, 1):  # 64-byte reads behind a first read of 0 bytes (63 in every full wave) and of 1 byte (64: the memory path)
+        lengths = [first] + [64] * 300
+        out[f"switch_first{first}"] = dict(bases=special_bytes(rng, sum(lengths)), offs=_ragged(lengths), read_len=0, spans=whole(301), keep_empty=True)
+    # empty_runs: a source read of 3 bases with the span (1, 1) per empty sequence
+    lengths = _empty_runs_lengths()
+    src = [x if x else 3 for x in lengths]
+    spans = np.array([(0, x) if x else (1, 1) for x in lengths], np.uint64)
+    out["empty_runs"] = dict(bases=special_bytes(rng, sum(src)), offs=_ragged(src), read_len=0, spans=spans, keep_empty=True)
+    # totals around a wave's bytes: from a single sequence and from 7-byte sequences (the last one cut)
+    W = WAVE_BYTES
+    for total in (W - 1, W, W + 1, 3 * W, 3 * W + 16):
+        out[f"total_{total}_single"] = dict(bases=special_bytes(rng, total + 10), offs=None, read_len=0, spans=np.array([[5, 5 + total]], np.uint64), keep_empty=False)
+        n = (total + 6) // 7
+        spans = np.tile(np.array([[0, 7]], np.uint64), (n, 1))
+        spans[-1, 1] = total - 7 * (n - 1)
+        out[f"total_{total}_sevens"] = dict(bases=special_bytes(rng, 7 * n), offs=None, read_len=7, spans=spans, keep_empty=False)
+    return out
+
+
+def scale_self_check(name, v, m):
+    """a scale variant holds what its name promises; m: the model's result"""
+    offsets = m["offsets"]
+    inside = wave_inside(offsets)
+    if name.startswith("depth_"):
+        n = int(name.split("_")[1])
+        if name.endswith("_dropped"):
+            assert m["n_seqs"] == n - (n + 5) // 6 and search_depth(m["n_seqs"]) == 3
+        else:
+            assert m["n_seqs"] == n and int((np.diff(offsets.astype(np.int64)) == 0).sum()) == (n + 5) // 6
+    if name == "switch":
+        assert {62, 63, 64} <= set(inside.tolist()), sorted(set(inside.tolist()))
+    if name == "switch_first0":
+        assert set(inside[:-1].tolist()) == {63}
+    if name == "switch_first1":
+        assert set(inside[:-1].tolist()) == {64} and len(inside) >= 4 and inside[-1] < 64
+    if name == "empty_runs":
+        lens = np.diff(offsets.astype(np.int64))
+        assert sorted(set(_runs(lens))) == sorted(EMPTY_RUNS)
+        assert lens[0] == 0 and lens[-1] == 0 and int(offsets[-65]) == m["n_bases"], "a run at the start and one behind the last byte"
+        shared = 0
+        for w in range(0, m["n_bases"], WAVE_BYTES):
+            at = np.nonzero(offsets[:-1] == np.uint64(w))[0]
+            if len(at) > 64:
+                shared += 1
+                holder = int(at[-1])  # the last sequence whose offset is the wave's first byte holds that byte
+                assert lens[holder] > 0 and (lens[at[:-1]] == 0).all() and int(m["source_index"][holder]) == holder
+        assert shared >= 3, "waves that start at an offset more than 64 sequences share"
+        assert (inside == 64).any() and (inside < 64).any()
+    if name.startswith("total_"):
+        assert m["n_bases"] == int(name.split("_")[1])
+    return inside
+
+
+def scale_depths():
+    return {n: search_depth(n) for n in DEPTH_N_OUT}
+
+
 def variant_offsets(v):
     """the offsets the model cuts a variant's source by"""
     if v["offs"] is not None:

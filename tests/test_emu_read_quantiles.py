@@ -119,3 +119,18 @@ def test_wrong_offsets_end_clean(exe, tmp_path, batch):
         for first, n in ((0, 0), (4321, 20_000)):
             got = run(exe, tmp_path, b["counts"], b["valid"], bad, n_seqs, first, n, QC.QUANTILES["ends"])
             assert got[0].shape == (n_seqs, 4)
+
+
+@pytest.mark.parametrize("kind", ("alternating", "sawtooth"))
+def test_overlapping_long_spans_end_clean(exe, tmp_path, batch, kind):
+    """wrong offsets whose passing spans overlap: the whole batch as every second span, and more long spans than the list of long
+    sequences holds (the surplus is dropped).  Clean under the sanitizers, and every row is the guard or the model's answer for its span."""
+    import scale_cases as S
+
+    b, q = batch, QC.QUANTILES["ends"]
+    n_seqs, n = len(b["offs"]) - 1, len(b["counts"])
+    bad = S.alternating_offsets(b) if kind == "alternating" else S.sawtooth_offsets(b)
+    for grid in (1, 3):
+        got = run(exe, tmp_path, b["counts"], b["valid"], bad, n_seqs, 0, 0, q, grid=grid)
+        written, long_written = S.check_rows_under_wrong_offsets(b, bad, 0, n, q, got[0], got[1])
+        assert long_written <= S.long_cap(n, n_seqs)

@@ -87,6 +87,24 @@ def test_variants(exe, tmp_path, name):
         assert np.array_equal(got["source_index"], np.arange(len(v["spans"]), dtype=np.uint64))
 
 
+@pytest.mark.parametrize("name", sorted(SC.scale_variants()))
+def test_scale_variants(exe, tmp_path, name):
+    """search depths 0 .. 4, the switch between the two lookups at 62, 63 and 64 lane offsets, runs of 64 and more empty kept sequences,
+    totals around a wave's bytes: the result byte for byte, and the lookup every wave took as the header's prose says it must"""
+    v = SC.scale_variants()[name]
+    want = SC.expected(v)
+    SC.scale_self_check(name, v, want)
+    got = run_select(exe, tmp_path, v["bases"], v["offs"], v["spans"], v["read_len"], v["keep_empty"])
+    same(got, want, None, name)
+    assert got["paths"] == SC.wave_paths(want["offsets"]), (name, "register waves, memory waves")
+    if name in ("switch", "empty_runs"):
+        assert got["paths"][0] > 0 and got["paths"][1] > 0, "both kinds of wave"
+    if name == "switch_first0":
+        assert got["paths"][1] == 0
+    if name == "switch_first1":
+        assert got["paths"] == (1, len(SC.wave_inside(want["offsets"])) - 1), "the last, partial wave alone keeps its sequences in registers"
+
+
 def test_given_offsets_equal_null_offsets(exe, tmp_path):
     """a fixed-length and a single-sequence source give the same result with their offsets spelled out"""
     for name in ("fixed_source", "single_sequence", "result_fixed"):

@@ -383,3 +383,63 @@ def test_count_then_table_then_kmer_counts(ctx, k, m):
     assert int(hist.sum()) == len(uniq) and np.array_equal(hist, np.bincount(cnt, minlength=256).astype(np.uint64)) and hist[0] == 0
     t.close()
     b.close()
+
+
+# ---- past the grid caps (scale_cases.py): the stride loops of lookup_kernel, histogram_lds_kernel and histogram_global_kernel
+
+def closed_form_table(ctx, key_words):
+    """8,392,705 keys in closed form (a bijection of the index: distinct), counts from a seeded generator with every histogram edge"""
+    import torch
+
+    import scale_cases as S
+
+    n = S.table_size()
+    keys = S.keys_of(np.arange(n, dtype=np.uint64), key_words)
+    t = ctx.count_table(torch.from_numpy(keys.view(np.int64)).cuda(), torch.from_numpy(S.table_counts().copy().view(np.int32)).cuda(),
+                        key_bits=S.KEY_BITS_1 if key_words == 1 else S.KEY_BITS_2)
+    assert t.n_distinct == n, "the keys are distinct"
+    return t
+
+
+@pytest.fixture(scope="module")
+def big_table(ctx):
+    t = closed_form_table(ctx, 1)
+    yield t
+    t.close()
+
+
+def check_lookup_past_the_grid_cap(t, key_words):
+    import torch
+
+    import scale_cases as S
+
+    idx = S.query_indices()
+    nq = len(idx)
+    assert nq > S.CAPS["LOOKUP_GRID_MAX"] * S.CAPS["LTPB"] * S.CAPS["G"]
+    q = torch.from_numpy(S.keys_of(idx, key_words).view(np.int64)).cuda()
+    got = host_u32(t.lookup(q))
+    want = S.expected_lookup()
+    bad = np.nonzero(got != want)[0]
+    assert len(bad) == 0, ("first wrong queries", bad[:8].tolist(), got[bad[:8]].tolist(), want[bad[:8]].tolist(), "of", nq)
+
+
+def test_lookup_past_the_grid_cap_one_word(big_table):
+    check_lookup_past_the_grid_cap(big_table, 1)
+
+
+def test_lookup_past_the_grid_cap_two_words(ctx):
+    t = closed_form_table(ctx, 2)
+    check_lookup_past_the_grid_cap(t, 2)
+    t.close()
+
+
+@pytest.mark.parametrize("n_bins", (1, 2, 4096, 8192, 8193, 65536))
+def test_histogram_past_the_grid_caps(big_table, n_bins):
+    """n_bins up to 4,096: the LDS kernel at its grid cap; 8,192: its largest; above: the global kernel at its grid cap"""
+    import scale_cases as S
+
+    assert n_bins in S.HIST_BINS
+    want = S.expected_histogram(n_bins)
+    got = big_table.histogram(n_bins)
+    bad = np.nonzero(got != want)[0]
+    assert len(bad) == 0 and int(got.sum()) == S.table_size(), ("first wrong bins", bad[:8].tolist(), got[bad[:8]].tolist(), want[bad[:8]].tolist())

@@ -264,3 +264,77 @@ def test_refusals_and_empty_range(ctx, cases):
         big.read_quantiles(t, 31)
     t.close()
     big.close()
+
+
+# ---- past both grid caps (scale_cases.py): a wave's second sequence, a workgroup's second, third and fourth long sequence
+
+@pytest.fixture(scope="module")
+def tiled(ctx):
+    """the model's batch laid end to end 140 times: 8,400 sequences (the wave kernel has 8,192 waves), 3,220 of them long (the workgroup
+    kernel has 1,024 workgroups, which take the list in the order the wave kernel's atomic handed it out)"""
+    import scale_cases as S
+
+    qc = S.quantile_case()
+    print(S.self_check_quantiles(qc))
+    batch = ctx.upload(np.full(len(qc["counts"]), ord("A"), np.uint8), qc["offs"])
+    assert batch.n_seqs == len(qc["offs"]) - 1
+    yield qc, batch
+    batch.close()
+
+
+@pytest.mark.parametrize("qname", sorted(QC.QUANTILES))
+def test_tiled_batch_past_both_grid_caps(tiled, qname):
+    import scale_cases as S
+
+    qc, batch = tiled
+    q = QC.QUANTILES[qname]
+    want = S.expected_quantiles(qc, 0, len(qc["counts"]), q)
+    assert want[2].all()
+    got = select(batch, qc, 0, 0, q)
+    same(qc, got, want[:2], qname)
+    again = select(batch, qc, 0, 0, q)
+    assert np.array_equal(got[0], again[0]) and np.array_equal(got[1], again[1]), "two runs give the same bits"
+
+
+def test_tiled_batch_range_from_a_boundary_into_a_long_sequence(tiled):
+    import scale_cases as S
+
+    qc, batch = tiled
+    q = QC.QUANTILES["ends"]
+    first, n = S.cut_range(qc)
+    want = S.expected_quantiles(qc, first, first + n, q)
+    assert first > 0 and first in qc["offs"].tolist() and S.CAPS["WG_GRID_MAX"] < int(want[2].sum()) < len(want[2])
+    got = select(batch, qc, first, n, q)
+    same(qc, got, want[:2], "cut")
+    again = select(batch, qc, first, n, q)
+    assert np.array_equal(got[0], again[0]) and np.array_equal(got[1], again[1]), "two runs give the same bits"
+
+
+@pytest.mark.parametrize("kind", ("shuffled1", "shuffled2", "shuffled3", "alternating", "sawtooth"))
+def test_wrong_offsets_on_the_device(cases, kind):
+    """The contract fixes no set of visited sequences where the offsets are wrong, so the property is asserted: a row is all guard, or
+    the model's answer for its raw span, which then lies inside the range; nothing else is written and no source array changes."""
+    import torch
+
+    import scale_cases as S
+
+    b, batch = cases
+    n = len(b["counts"])
+    if kind.startswith("shuffled"):
+        bad = QC.wrong_offsets(b["offs"], np.random.default_rng(int(kind[-1])))
+    else:
+        bad = S.alternating_offsets(b) if kind == "alternating" else S.sawtooth_offsets(b)
+    q = QC.QUANTILES["ends"]
+    n_seqs = len(bad) - 1
+    counts, valid = dev(b["counts"], torch.int32), dev(b["valid"], torch.uint8)
+    offs = torch.from_numpy(bad.view(np.int64)).cuda()
+    out_q, out_m = guards(n_seqs * len(q)), guards(n_seqs)
+    torch.cuda.synchronize()
+    batch.select_read_counts_raw(counts, valid, q, out_q, out_m, 0, 0, offs)
+    got_q, got_m = host(out_q), host(out_m)
+    assert (got_q[n_seqs * len(q):] == QC.GUARD).all() and (got_m[n_seqs:] == QC.GUARD).all(), "written behind an output"
+    written, long_written = S.check_rows_under_wrong_offsets(b, bad, 0, n, q, got_q[:n_seqs * len(q)].reshape(n_seqs, len(q)), got_m[:n_seqs])
+    print(kind, dict(rows_written=written, long_rows_written=long_written, long_cap=S.long_cap(n, n_seqs)))
+    assert long_written <= S.long_cap(n, n_seqs), "more long sequences answered than the list holds"
+    assert np.array_equal(host(counts), b["counts"]) and np.array_equal(valid.cpu().numpy(), b["valid"]), "a source array changed"
+    assert np.array_equal(offs.cpu().numpy().view(np.uint64), bad)

@@ -132,6 +132,49 @@ def test_variants_byte_for_byte(ctx, name):
     src.close()
 
 
+@pytest.mark.parametrize("name", sorted(SC.scale_variants()))
+def test_scale_variants_byte_for_byte(ctx, name):
+    """the wave's 64-ary search at depths 0 .. 4, the switch between its two lookups at 62, 63 and 64 lane offsets, runs of 64 and more
+    empty kept sequences, totals around a wave's bytes (select_cases.scale_variants; the emulation ran each under the sanitizers)"""
+    v = SC.scale_variants()[name]
+    want = SC.expected(v)
+    inside = SC.scale_self_check(name, v, want)
+    print(name, dict(n_out=want["n_seqs"], n_bases=want["n_bases"], depth=SC.search_depth(want["n_seqs"]), paths=SC.wave_paths(want["offsets"]),
+                     inside=sorted(set(inside.tolist()))[-3:]))
+    src = source_of(ctx, v)
+    assert src.n_seqs == len(v["spans"])
+    got, out = select_raw(ctx, src, v["spans"], v["keep_empty"], v["offs"])
+    same(got, want, name)
+    out.close()
+    again, out = select_raw(ctx, src, v["spans"], v["keep_empty"], v["offs"])
+    assert np.array_equal(again["bases"], got["bases"]), "two runs give the same bytes"
+    out.close()
+    # the binding: offsets kept on both sides, read_len where the result is fixed-length
+    new, index = src.select(dev_u64(v["spans"]).view(-1, 2), keep_empty=v["keep_empty"])
+    assert np.array_equal(new.offsets, want["offsets"]) and new.read_len == want["fixed_len"]
+    assert np.array_equal(index.cpu().numpy().view(np.uint64), want["source_index"])
+    assert np.array_equal(new.download(), want["bases"])
+    new.close()
+    src.close()
+
+
+def test_a_deep_search_on_a_source_without_slack(ctx):
+    """depth_4097 (three steps of the search) from a tensor of exactly n_bases bytes"""
+    import torch
+
+    v = SC.scale_variants()["depth_4097"]
+    want = SC.expected(v)
+    t = torch.from_numpy(v["bases"].copy()).cuda()
+    assert t.numel() == len(v["bases"]) and t.data_ptr() % 16 == 0 and SC.search_depth(want["n_seqs"]) == 3
+    src = ctx.from_tensor(t, read_len=v["read_len"])
+    assert src.n_seqs == len(v["spans"])
+    got, out = select_raw(ctx, src, v["spans"], v["keep_empty"], None)
+    same(got, want, "depth_4097 from_device")
+    assert torch.equal(t.cpu(), torch.from_numpy(v["bases"])), "the source tensor is unchanged"
+    out.close()
+    src.close()
+
+
 @pytest.mark.parametrize("name", ("cases", "keep_empty", "result_fixed", "result_just_not_fixed", "fixed_source"))
 def test_the_result_is_a_batch_for_every_scan(ctx, cases, name):
     """kmers, minimizers and kmer_counts on the selected batch equal those on an upload of the model's bases and offsets"""
