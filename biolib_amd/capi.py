@@ -27,7 +27,7 @@ SYMBOLS = [
     "bl_write_run_u128", "bl_write_vector_u128", "bl_file_count_u128", "bl_read_file_u128_host", "bl_read_file_u128", "bl_merge_runs_u128",
     "bl_table_build_u64", "bl_table_build_u128", "bl_table_destroy", "bl_table_info", "bl_table_arrays", "bl_table_lookup_u64", "bl_table_lookup_u128",
     "bl_table_histogram", "bl_scan_kmer_counts", "bl_scan_read_counts", "bl_table_combine", "bl_table_filter",
-    "bl_select_read_counts", "bl_batch_select", "bl_read_spans",
+    "bl_select_read_counts", "bl_batch_select", "bl_read_spans", "bl_scan_read_edits", "bl_batch_apply_edits",
 ]
 
 
@@ -62,6 +62,23 @@ class SpanRule(C.Structure):
     _fields_ = [("trim", C.c_uint32), ("k", C.c_uint32), ("min_len", C.c_uint64), ("min_kmers", C.c_uint32), ("solid_min_num", C.c_uint32),
                 ("solid_min_den", C.c_uint32), ("solid_max_num", C.c_uint32), ("solid_max_den", C.c_uint32), ("stat_lo", C.c_uint32),
                 ("stat_hi", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class Edit(C.Structure):
+    """bl_edit: one substitution (16 bytes)"""
+    _fields_ = [("pos", C.c_uint64), ("from_", C.c_uint8), ("to", C.c_uint8), ("support", C.c_uint8), ("anchor", C.c_uint8), ("reserved", C.c_uint32)]
+
+
+# the same 16 bytes as a numpy record
+EDIT_DTYPE = [("pos", "<u8"), ("from", "u1"), ("to", "u1"), ("support", "u1"), ("anchor", "u1"), ("reserved", "<u4")]
+
+
+class EditStats(C.Structure):
+    """bl_edit_stats"""
+    _fields_ = [(name, C.c_uint64) for name in ("n_runs", "n_edits", "n_ambiguous", "n_no_base", "n_misfit", "n_low_support")] + [("reserved", C.c_uint64 * 2)]
+
+    def as_dict(self):
+        return {name: int(getattr(self, name)) for name, _ in self._fields_ if name != "reserved"}
 
 
 class TableStats(C.Structure):
@@ -223,6 +240,9 @@ def lib():
     if "BIOLIB_AMD_LIB" not in os.environ or hasattr(L, "bl_batch_select"):
         L.bl_batch_select.argtypes = [vp, vp, vp, vp, u32, C.POINTER(vp), vp, vp, C.POINTER(u64), C.POINTER(u64)]
         L.bl_read_spans.argtypes = [vp, vp, vp, vp, vp, C.POINTER(SpanRule), vp]
+    if "BIOLIB_AMD_LIB" not in os.environ or hasattr(L, "bl_scan_read_edits"):
+        L.bl_scan_read_edits.argtypes = [vp, vp, u64, u64, u32, u32, vp, u32, u32, vp, u64, C.POINTER(EditStats)]
+        L.bl_batch_apply_edits.argtypes = [vp, vp, vp, u64, C.POINTER(vp)]
     _lib = L
     return L
 

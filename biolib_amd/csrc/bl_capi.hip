@@ -370,6 +370,18 @@ int bl_batch_describe(const bl_batch* b, bl_ctx** ctx, uint64_t* n_bases, uint64
     return BL_OK;
 }
 
+// what bl_correct.hip needs of a batch: the start-bit vector the position-tiled scans read (NULL: one sequence).  ensure: build it where a
+// fixed-length batch has not needed it yet; without, such a batch answers NULL and a copy of it builds its own on demand
+int bl_batch_scan_view(bl_ctx* c, const bl_batch* b, int ensure, const uint32_t** start_bits)
+{
+    if (ensure) {
+        int rc = ensure_start_bits(c, b);
+        if (rc != BL_OK) return rc;
+    }
+    *start_bits = b->start_bits;
+    return BL_OK;
+}
+
 // Device scratch that lives with the context (slot 0..7), grown on demand and never shrunk: the set operations and the
 // bucketed counter need gigabytes of temporary space per call, and hipMalloc / hipFree of that size costs more than their
 // kernels.  The caller has synchronised its previous use (these entry points are synchronous).  nullptr on failure.
@@ -838,6 +850,23 @@ int bl_batch_adopt_device(bl_ctx* c, void* d_bases, uint64_t n_bases, uint64_t* 
     if (e == hipSuccess) e = hipStreamSynchronize(s);
     bl_ctx_pool_free(c, d_offsets);
     if (e != hipSuccess) { bl_batch_destroy(b); return fail(BL_ERR_HIP, std::string("adopt: ") + hipGetErrorString(e)); }
+    *out = b;
+    return BL_OK;
+}
+
+// Used by bl_batch_apply_edits (bl_correct.hip): a batch with the geometry of `like` — n_bases, n_seqs, read length, origin — that takes
+// ownership of a pool buffer of its bases (>= n_bases + 64 bytes, zero padded) and of a pool copy of like's start bits (or NULL).
+int bl_batch_adopt_like(bl_ctx* c, const bl_batch* like, void* d_bases, uint32_t* d_start_bits, bl_batch** out)
+{
+    bl_batch* b = nullptr;
+    int rc = new_batch(c, like->n_bases, out, b);
+    if (rc != BL_OK) { bl_ctx_pool_free(c, d_bases); bl_ctx_pool_free(c, d_start_bits); return rc; }
+    b->bases = static_cast<uint8_t*>(d_bases);
+    b->owns_bases = true;
+    b->start_bits = d_start_bits;
+    b->n_seqs = like->n_seqs;
+    b->read_len = like->read_len;
+    b->origin = like->origin;
     *out = b;
     return BL_OK;
 }

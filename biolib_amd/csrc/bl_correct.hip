@@ -1,0 +1,351 @@
+// bl_correct.hip — bl_scan_read_edits: single-substitution repair of reads from a count table, and bl_batch_apply_edits: the edits applied
+// to a copy of the batch.  The per-thread bodies are in bl_correct_core.hpp.  Kernels:
+//   state_kernel        the tile of bl_scan_kmer_counts (bl_tile128.hpp): a state byte per position instead of five bytes of count and validity
+//   run_kernel<false>   one lane per position of the range: the candidates of a workgroup counted, the rejected runs into the statistics
+//   run_kernel<true>    after rocPRIM's exclusive sum of the workgroups' counts: the candidates written in position order
+//   test_kernel         the hot one: a wave per candidate, a lane per k-mer of the run, three alternatives through one search_group call,
+//                       the verdict by ballots; lane 0 writes the edit or the class
+//   compact_kernel      after the exclusive sum of the edit flags: the edits in candidate order, nothing at or beyond the capacity;
+//                       the verdict classes into the statistics
+//   copy_kernel         bl_batch_apply_edits: 16-byte stores
+//   apply_kernel        one lane per edit
+// No atomic decides where anything is stored; the only atomics add to the statistics words.
+#include <hip/hip_runtime.h>
+
+#include <rocprim/device/device_scan.hpp>
+#include <string>
+
+#include "../../include/biolib_amd.h"
+#include "bl_correct_core.hpp"
+#include "bl_lookup_launch.hpp"
+#include "bl_tile128.hpp"
+
+extern int bl_set_error(int code, const char* msg);  // bl_capi.hip
+extern hipStream_t bl_ctx_stream(bl_ctx* ctx);
+extern int bl_ctx_device(bl_ctx* ctx);
+extern void* bl_ctx_scratch(bl_ctx* ctx, int slot, size_t bytes);  // 0 candidates, 4 states and workgroup counts, 5 library workspace, 6 statistics
+extern void* bl_ctx_pool_alloc(bl_ctx* ctx, size_t bytes);         // batch buffers
+extern void bl_ctx_pool_free(bl_ctx* ctx, void* p);
+extern int bl_batch_describe(const bl_batch* batch, bl_ctx** ctx, uint64_t* n_bases, uint64_t* n_seqs, uint64_t* read_len);
+extern int bl_batch_scan_view(bl_ctx* ctx, const bl_batch* batch, int ensure, const uint32_t** start_bits);
+extern int bl_batch_adopt_like(bl_ctx* ctx, const bl_batch* like, void* d_bases, uint32_t* d_start_bits, bl_batch** out);
+
+static_assert(sizeof(blcr::Edit) == sizeof(bl_edit) && alignof(blcr::Edit) == 16, "Edit is bl_edit");
+static_assert(sizeof(bl_edit_stats) == blcr::STAT_WORDS * sizeof(uint64_t), "the statistics words are bl_edit_stats");
+
+namespace blcr {
+
+typedef unsigned long long ull;
+
+struct StateShared {
+    uint32_t codes[bl::NCHUNK_POS];
+    uint32_t flags[bl::NCHUNK_POS];
+};
+
+__global__ __launch_bounds__(bl::TPB) void state_kernel(const StateParams p)
+{
+    __shared__ StateShared sh;
+    const int tid = threadIdx.x;
+    for (int tile = blockIdx.x; tile < p.km.n_tiles; tile += gridDim.x) {
+        const int64_t q0 = p.km.origin + (int64_t)tile * bl::H;
+        __syncthreads();  // the previous tile's codes and flags have been read
+        bl::stage_tile128<bl::NCHUNK_POS>(p.km, sh.codes, sh.flags, tid, q0);
+        __syncthreads();
+        state_thread(p, sh.codes, sh.flags, tid, q0);
+    }
+}
+
+// EMIT = false: block_counts[workgroup] = its candidates, stats += its runs by class.  EMIT = true: block_base = the exclusive sum of the
+// counts; the candidates stored from there on in position order.
+template <bool EMIT>
+__global__ __launch_bounds__(CTPB) void run_kernel(const RunParams p, ull* block_counts, const ull* block_base, Candidate* cand, ull n_cand, ull* stats)
+{
+    __shared__ uint32_t wave_tot[CTPB / 64];
+    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    const int64_t a = p.first + (int64_t)blockIdx.x * CTPB + tid;
+    Candidate c{0, 0, 0};
+    const int cls = a < p.end ? run_at(p, a, c) : RUN_NOT_A_START;
+    const ull is_cand = __ballot(cls == RUN_CANDIDATE);
+    if (lane == 0) wave_tot[wv] = (uint32_t)__popcll(is_cand);
+    if (!EMIT) {
+        const ull runs = __ballot(cls != RUN_NOT_A_START), misfit = __ballot(cls == RUN_MISFIT), low = __ballot(cls == RUN_LOW_SUPPORT);
+        if (lane == 0) {
+            if (runs) atomicAdd(&stats[STAT_RUNS], (ull)__popcll(runs));
+            if (misfit) atomicAdd(&stats[STAT_MISFIT], (ull)__popcll(misfit));
+            if (low) atomicAdd(&stats[STAT_LOW_SUPPORT], (ull)__popcll(low));
+        }
+    }
+    __syncthreads();
+    if (!EMIT) {
+        if (tid == 0) {
+            uint32_t all = 0;
+#pragma unroll
+            for (int i = 0; i < CTPB / 64; ++i) all += wave_tot[i];
+            block_counts[blockIdx.x] = all;
+        }
+    } else if (cls == RUN_CANDIDATE) {
+        ull at = block_base[blockIdx.x] + (ull)__popcll(is_cand & ((1ull << lane) - 1));
+#pragma unroll
+        for (int i = 0; i < CTPB / 64; ++i)
+            if (i < wv) at += wave_tot[i];
+        if (at < n_cand) cand[at] = c;  // (always)
+    }
+}
+
+__global__ __launch_bounds__(CTPB) void test_kernel(const TestParams p)
+{
+    __shared__ uint32_t words[TEST_WAVES][CODE_WORDS_PADDED];
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    const ull idx = (ull)blockIdx.x * TEST_WAVES + wv;
+    const bool active = idx < p.n_cand;  // (wave-uniform)
+    Candidate c{0, 1, 0};
+    if (active) {
+        c = p.cand[idx];
+        if (lane < 4 * CODE_WORDS) reinterpret_cast<uint8_t*>(words[wv])[code_byte_index(lane)] = (uint8_t)code_byte(p.bases, p.n_bases, (int64_t)c.a + 4 * lane);
+        else if (lane < 4 * CODE_WORDS + (CODE_WORDS_PADDED - CODE_WORDS)) words[wv][CODE_WORDS + lane - 4 * CODE_WORDS] = 0;
+    }
+    __syncthreads();
+    if (!active) return;
+    const bool mine = lane < (int)c.len;
+    uint32_t orig = 0, fail = 0;
+    if (mine) fail = test_lane(p, words[wv], c, lane, orig);
+    uint32_t qualifying = 0;
+#pragma unroll
+    for (int t = 0; t < 3; ++t)
+        if (__ballot(mine && ((fail >> t) & 1u)) == 0) qualifying |= 1u << t;
+    if (lane == 0) {
+        Edit e{};
+        const uint64_t pos = edit_position(c, p.k);
+        const uint8_t from = pos < (uint64_t)p.n_bases ? p.bases[pos] : (uint8_t)0;  // (always inside: p lies in a valid k-mer)
+        const uint32_t v = verdict(qualifying, orig, from, c, p.k, e);
+        p.verdicts[idx] = (uint8_t)v;
+        p.edit_flag[idx] = v == V_EDIT ? 1 : 0;
+        if (v == V_EDIT) p.edits[idx] = e;
+    }
+}
+
+__global__ __launch_bounds__(CTPB) void compact_kernel(const Edit* edits, const uint8_t* verdicts, const ull* edit_sum, ull n_cand, Edit* out, ull capacity, ull* stats)
+{
+    const ull i = (ull)blockIdx.x * CTPB + threadIdx.x;
+    const uint32_t v = i < n_cand ? verdicts[i] : V_NONE;
+    if (i < n_cand && out) compact_edit(edits, verdicts, reinterpret_cast<const uint64_t*>(edit_sum), i, out, capacity);
+    const ull ed = __ballot(v == V_EDIT), amb = __ballot(v == V_AMBIGUOUS), nb = __ballot(v == V_NO_BASE);
+    if ((threadIdx.x & 63) == 0) {
+        if (ed) atomicAdd(&stats[STAT_EDITS], (ull)__popcll(ed));
+        if (amb) atomicAdd(&stats[STAT_AMBIGUOUS], (ull)__popcll(amb));
+        if (nb) atomicAdd(&stats[STAT_NO_BASE], (ull)__popcll(nb));
+    }
+}
+
+// n16 16-byte chunks, then the tail's bytes; pad more zero bytes behind them
+__global__ __launch_bounds__(CTPB) void copy_kernel(const uint8_t* __restrict__ src, uint8_t* __restrict__ dst, ull n_bytes, ull pad)
+{
+    const ull i = (ull)blockIdx.x * CTPB + threadIdx.x, n16 = n_bytes / 16;
+    if (i < n16) reinterpret_cast<uint4*>(dst)[i] = reinterpret_cast<const uint4*>(src)[i];
+    if (i < (n_bytes & 15) + pad) {
+        const ull at = 16 * n16 + i;
+        dst[at] = at < n_bytes ? src[at] : (uint8_t)0;
+    }
+}
+
+__global__ __launch_bounds__(CTPB) void apply_kernel(const Edit* edits, ull n_edits, uint8_t* bases, ull n_bases)
+{
+    edit_at(edits, n_edits, (ull)blockIdx.x * CTPB + threadIdx.x, bases, n_bases);
+}
+
+namespace {
+
+int hip_rc(hipError_t e) { return bl_set_error(e == hipErrorOutOfMemory ? BL_ERR_OOM : BL_ERR_HIP, hipGetErrorString(e)); }
+int invalid(const std::string& msg) { return bl_set_error(BL_ERR_INVALID, msg.c_str()); }
+unsigned blocks_for(ull threads) { return (unsigned)((threads + CTPB - 1) / CTPB); }
+size_t round16(size_t b) { return (b + 15) & ~(size_t)15; }
+
+int exclusive_sum(bl_ctx* ctx, const ull* in, ull* out, size_t n, hipStream_t s)
+{
+    size_t bytes = 0;
+    hipError_t e = rocprim::exclusive_scan(nullptr, bytes, in, out, (ull)0, n, rocprim::plus<ull>(), s);
+    if (e != hipSuccess) return hip_rc(e);
+    void* tmp = bl_ctx_scratch(ctx, 5, bytes ? bytes : 16);
+    if (!tmp) return bl_set_error(BL_ERR_OOM, "scratch allocation failed");
+    e = rocprim::exclusive_scan(tmp, bytes, in, out, (ull)0, n, rocprim::plus<ull>(), s);
+    return e == hipSuccess ? BL_OK : hip_rc(e);
+}
+
+}  // namespace
+
+}  // namespace blcr
+
+#define C_HIP(call)                                   \
+    do {                                              \
+        hipError_t e_ = (call);                       \
+        if (e_ != hipSuccess) return blcr::hip_rc(e_); \
+    } while (0)
+
+extern "C" int bl_scan_read_edits(bl_ctx* ctx, const bl_batch* batch, uint64_t first, uint64_t n, uint32_t k, uint32_t flags, const bl_table* table,
+                                  uint32_t min_count, uint32_t min_support, bl_edit* d_edits, uint64_t capacity, bl_edit_stats* stats)
+{
+    using namespace blcr;
+    if (!ctx || !batch || !table) return invalid("ctx, batch or table is NULL");
+    bl_ctx* owner = nullptr;
+    uint64_t n_bases = 0, unused[2];
+    bl_batch_describe(batch, &owner, &n_bases, &unused[0], &unused[1]);
+    if (owner != ctx) return invalid("the batch belongs to another context");
+    if (table->ctx != ctx) return invalid("the table belongs to another context");
+    if (!d_edits && capacity != 0) return invalid("d_edits is NULL with a capacity: the counting call passes capacity 0");
+    if (reinterpret_cast<uintptr_t>(d_edits) & 15) return invalid("d_edits must be 16-byte aligned");
+    if (k < 1 || k > (uint32_t)bl::MAX_UNIT128) return invalid("k must be in [1, 64]");
+    if (table->view.key_words == 1 && k > 32) return invalid("a table of one-word keys takes k <= 32");
+    if (2 * k > table->view.key_bits) return invalid("2k = " + std::to_string(2 * k) + " exceeds the table's key_bits = " + std::to_string(table->view.key_bits));
+    if (min_count == 0) return invalid("min_count must be at least 1");
+    if (min_support < 1 || min_support > k) return invalid("min_support must be in [1, k]");
+    if (flags & ~(uint32_t)(BL_FLAG_CANONICAL | BL_FLAG_SYNC)) return invalid("flags: BL_FLAG_CANONICAL only (BL_FLAG_SYNC is accepted)");
+    if (first > n_bases) return invalid("range starts beyond the batch");
+    const uint64_t end = (n == 0 || n > n_bases - first) ? n_bases : first + n;
+    if (end - first > (1ull << 31)) return invalid("a scan range may hold at most 2^31 positions; split it");
+    if (stats) *stats = bl_edit_stats{};
+    int rc = bl_ctx_sync(ctx);  // the context's scans in flight
+    if (rc != BL_OK) return rc;
+    if (end <= first) return BL_OK;
+
+    const uint32_t* start_bits = nullptr;
+    rc = bl_batch_scan_view(ctx, batch, 1, &start_bits);
+    if (rc != BL_OK) return rc;
+    C_HIP(hipSetDevice(bl_ctx_device(ctx)));
+    hipStream_t s = bl_ctx_stream(ctx);
+
+    // the states of the range, one position in front and k + 1 behind
+    const int64_t s0 = first ? (int64_t)first - 1 : 0;
+    const int64_t s1 = end + k + 1 < n_bases ? (int64_t)(end + k + 1) : (int64_t)n_bases;
+    const ull n_blocks = (end - first + CTPB - 1) / CTPB;
+    const size_t state_bytes = round16((size_t)(s1 - s0));
+    unsigned char* arena = static_cast<unsigned char*>(bl_ctx_scratch(ctx, 4, state_bytes + 2 * (size_t)(n_blocks + 1) * sizeof(ull)));
+    ull* d_stats = static_cast<ull*>(bl_ctx_scratch(ctx, 6, 128));
+    if (!arena || !d_stats) return bl_set_error(BL_ERR_OOM, "scratch allocation failed");
+    ull* block_counts = reinterpret_cast<ull*>(arena + state_bytes);
+    ull* block_base = block_counts + (n_blocks + 1);
+
+    StateParams sp{};
+    sp.km.bases = static_cast<const uint8_t*>(bl_batch_device_bases(batch));
+    sp.km.n_bases = (int64_t)n_bases;
+    sp.km.start_bits = start_bits;
+    bl::plan_kmers128(s0, s1, sp.km);
+    sp.km.unit = (int32_t)k;
+    sp.km.canonical = (flags & BL_FLAG_CANONICAL) ? 1 : 0;
+    sp.table = table->view;
+    sp.min_count = min_count;
+    sp.states = arena;
+    C_HIP(hipMemsetAsync(d_stats, 0, STAT_WORDS * sizeof(ull), s));
+    C_HIP(hipMemsetAsync(block_counts + n_blocks, 0, sizeof(ull), s));
+    C_HIP(bl::launch_tiles128(state_kernel, sp, sp.km.n_tiles, s));
+
+    RunParams rp{};
+    rp.states = arena;
+    rp.s0 = s0;
+    rp.s1 = s1;
+    rp.first = (int64_t)first;
+    rp.end = (int64_t)end;
+    rp.k = k;
+    rp.min_support = min_support;
+    hipLaunchKernelGGL(run_kernel<false>, dim3((unsigned)n_blocks), dim3(CTPB), 0, s, rp, block_counts, (const ull*)nullptr, (Candidate*)nullptr, (ull)0, d_stats);
+    C_HIP(hipGetLastError());
+    rc = exclusive_sum(ctx, block_counts, block_base, (size_t)(n_blocks + 1), s);
+    if (rc != BL_OK) return rc;
+    ull n_cand = 0;
+    C_HIP(hipMemcpyAsync(&n_cand, block_base + n_blocks, sizeof(n_cand), hipMemcpyDeviceToHost, s));
+    C_HIP(hipStreamSynchronize(s));
+
+    if (n_cand) {
+        // slot 0: candidates | their edits | edit flags | the flags' exclusive sum | verdicts
+        const size_t rec = (size_t)n_cand * sizeof(Candidate), words = (size_t)(n_cand + 1) * sizeof(ull);
+        unsigned char* ca = static_cast<unsigned char*>(bl_ctx_scratch(ctx, 0, 2 * rec + 2 * words + round16((size_t)n_cand)));
+        if (!ca) return bl_set_error(BL_ERR_OOM, "scratch allocation failed");
+        Candidate* cand = reinterpret_cast<Candidate*>(ca);
+        Edit* edits = reinterpret_cast<Edit*>(ca + rec);
+        ull* edit_flag = reinterpret_cast<ull*>(ca + 2 * rec);
+        ull* edit_sum = edit_flag + (n_cand + 1);
+        uint8_t* verdicts = ca + 2 * rec + 2 * words;
+        hipLaunchKernelGGL(run_kernel<true>, dim3((unsigned)n_blocks), dim3(CTPB), 0, s, rp, (ull*)nullptr, (const ull*)block_base, cand, n_cand, (ull*)nullptr);
+        C_HIP(hipGetLastError());
+        TestParams tp{};
+        tp.bases = sp.km.bases;
+        tp.n_bases = (int64_t)n_bases;
+        tp.table = table->view;
+        tp.k = k;
+        tp.min_count = min_count;
+        tp.canonical = (uint32_t)sp.km.canonical;
+        tp.cand = cand;
+        tp.n_cand = n_cand;
+        tp.edits = edits;
+        tp.verdicts = verdicts;
+        tp.edit_flag = reinterpret_cast<uint64_t*>(edit_flag);
+        C_HIP(hipMemsetAsync(edit_flag + n_cand, 0, sizeof(ull), s));
+        hipLaunchKernelGGL(test_kernel, dim3((unsigned)((n_cand + TEST_WAVES - 1) / TEST_WAVES)), dim3(CTPB), 0, s, tp);
+        C_HIP(hipGetLastError());
+        rc = exclusive_sum(ctx, edit_flag, edit_sum, (size_t)(n_cand + 1), s);
+        if (rc != BL_OK) return rc;
+        hipLaunchKernelGGL(compact_kernel, dim3(blocks_for(n_cand)), dim3(CTPB), 0, s, edits, verdicts, (const ull*)edit_sum, n_cand, reinterpret_cast<Edit*>(d_edits), (ull)capacity, d_stats);
+        C_HIP(hipGetLastError());
+    }
+    ull host[STAT_WORDS] = {};
+    C_HIP(hipMemcpyAsync(host, d_stats, sizeof(host), hipMemcpyDeviceToHost, s));
+    C_HIP(hipStreamSynchronize(s));
+    if (stats) {
+        stats->n_runs = host[STAT_RUNS];
+        stats->n_edits = host[STAT_EDITS];
+        stats->n_ambiguous = host[STAT_AMBIGUOUS];
+        stats->n_no_base = host[STAT_NO_BASE];
+        stats->n_misfit = host[STAT_MISFIT];
+        stats->n_low_support = host[STAT_LOW_SUPPORT];
+    }
+    if (host[STAT_EDITS] > capacity) return bl_set_error(BL_ERR_CAPACITY, "more edits than the capacity: stats->n_edits is the count");
+    return BL_OK;
+}
+
+extern "C" int bl_batch_apply_edits(bl_ctx* ctx, const bl_batch* batch, const bl_edit* d_edits, uint64_t n_edits, bl_batch** out)
+{
+    using namespace blcr;
+    if (!ctx || !batch || !out) return invalid("ctx, batch or out is NULL");
+    *out = nullptr;
+    bl_ctx* owner = nullptr;
+    uint64_t n_bases = 0, unused[2];
+    bl_batch_describe(batch, &owner, &n_bases, &unused[0], &unused[1]);
+    if (owner != ctx) return invalid("the batch belongs to another context");
+    if (n_edits && !d_edits) return invalid("d_edits is NULL");
+    if (reinterpret_cast<uintptr_t>(d_edits) & 15) return invalid("d_edits must be 16-byte aligned");
+    int rc = bl_ctx_sync(ctx);
+    if (rc != BL_OK) return rc;
+    const uint32_t* start_bits = nullptr;  // (NULL on a fixed-length batch that has not needed them: the copy builds its own on demand)
+    rc = bl_batch_scan_view(ctx, batch, 0, &start_bits);
+    if (rc != BL_OK) return rc;
+    C_HIP(hipSetDevice(bl_ctx_device(ctx)));
+    hipStream_t s = bl_ctx_stream(ctx);
+
+    const size_t bit_words = (size_t)((n_bases + 31) / 32 + 4);  // the length every maker of start bits gives them
+    uint8_t* d_bases = static_cast<uint8_t*>(bl_ctx_pool_alloc(ctx, (size_t)n_bases + 64));
+    uint32_t* d_bits = start_bits ? static_cast<uint32_t*>(bl_ctx_pool_alloc(ctx, bit_words * sizeof(uint32_t))) : nullptr;
+    if (!d_bases || (start_bits && !d_bits)) {
+        bl_ctx_pool_free(ctx, d_bases);
+        bl_ctx_pool_free(ctx, d_bits);
+        return bl_set_error(BL_ERR_OOM, "device allocation failed (batch)");
+    }
+    auto fail_free = [&](hipError_t err) {
+        bl_ctx_pool_free(ctx, d_bases);
+        bl_ctx_pool_free(ctx, d_bits);
+        return hip_rc(err);
+    };
+    const uint8_t* src = static_cast<const uint8_t*>(bl_batch_device_bases(batch));
+    hipLaunchKernelGGL(copy_kernel, dim3(blocks_for(n_bases / 16 + 80)), dim3(CTPB), 0, s, src, d_bases, (ull)n_bases, (ull)64);  // 64 bytes of zeros behind the bases
+    hipError_t e = hipGetLastError();
+    if (e == hipSuccess && d_bits) {
+        hipLaunchKernelGGL(copy_kernel, dim3(blocks_for(bit_words * 4 / 16 + 16)), dim3(CTPB), 0, s, reinterpret_cast<const uint8_t*>(start_bits), reinterpret_cast<uint8_t*>(d_bits),
+                           (ull)(bit_words * 4), (ull)0);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess && n_edits) {
+        hipLaunchKernelGGL(apply_kernel, dim3(blocks_for(n_edits)), dim3(CTPB), 0, s, reinterpret_cast<const Edit*>(d_edits), (ull)n_edits, d_bases, (ull)n_bases);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipStreamSynchronize(s);
+    if (e != hipSuccess) return fail_free(e);
+    return bl_batch_adopt_like(ctx, batch, d_bases, d_bits, out);  // takes ownership of both
+}

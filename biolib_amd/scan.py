@@ -1082,6 +1082,86 @@ class Batch:
         out, source_index = self.select(spans, keep_empty, offsets=offsets)
         return out, source_index, rc
 
+    # ---- repair: single-substitution correction from a count table
+    def read_edits_raw(self, table, k, flags, min_count, min_support, edits, capacity, first=0, n=0, stats=None):
+        """bl_scan_read_edits: `edits` (or None with capacity 0: the counting call) takes `capacity` 16-byte records.  Synchronous; it
+        waits for the scans in flight itself.  Returns (rc, capi.EditStats): rc is BL_OK or BL_ERR_CAPACITY, any other error raises."""
+        stats = stats if stats is not None else capi.EditStats()
+        rc = self._lib.bl_scan_read_edits(self.ctx._h, self._h, int(first), int(n), int(k), int(flags), table._h, int(min_count), int(min_support),
+                                          _ptr(edits), int(capacity), C.byref(stats))
+        if rc != capi.BL_ERR_CAPACITY:
+            check(rc)
+        return rc, stats
+
+    def read_edits(self, table, k, min_count, min_support=1, canonical=False, first=0, n=0, capacity=None):
+        """The single-base repairs the count table supports for the weak runs that begin in the range (bl_scan_read_edits): (edits, stats).
+        A weak run — consecutive k-mers of one read with count < min_count — that has the exact extent a substitution at one base p
+        gives it, with a solid k-mer on one side, is repaired iff exactly one other base at p makes all of its k-mers solid.  edits: an
+        int64 device tensor [n_edits, 2] holding the 16-byte bl_edit records in ascending position (edits_host turns it into a numpy
+        record array, edit_reads into (read, position in the read)); stats: runs by class.  Run once more with the reported count
+        when `capacity` (default: one edit per 64 positions) was too small."""
+        import torch
+
+        span = self._span(first, n)
+        cap = max(int(capacity if capacity is not None else span // 64 + 64), 1)
+        self.ctx._inputs_ready()
+        while True:
+            edits = torch.zeros((cap, 2), dtype=torch.int64, device=self.ctx.torch_device)
+            rc, stats = self.read_edits_raw(table, k, _flags(canonical, False, False), min_count, min_support, edits, cap, first, n)
+            if rc == capi.BL_OK:
+                return edits[:int(stats.n_edits)], stats.as_dict()
+            cap = int(stats.n_edits)
+
+    @staticmethod
+    def edits_host(edits):
+        """the records of read_edits as a numpy record array: pos, from, to, support, anchor, reserved"""
+        return edits.cpu().numpy().view(np.uint8).reshape(-1, 16).copy().view(capi.EDIT_DTYPE).reshape(-1)
+
+    def edit_reads(self, edits, offsets=None):
+        """(read, position inside the read) of every edit, two int64 device tensors, for reporting: torch.searchsorted over the device
+        offsets (offsets: as read_counts; a fixed-length or single-sequence batch needs none)."""
+        import torch
+
+        pos = edits[:, 0].contiguous()
+        d_offsets = self._device_offsets(offsets)
+        if d_offsets is None:
+            if self.n_seqs > 1 and not self.read_len:
+                raise ValueError("offsets: this batch does not know its own")
+            L = self.read_len if self.read_len else max(self.n_bases, 1)
+            read = torch.div(pos, L, rounding_mode="floor")
+            return read, pos - read * L
+        read = torch.searchsorted(d_offsets, pos, right=True) - 1  # the LAST sequence that starts at or before pos: empty ones are skipped
+        return read, pos - d_offsets[read]
+
+    def apply_edits(self, edits):
+        """A new batch with the edits of read_edits applied (bl_batch_apply_edits): the same reads, offsets and origin, every byte
+        verbatim except the edited ones.  This batch is not modified."""
+        if not (edits.is_cuda and edits.element_size() == 8 and edits.is_contiguous() and edits.dim() == 2 and edits.shape[1] == 2):
+            raise ValueError("edits: a contiguous int64 device tensor [n_edits, 2]")
+        self.ctx._inputs_ready()
+        h = C.c_void_p()
+        n = int(edits.shape[0])
+        check(self._lib.bl_batch_apply_edits(self.ctx._h, self._h, _ptr(edits) if n else None, n, C.byref(h)))
+        b = Batch(self.ctx, h, offsets=self._host_offsets, read_len=self.read_len)
+        b._d_offsets = self._d_offsets
+        b._offsets_from_device = self._offsets_from_device
+        return b
+
+    def correct_by_counts(self, table, k, min_count, min_support=1, canonical=False, passes=1):
+        """read_edits and apply_edits chained: (Batch, [edits of each pass], [stats of each pass]).  passes > 1 repeats on the result —
+        a repaired base can complete the shape of a neighbouring run — and stops early when a pass makes no edit."""
+        batch, all_edits, all_stats = self, [], []
+        for _ in range(max(int(passes), 1)):
+            edits, stats = batch.read_edits(table, k, min_count, min_support, canonical)
+            all_edits.append(edits)
+            all_stats.append(stats)
+            if stats["n_edits"] == 0:
+                break
+            batch = batch.apply_edits(edits)
+        if batch is self:
+            batch = self.apply_edits(all_edits[0])  # no edit at all: still a batch of its own
+        return batch, all_edits, all_stats
+
     def hash_sample128(self, k, seed=0, threshold=2**64 - 1, canonical=False, drop_last=False, first=0, n=0, capacity=None, device=False):
         """k-mers up to k = 64 with hash64_u128(value, seed) < threshold, in position order; values has shape (count, 2) as in kmers128.
         Run again with the count the scan reports when `capacity` (default: the expected number of records) was too small.

@@ -601,6 +601,61 @@ typedef struct bl_span_rule {
 int bl_read_spans(bl_ctx* ctx, const bl_batch* batch, const uint64_t* d_offsets, const bl_read_counts* d_records, const uint32_t* d_stat /* nullable */,
                   const bl_span_rule* rule, uint64_t* d_spans);
 
+/* Correct substitution errors from a count table: the chain's repair step (Quake, Musket, BFC and Lighter use a k-mer spectrum this
+ * way).  bl_scan_read_edits finds the edits, bl_batch_apply_edits makes the corrected batch, an ordinary batch for every scan.
+ *
+ * The rule.  A read of L bases has n = L - k + 1 k-mer positions j = 0 .. n - 1 (none if L < k).  Validity and the canonical form are
+ * exactly bl_scan_kmer_counts's under the same BL_FLAG_CANONICAL.  A position is INVALID (no valid k-mer starts there), SOLID (valid,
+ * table count >= min_count) or WEAK (valid, count < min_count; an absent key counts 0).  A weak run is a maximal interval [a, b] of
+ * consecutive WEAK positions of one read; runs never cross reads.  A substitution at read-relative base p touches exactly the k-mers
+ * max(0, p - k + 1) .. min(p, n - 1).  Every run is counted under the first of these classes that applies:
+ *   1 shape      left-anchored: a >= 1 and state[a - 1] SOLID; then p = a + k - 1 and the run fits iff b = min(p, n - 1).
+ *                right-anchored: not left-anchored, b <= n - 2 and state[b + 1] SOLID; then p = b and the run fits iff
+ *                a = max(0, b - k + 1).  An unanchored run or one of the wrong length is a MISFIT (two errors closer than k are).
+ *   2 support    b - a + 1 < min_support: LOW SUPPORT.  1 <= min_support <= k; 1 is no condition.
+ *   3 alternatives   for each of the three other 2-bit codes c: the k-mers a .. b with the code at p replaced by c, made canonical as
+ *                the scan does; c qualifies iff every one of them is SOLID.
+ *   4 decision   exactly one qualifying c: an EDIT; none: NO BASE; two or three: AMBIGUOUS, no edit.
+ * An edit replaces the byte at p by "ACGT"[c] with the original byte's 0x20 (case) bit (U and T share a code, so a U is
+ * only ever replaced by A, C or G, and U is never written).
+ * Consequence: the edit at p touches exactly the k-mers a .. b of its own run, so the edits of different runs are independent.  After
+ * all edits of a batch are applied every k-mer of a corrected run is SOLID, and every other position of the batch keeps its state and
+ * its count.  Not attempted: insertions and deletions, two errors within k of each other, ties broken by counts, qualities.
+ *
+ * bl_scan_read_edits judges the weak runs whose FIRST position a lies in [first, first + n) (n = 0: to the end; at most 2^31
+ * positions).  It reads states and bases in front of and behind the range as needed, so the edits of consecutive ranges concatenate
+ * and their stats add up exactly to those of one call over the union, wherever the cut falls.  Read boundaries come from the batch
+ * itself (start bits or the fixed read length): no offsets array is taken.
+ *   k            1 .. 64; the table rules are bl_scan_kmer_counts's (a one-word table takes k <= 32, 2k <= key_bits)
+ *   flags        BL_FLAG_CANONICAL only; BL_FLAG_SYNC is accepted and means nothing here; BL_FLAG_DROP_LAST and unknown bits are refused
+ *   min_count    >= 1
+ *   d_edits      16-byte aligned, room for `capacity` records, written in strictly ascending pos: a bit-reproducible order, no atomic
+ *                decides placement.  Nothing is written at or beyond capacity.  NULL with capacity 0 is the counting call.
+ *   stats        (nullable) host struct, always the full counts; n_runs is the sum of the five classes.
+ * BL_ERR_CAPACITY when n_edits > capacity (stats still complete).  Synchronous; it first waits for the context's scans in flight.
+ * An empty range, an empty batch and an empty table succeed; with an empty table every valid k-mer is weak and every run a misfit.
+ *
+ * bl_batch_apply_edits returns a NEW batch of the same context with the source's geometry — n_bases, n_seqs, fixed read length or
+ * start bits, origin; the source is not modified.  Every byte is copied verbatim except bases[pos] = to for every edit.  `from` is
+ * not checked; an edit with pos >= n_bases is ignored; among neighbouring edits with equal pos the first wins (an unsorted array with
+ * duplicates is the caller's problem); whatever the array holds, no store leaves the new batch.  n_edits = 0 gives a plain copy.
+ * Synchronous.
+ *
+ * BL_ERR_INVALID with a message, nothing launched: NULL or foreign-context ctx, batch, table or out; misaligned d_edits; d_edits NULL
+ * with a capacity (or with n_edits); k out of range; a table too narrow for k; min_count = 0; min_support outside 1 .. k; bad flags;
+ * a range that starts beyond the batch or holds more than 2^31 positions. */
+typedef struct bl_edit {        /* 16 bytes, 16-byte aligned arrays */
+    uint64_t pos;               /* position of the byte in the batch (batch-relative; the origin is NOT added: bl_batch_apply_edits consumes it) */
+    uint8_t  from, to;          /* the byte that was there, the byte to write */
+    uint8_t  support;           /* b - a + 1: the k-mers that vouch for the edit, 1..64 */
+    uint8_t  anchor;            /* 0 left-anchored, 1 right-anchored */
+    uint32_t reserved;          /* 0 */
+} bl_edit;
+typedef struct bl_edit_stats { uint64_t n_runs, n_edits, n_ambiguous, n_no_base, n_misfit, n_low_support, reserved[2]; } bl_edit_stats;
+int bl_scan_read_edits(bl_ctx* ctx, const bl_batch* batch, uint64_t first, uint64_t n, uint32_t k, uint32_t flags, const bl_table* table,
+                       uint32_t min_count, uint32_t min_support, bl_edit* d_edits, uint64_t capacity, bl_edit_stats* stats);
+int bl_batch_apply_edits(bl_ctx* ctx, const bl_batch* batch, const bl_edit* d_edits, uint64_t n_edits, bl_batch** out);
+
 /* Count reduction across the GPUs of one node: ctxs[g] is the context of device g (all distinct devices),
  * counters holds n_gpu rows of n 64-bit counters — row g = GPU g's local counts in, the column sums out (in every row).  One
  * ncclAllReduce(sum, uint64) per GPU over RCCL / xGMI, called on RCCL's C API directly (librccl.so.1 is loaded on first use);
