@@ -28,6 +28,7 @@ SYMBOLS = [
     "bl_table_build_u64", "bl_table_build_u128", "bl_table_destroy", "bl_table_info", "bl_table_arrays", "bl_table_lookup_u64", "bl_table_lookup_u128",
     "bl_table_histogram", "bl_scan_kmer_counts", "bl_scan_read_counts", "bl_table_combine", "bl_table_filter",
     "bl_select_read_counts", "bl_batch_select", "bl_read_spans", "bl_scan_read_edits", "bl_batch_apply_edits",
+    "bl_table_adjacency", "bl_table_unitigs",
 ]
 
 
@@ -88,6 +89,19 @@ class TableStats(C.Structure):
     def as_dict(self):
         return {name: int(getattr(self, name)) for name, _ in self._fields_ if name != "reserved"}
 
+
+class GraphStats(C.Structure):
+    """bl_graph_stats"""
+    _fields_ = [(name, C.c_uint64) for name in ("n_keys", "n_arcs", "n_isolated", "n_dead_end_sides", "n_branch_sides", "n_linked_sides", "n_unitigs",
+                                                "n_cycles", "longest_unitig")] + [("reserved", C.c_uint64 * 3)]
+
+    def as_dict(self):
+        return {name: int(getattr(self, name)) for name, _ in self._fields_ if name != "reserved"}
+
+
+LINK_NONE = 0xFFFFFFFF
+# bl_unitig_node as a numpy record
+UNITIG_NODE_DTYPE = [("unitig", "<u4"), ("rank_flip", "<u4")]
 
 TABLE_UNION, TABLE_INTERSECT, TABLE_SUBTRACT, TABLE_COUNT_SUBTRACT = 0, 1, 2, 3
 COUNT_SUM, COUNT_MIN, COUNT_MAX, COUNT_LEFT, COUNT_RIGHT = 0, 1, 2, 3, 4
@@ -243,6 +257,9 @@ def lib():
     if "BIOLIB_AMD_LIB" not in os.environ or hasattr(L, "bl_scan_read_edits"):
         L.bl_scan_read_edits.argtypes = [vp, vp, u64, u64, u32, u32, vp, u32, u32, vp, u64, C.POINTER(EditStats)]
         L.bl_batch_apply_edits.argtypes = [vp, vp, vp, u64, C.POINTER(vp)]
+    if "BIOLIB_AMD_LIB" not in os.environ or hasattr(L, "bl_table_adjacency"):
+        L.bl_table_adjacency.argtypes = [vp, vp, u32, vp, vp, C.POINTER(GraphStats)]
+        L.bl_table_unitigs.argtypes = [vp, vp, u32, C.POINTER(vp), vp, vp, vp, C.POINTER(u64), C.POINTER(u64), C.POINTER(GraphStats)]
     _lib = L
     return L
 

@@ -386,7 +386,8 @@ int bl_batch_scan_view(bl_ctx* c, const bl_batch* b, int ensure, const uint32_t*
 // bucketed counter need gigabytes of temporary space per call, and hipMalloc / hipFree of that size costs more than their
 // kernels.  The caller has synchronised its previous use (these entry points are synchronous).  nullptr on failure.
 // Who uses what: 0-3 the k-mer counter and the text parser (which call the set operations while holding them), 4-6 the set
-// operations themselves (4 data, 5 library workspace, 6 counters).
+// operations themselves (4 data, 5 library workspace, 6 counters).  The table algebra, the quantiles, select, the corrector and the
+// table graph (bl_graph.hip: about 133 bytes per key in slot 4) use 4-6 the same way: none of them calls another while holding them.
 void* bl_ctx_scratch(bl_ctx* c, int slot, size_t bytes)
 {
     if (!c || slot < 0 || slot >= 8) return nullptr;

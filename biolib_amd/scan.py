@@ -654,6 +654,81 @@ class CountTable:
         st["weighted_jaccard"] = st["sum_min"] / st["sum_max"] if st["sum_max"] else 0.0
         return st
 
+    # ---- the graph on the keys (bl_table_adjacency, bl_table_unitigs): a table of canonical k-mers, k odd, is a de Bruijn graph
+    def adjacency_raw(self, k, mask, links=None, stats=None):
+        """bl_table_adjacency: `mask` takes n_distinct bytes, `links` (or None) 2 * n_distinct 32-bit words, `stats` (or None) is a
+        capi.GraphStats.  Synchronous; the library checks k and the table."""
+        check(self._lib.bl_table_adjacency(self.ctx._h, self._h, int(k), _ptr(mask), _ptr(links), C.byref(stats) if stats is not None else None))
+
+    def adjacency(self, k, links=False):
+        """The neighbours of every key in the bidirected de Bruijn graph of this table of canonical k-mers (k odd, at most 63):
+        (mask, links, stats).  mask: a uint8 device tensor, one byte per key in key order; bit c (A C G T = 0..3) is set where the k-mer
+        with base c appended has its canonical form in the table, bit 4 + c where the one with base c prepended has.  links (None
+        without links=True): an int32 device tensor [n_distinct, 2] holding uint32 words, column 0 the key's left side and column 1
+        its right side: (j << 1) | t where the side has exactly one neighbour, another key j, whose side t (0 left, 1 right) has
+        exactly one too; -1 (BL_LINK_NONE) otherwise.  stats: n_keys, n_arcs, n_isolated, n_dead_end_sides, n_branch_sides,
+        n_linked_sides.  Filter the table first (filter(2)) to build the graph of the solid k-mers."""
+        import torch
+
+        n, dev = self.n_distinct, self.ctx.torch_device
+        mask = torch.empty(max(n, 1), dtype=torch.uint8, device=dev)
+        d_links = torch.empty((max(n, 1), 2), dtype=torch.int32, device=dev) if links else None
+        st = capi.GraphStats()
+        self.ctx._inputs_ready()
+        self.adjacency_raw(k, mask, d_links, st)
+        stats = {name: value for name, value in st.as_dict().items() if name in ("n_keys", "n_arcs", "n_isolated", "n_dead_end_sides", "n_branch_sides", "n_linked_sides")}
+        return mask[:n], (d_links[:n] if links else None), stats
+
+    def unitigs_raw(self, k, batch=True, offsets=None, count_sums=None, nodes=None, stats=None):
+        """bl_table_unitigs: `offsets` / `count_sums` / `nodes` (or None) take n_distinct + 1 / n_distinct 64-bit words and n_distinct
+        8-byte records.  Returns (handle or None, n_unitigs, n_bases).  Synchronous; the library checks k and the table."""
+        h, nu, nb = C.c_void_p(), C.c_uint64(), C.c_uint64()
+        check(self._lib.bl_table_unitigs(self.ctx._h, self._h, int(k), C.byref(h) if batch else None, _ptr(offsets), _ptr(count_sums), _ptr(nodes),
+                                         C.byref(nu), C.byref(nb), C.byref(stats) if stats is not None else None))
+        return (h if batch else None), int(nu.value), int(nb.value)
+
+    def unitigs(self, k, nodes=False, batch=True):
+        """The unitigs of this table of canonical k-mers (k odd, at most 63): its non-branching paths and cycles compacted on the device,
+        every key in exactly one (bl_table_unitigs; the header states the start and orientation rules).  Returns a Unitigs:
+        .batch       a device-resident Batch of the unitig strings (L + k - 1 uppercase bases for L keys), numbered by the slot of their
+                     start key; it keeps its offsets on the device like the result of select, so kmers, minimizers, kmer_counts,
+                     read_counts run on it as they are: the canonical k-mers of the batch are the table's keys, each exactly once
+                     (None with batch=False: labels only)
+        .offsets     int64 device tensor [n_unitigs + 1]
+        .count_sums  int64 device tensor [n_unitigs]: the sum of the unitig's keys' counts; over its number of keys
+                     (length - k + 1) BCALM's mean abundance
+        .nodes       with nodes=True an int32 device tensor [n_distinct, 2] (uint32 words): the unitig of every key and
+                     (rank << 1) | flip — its place counted from the start key, and whether it is read reverse-complemented
+        .stats       n_unitigs, n_cycles and longest_unitig (in keys) besides the six of adjacency
+        Filter the table first (filter(2)) to compact the graph of the solid k-mers."""
+        import torch
+
+        n, dev = self.n_distinct, self.ctx.torch_device
+        offsets = torch.empty(n + 1, dtype=torch.int64, device=dev)
+        sums = torch.empty(max(n, 1), dtype=torch.int64, device=dev)
+        d_nodes = torch.empty((max(n, 1), 2), dtype=torch.int32, device=dev) if nodes else None
+        st = capi.GraphStats()
+        self.ctx._inputs_ready()
+        h, n_unitigs, n_bases = self.unitigs_raw(k, batch, offsets, sums, d_nodes, st)
+        d_out = offsets[:n_unitigs + 1]
+        b = None
+        if batch:
+            fixed = 0  # the library's rule: more than one sequence, all equally long
+            if n_unitigs > 1 and n_bases % n_unitigs == 0 and bool((d_out[1:] - d_out[:-1] == n_bases // n_unitigs).all()):
+                fixed = n_bases // n_unitigs
+            b = Batch(self.ctx, h, read_len=fixed)
+            b._d_offsets = d_out
+            b._offsets_from_device = True
+        return Unitigs(b, d_out, sums[:n_unitigs], d_nodes[:n] if nodes else None, st.as_dict(), n_unitigs, n_bases)
+
+
+class Unitigs:
+    """What CountTable.unitigs returns: batch, offsets, count_sums, nodes, stats (and n_unitigs, n_bases)."""
+
+    def __init__(self, batch, offsets, count_sums, nodes, stats, n_unitigs, n_bases):
+        self.batch, self.offsets, self.count_sums, self.nodes, self.stats = batch, offsets, count_sums, nodes, stats
+        self.n_unitigs, self.n_bases = n_unitigs, n_bases
+
 
 class ReadCounts:
     """The records of bl_scan_read_counts, one per sequence: `records` is the raw device buffer, int64[n_seqs, 6]; the fields are views

@@ -656,6 +656,59 @@ int bl_scan_read_edits(bl_ctx* ctx, const bl_batch* batch, uint64_t first, uint6
                        uint32_t min_count, uint32_t min_support, bl_edit* d_edits, uint64_t capacity, bl_edit_stats* stats);
 int bl_batch_apply_edits(bl_ctx* ctx, const bl_batch* batch, const bl_edit* d_edits, uint64_t n_edits, bl_batch** out);
 
+/* The graph on a table's keys: the compacted de Bruijn graph (BCALM's unitigs; what assemblers, variant callers and the colored-graph
+ * tools work on) of a table of canonical k-mers.  The keys are the nodes, the arcs are implied by (k - 1)-overlaps; bl_table_adjacency
+ * asks the table for all eight neighbours of every key, bl_table_unitigs compacts the non-branching paths.  Usually the table is first
+ * reduced to its solid k-mers with bl_table_filter.
+ * SCOPE  the bidirected graph of canonical k-mers, k ODD, 1 <= k <= 63.  A key holds the first base in its most significant pair
+ *   (A C G T = 0 1 2 3); canonical is the numeric minimum of the value and its reverse complement taken in 2k bits, exactly
+ *   bl_scan_kmers128's with BL_FLAG_CANONICAL.  An even k (a k-mer can be its own reverse complement) and a table of forward k-mers
+ *   (it needs another start rule) are refused.
+ * MASK  the key x at slot i gets one byte.  Bit c (c = 0..3) is set iff the canonical form of f = ((x << 2) | c) mod 4^k is a key: the
+ *   RIGHT side of x, base c appended.  Bit 4 + c is set iff the canonical form of f = (x >> 2) | (c << (2k - 2)) is a key: the LEFT side,
+ *   base c prepended.  The neighbour y = canon(f) is entered by its side t: going right, t is left if y == f, else right; going left, t
+ *   is right if y == f, else left.  The degree of a side is the number of bits of its nibble.  Arcs to the key itself count (AAA's right
+ *   nibble has bit A), and two bases that lead to one key (f1 = rc(f2); k = 1 only) set two bits.
+ * LINKS  side s of key i is linked to side t of key j iff side s has degree 1 and its one neighbour is (j, t), j != i, and side t of j
+ *   has degree 1.  Links are symmetric.  d_links[2i + s] = (j << 1) | t or BL_LINK_NONE, s = 0 for the left side and 1 for the right.
+ * UNITIGS  sides connected by links and by passing through a key form paths and cycles; each is one unitig and each key lies in exactly
+ *   one.  A path of one key: the key as stored, flip 0.  A path of several keys starts at the end key with the smaller slot and leaves it
+ *   through its linked side; a key is read as stored (flip 0) when the walk leaves it through its right side (it entered through the
+ *   left), otherwise reverse-complemented (flip 1).  A cycle starts at its smallest slot, leaves through that key's right side (flip 0)
+ *   and ends in front of the start: the link of the start's left side counts as cut.  Unitigs are numbered in ascending slot of their
+ *   start key.  A unitig of L keys is a string of L + k - 1 uppercase ACGT bytes: the k bases of the oriented start key, then the last
+ *   base of every later oriented key.  Its count sum is the 64-bit sum of its keys' counts (divided by L: BCALM's mean abundance).
+ *
+ * bl_table_adjacency: d_mask takes n = n_distinct bytes, d_links (nullable) 2n words; stats (nullable, host) gets its first six words:
+ *   n_keys, n_arcs (all set mask bits), n_isolated (keys with no arc), n_dead_end_sides (degree 0), n_branch_sides (degree >= 2),
+ *   n_linked_sides; the others are 0.
+ * bl_table_unitigs: *out (nullable: labels only) is a NEW batch the library owns (bl_batch_destroy), an ordinary batch of the context
+ *   for every scan: the unitig strings concatenated, origin 0; a fixed-length batch only where it holds more than one unitig and all are
+ *   equally long, otherwise it carries start bits.  d_out_offsets (nullable) takes n_unitigs + 1 offsets into it, room for n + 1;
+ *   d_count_sums (nullable) n_unitigs sums, room for n; d_nodes (nullable) one bl_unitig_node per key: its unitig and
+ *   (rank << 1) | flip, rank counted from the start key.  n_unitigs, n_bases (nullable) are host words; stats gets all nine words:
+ *   n_unitigs, n_cycles and longest_unitig (in keys) besides the six above.  An empty table gives zero unitigs: a valid batch of 0
+ *   bases and 0 sequences, as bl_batch_select makes one.  Results are bit-reproducible: no atomic decides a placement.
+ * Both calls are synchronous; temporaries come from the context's scratch (bl_table_unitigs: about 133 bytes per key).
+ * BL_ERR_INVALID with a message, nothing written: NULL ctx or table; a table of another context; k even, 0 or above 63; 2k above the
+ * table's key_bits; a table of one-word keys with k > 31; 2^31 keys or more; a table that holds a key with a bit at or above 2k or a key
+ * greater than its own reverse complement (one reduction over the keys in front of everything else; the message names the first such
+ * slot); bl_table_adjacency with d_mask NULL on a table that is not empty. */
+#define BL_LINK_NONE 0xFFFFFFFFu
+typedef struct bl_graph_stats {
+    uint64_t n_keys, n_arcs;
+    uint64_t n_isolated, n_dead_end_sides, n_branch_sides, n_linked_sides;
+    uint64_t n_unitigs, n_cycles, longest_unitig;
+    uint64_t reserved[3];
+} bl_graph_stats;
+typedef struct bl_unitig_node { uint32_t unitig; uint32_t rank_flip; /* (rank << 1) | flip */ } bl_unitig_node;
+int bl_table_adjacency(bl_ctx* ctx, const bl_table* table, uint32_t k, uint8_t* d_mask /* n */, uint32_t* d_links /* 2n, nullable */,
+                       bl_graph_stats* stats /* nullable */);
+int bl_table_unitigs(bl_ctx* ctx, const bl_table* table, uint32_t k, bl_batch** out /* nullable: labels only */,
+                     uint64_t* d_out_offsets /* n + 1, nullable */, uint64_t* d_count_sums /* n, nullable */,
+                     bl_unitig_node* d_nodes /* n, nullable */, uint64_t* n_unitigs, uint64_t* n_bases,
+                     bl_graph_stats* stats /* nullable */);
+
 /* Count reduction across the GPUs of one node: ctxs[g] is the context of device g (all distinct devices),
  * counters holds n_gpu rows of n 64-bit counters — row g = GPU g's local counts in, the column sums out (in every row).  One
  * ncclAllReduce(sum, uint64) per GPU over RCCL / xGMI, called on RCCL's C API directly (librccl.so.1 is loaded on first use);
