@@ -10,7 +10,7 @@ import os
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("BIOLIB_AMD_LIB", os.path.join(_HERE, "lib", "libbiolib_amd.so"))  # override: A/B builds only
 
-BL_OK, BL_ERR_INVALID, BL_ERR_HIP, BL_ERR_OOM, BL_ERR_CAPACITY, BL_ERR_NO_DEVICE, BL_ERR_INTERNAL = 0, -1, -2, -3, -4, -5, -6
+BL_OK, BL_ERR_INVALID, BL_ERR_HIP, BL_ERR_OOM, BL_ERR_CAPACITY, BL_ERR_NO_DEVICE, BL_ERR_INTERNAL, BL_ERR_IO = 0, -1, -2, -3, -4, -5, -6, -7
 FLAG_CANONICAL, FLAG_DROP_LAST, FLAG_SYNC = 1, 2, 4
 
 # every symbol include/biolib_amd.h declares (tests check the library exports exactly these)
@@ -29,6 +29,8 @@ SYMBOLS = [
     "bl_table_histogram", "bl_scan_kmer_counts", "bl_scan_read_counts", "bl_table_combine", "bl_table_filter",
     "bl_select_read_counts", "bl_batch_select", "bl_read_spans", "bl_scan_read_edits", "bl_batch_apply_edits",
     "bl_table_adjacency", "bl_table_unitigs",
+    "bl_text_index_build", "bl_text_index_info", "bl_text_index_offsets", "bl_text_index_destroy", "bl_reader_next_batch_device_indexed", "bl_batch_format",
+    "bl_text_write",
 ]
 
 
@@ -97,6 +99,18 @@ class GraphStats(C.Structure):
 
     def as_dict(self):
         return {name: int(getattr(self, name)) for name, _ in self._fields_ if name != "reserved"}
+
+
+FORMAT_FASTA, FORMAT_FASTQ = 0, 1
+FORMAT_SKIP_EMPTY, FORMAT_TAG_LENGTH = 1, 2
+# the 16-byte record of bl_text_index_info as a numpy record
+TEXT_RECORD_DTYPE = [("name_begin", "<u8"), ("name_len", "<u4"), ("qual_delta", "<u4")]
+
+
+class FormatRule(C.Structure):
+    """bl_format_rule (64 bytes)"""
+    _fields_ = [("format", C.c_uint32), ("flags", C.c_uint32), ("line_width", C.c_uint32), ("quality_fill", C.c_uint32), ("name_prefix", C.c_char * 16),
+                ("first_number", C.c_uint64), ("tag_label", C.c_char * 16), ("reserved", C.c_uint64)]
 
 
 LINK_NONE = 0xFFFFFFFF
@@ -260,6 +274,15 @@ def lib():
     if "BIOLIB_AMD_LIB" not in os.environ or hasattr(L, "bl_table_adjacency"):
         L.bl_table_adjacency.argtypes = [vp, vp, u32, vp, vp, C.POINTER(GraphStats)]
         L.bl_table_unitigs.argtypes = [vp, vp, u32, C.POINTER(vp), vp, vp, vp, C.POINTER(u64), C.POINTER(u64), C.POINTER(GraphStats)]
+    if "BIOLIB_AMD_LIB" not in os.environ or hasattr(L, "bl_batch_format"):
+        L.bl_text_index_build.argtypes = [vp, vp, u64, C.POINTER(vp), C.POINTER(vp), C.POINTER(u64), C.POINTER(u64)]
+        L.bl_text_index_info.argtypes = [vp, C.POINTER(u64), C.POINTER(C.c_int), C.POINTER(vp), C.POINTER(u64), C.POINTER(vp)]
+        L.bl_text_index_offsets.argtypes = [vp]
+        L.bl_text_index_offsets.restype = vp
+        L.bl_text_index_destroy.argtypes = [vp]
+        L.bl_reader_next_batch_device_indexed.argtypes = [vp, vp, u64, C.POINTER(vp), C.POINTER(vp), C.POINTER(u64), C.POINTER(u64)]
+        L.bl_batch_format.argtypes = [vp, vp, vp, vp, vp, vp, vp, C.POINTER(FormatRule), vp, u64, C.POINTER(u64), C.POINTER(u64)]
+        L.bl_text_write.argtypes = [vp, vp, u64, C.c_char_p, C.c_int]
     _lib = L
     return L
 

@@ -60,6 +60,8 @@ extern int bl_bgzf_inflate_on(hipStream_t s, const void* d_packed, uint64_t pack
                               uint64_t text_bytes, uint32_t* d_status);  // bl_inflate.hip
 extern int bl_parse_device_text(bl_ctx* ctx, const uint8_t* d_text, uint64_t n_bytes, char first_byte, const char* ends, uint64_t ends_n, bl_batch** out,
                                 uint64_t* n_seqs, uint64_t* n_bases);  // bl_parse.hip
+extern int bl_text_index_from_device(bl_ctx* ctx, const uint8_t* d_text, uint64_t n_bytes, char first_byte, const char* ends, uint64_t ends_n,
+                                     bl_batch** out_batch, bl_text_index** out_index, uint64_t* n_seqs, uint64_t* n_bases);  // bl_format.hip
 
 namespace {
 
@@ -2061,7 +2063,7 @@ int launch_packed(DeviceBgzf& d, int buf, size_t offset)
 // inflated on the reader's own stream before this call parses its text: the upload, the launch and the host's part overlap the
 // parse and whatever the caller does with the batch.  (The kernels themselves take turns: four members per CU hold all of its
 // LDS, so a scan queued behind a span's inflate starts when that has drained — tests/perf/ingest_trace.py.)
-int next_batch_packed(bl_ctx* ctx, bl_reader* r, bl_batch** out, uint64_t* n_seqs, uint64_t* n_bases)
+int next_batch_packed(bl_ctx* ctx, bl_reader* r, bl_batch** out, bl_text_index** out_index, uint64_t* n_seqs, uint64_t* n_bases)
 {
     DeviceBgzf& d = *r->packed;
     if (d.ctx != ctx) return bl_set_error(BL_ERR_INVALID, "a reader's device batches must all go to the same context");
@@ -2197,7 +2199,8 @@ int next_batch_packed(bl_ctx* ctx, bl_reader* r, bl_batch** out, uint64_t* n_seq
         const size_t ends_n = cut < 64 ? cut : 64;
         const char* ends = d.window + (cut - win_from) - ends_n;
         const double t0 = now();
-        const int rc = bl_parse_device_text(ctx, text, cut, d.first_byte, ends, ends_n, out, n_seqs, n_bases);
+        const int rc = out_index ? bl_text_index_from_device(ctx, text, cut, d.first_byte, ends, ends_n, out, out_index, n_seqs, n_bases)
+                                 : bl_parse_device_text(ctx, text, cut, d.first_byte, ends, ends_n, out, n_seqs, n_bases);
         d.t_parse += now() - t0;
         ++d.n_batches;
         return rc;
@@ -2206,7 +2209,23 @@ int next_batch_packed(bl_ctx* ctx, bl_reader* r, bl_batch** out, uint64_t* n_seq
 
 }  // namespace
 
+static int next_batch_device(bl_ctx* ctx, bl_reader* r, uint64_t max_text_bytes, bl_batch** out, bl_text_index** out_index, uint64_t* n_seqs, uint64_t* n_bases);
+
 int bl_reader_next_batch_device(bl_ctx* ctx, bl_reader* r, uint64_t max_text_bytes, bl_batch** out, uint64_t* n_seqs, uint64_t* n_bases)
+{
+    return next_batch_device(ctx, r, max_text_bytes, out, nullptr, n_seqs, n_bases);
+}
+
+// the same spans, every batch with the index of its text (bl_format.hip)
+int bl_reader_next_batch_device_indexed(bl_ctx* ctx, bl_reader* r, uint64_t max_text_bytes, bl_batch** out, bl_text_index** out_index, uint64_t* n_seqs,
+                                        uint64_t* n_bases)
+{
+    if (!out_index) return bl_set_error(BL_ERR_INVALID, "NULL argument");
+    *out_index = nullptr;
+    return next_batch_device(ctx, r, max_text_bytes, out, out_index, n_seqs, n_bases);
+}
+
+static int next_batch_device(bl_ctx* ctx, bl_reader* r, uint64_t max_text_bytes, bl_batch** out, bl_text_index** out_index, uint64_t* n_seqs, uint64_t* n_bases)
 {
     if (!ctx || !r || !out) return bl_set_error(BL_ERR_INVALID, "NULL argument");
     *out = nullptr;
@@ -2224,13 +2243,13 @@ int bl_reader_next_batch_device(bl_ctx* ctx, bl_reader* r, uint64_t max_text_byt
     }
     if (r->packed) {
         if (r->records || r->text) return bl_set_error(BL_ERR_INVALID, "records, spans and device batches cannot be mixed on one reader");
-        return next_batch_packed(ctx, r, out, n_seqs, n_bases);
+        return next_batch_packed(ctx, r, out, out_index, n_seqs, n_bases);
     }
     const char* text = nullptr;
     uint64_t n = 0;
     const int rc = next_span(r, max_text_bytes, PINNED_MEMORY, &text, &n);
     if (rc != BL_OK) return rc == 1 ? BL_OK : rc;  // end of file: *out stays NULL
-    return bl_batch_from_text(ctx, text, n, out, n_seqs, n_bases);
+    return out_index ? bl_text_index_build(ctx, text, n, out, out_index, n_seqs, n_bases) : bl_batch_from_text(ctx, text, n, out, n_seqs, n_bases);
 }
 
 int bl_reader_last_batch(bl_reader* r, const char** bases, const uint64_t** offsets, uint64_t* n_seqs)

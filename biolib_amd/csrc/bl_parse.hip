@@ -125,6 +125,10 @@ __global__ void gather_bases_kernel(const uint8_t* text, const unsigned long lon
 // (all of it when the text is shorter than 64): the few decisions taken on the host look at the first byte and at the end only.
 int bl_parse_device_text(bl_ctx* ctx, const uint8_t* d_text_in, uint64_t n_bytes, char first_byte, const char* ends, uint64_t ends_n, bl_batch** out,
                          uint64_t* n_seqs, uint64_t* n_bases);
+// The same, and (lines != NULL) where the line arrays it leaves in scratch slot 1 are: valid until the context's next parse.  bl_format.hip
+// builds the record index of a text from them.  With lines NULL the launches and the results are those of bl_parse_device_text.
+int bl_parse_device_text_lines(bl_ctx* ctx, const uint8_t* d_text_in, uint64_t n_bytes, char first_byte, const char* ends, uint64_t ends_n, bl_batch** out,
+                               uint64_t* n_seqs, uint64_t* n_bases, bl_parse::LineIndex* lines);
 
 extern "C" int bl_batch_from_text(bl_ctx* ctx, const char* text, uint64_t n_bytes, bl_batch** out, uint64_t* n_seqs, uint64_t* n_bases)
 {
@@ -147,6 +151,13 @@ extern "C" int bl_batch_from_text(bl_ctx* ctx, const char* text, uint64_t n_byte
 int bl_parse_device_text(bl_ctx* ctx, const uint8_t* d_text_in, uint64_t n_bytes, char first_byte, const char* ends, uint64_t ends_n, bl_batch** out,
                          uint64_t* n_seqs, uint64_t* n_bases)
 {
+    return bl_parse_device_text_lines(ctx, d_text_in, n_bytes, first_byte, ends, ends_n, out, n_seqs, n_bases, nullptr);
+}
+
+int bl_parse_device_text_lines(bl_ctx* ctx, const uint8_t* d_text_in, uint64_t n_bytes, char first_byte, const char* ends, uint64_t ends_n, bl_batch** out,
+                               uint64_t* n_seqs, uint64_t* n_bases, bl_parse::LineIndex* lines)
+{
+    if (lines) *lines = bl_parse::LineIndex{};
     if (!ctx || !out || !d_text_in || !ends || ends_n == 0 || ends_n > n_bytes) return bl_set_error(BL_ERR_INVALID, "NULL argument");
     *out = nullptr;
     if (n_seqs) *n_seqs = 0;
@@ -293,6 +304,7 @@ int bl_parse_device_text(bl_ctx* ctx, const uint8_t* d_text_in, uint64_t n_bytes
     if (ragged) fixed_len = 0;
     handed_over = true;
     cleanup();
+    if (lines) *lines = bl_parse::LineIndex{d_line_end, d_hdr, d_rec, d_dst, n_lines, n_records, total, fastq ? 1 : 0};
     int rc = bl_batch_adopt_device(ctx, d_bases, total, reinterpret_cast<uint64_t*>(d_offsets), n_records, fixed_len, out);  // takes ownership of both
     if (rc != BL_OK) return rc;
     if (n_seqs) *n_seqs = n_records;

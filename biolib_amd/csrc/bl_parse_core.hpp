@@ -38,6 +38,14 @@ enum {
     ERR_MASK = 63
 };
 
+// What a parse leaves behind for the record index of bl_format.hip: the per-line arrays (device, the context's scratch) of the text
+// just parsed.  All zero where the text held no record.
+struct LineIndex {
+    const unsigned long long *line_end, *hdr, *rec_incl, *dst;  // [n_lines] (dst: n_lines + 1)
+    uint64_t n_lines, n_records, total;
+    int fastq;
+};
+
 // bit b set <=> text[at + b] == '\n', for the 16 bytes at `at` (a multiple of 16; text is 16-byte aligned).  Whole chunks are
 // tested four bytes at a time, the text's last partial chunk byte by byte: nothing behind text[n - 1] is read.
 BL_PDEV uint32_t newline_mask16(const uint8_t* text, uint64_t n, uint64_t at)

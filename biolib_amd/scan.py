@@ -179,6 +179,16 @@ class Context:
         check(self._lib.bl_batch_from_text(self._h, arr.ctypes.data_as(C.c_void_p) if arr.size else None, arr.size, C.byref(h), C.byref(ns), C.byref(nb)))
         return Batch(self, h)
 
+    def from_text_indexed(self, text):
+        """from_text that keeps the names and qualities on the device (bl_text_index_build): (Batch, TextIndex).  The batch is
+        from_text's, byte for byte, and carries its offsets on the device like the result of select; the index holds a device copy
+        of the text (about 2.3 times the bases for FASTQ) until it is closed, and is what Batch.format / Batch.write take as `index`."""
+        arr = np.frombuffer(text, dtype=np.uint8) if isinstance(text, (bytes, bytearray, memoryview)) else np.ascontiguousarray(text, dtype=np.uint8)
+        h, ix, ns, nb = C.c_void_p(), C.c_void_p(), C.c_uint64(), C.c_uint64()
+        check(self._lib.bl_text_index_build(self._h, arr.ctypes.data_as(C.c_void_p) if arr.size else None, arr.size, C.byref(h), C.byref(ix), C.byref(ns),
+                                            C.byref(nb)))
+        return _indexed_batch(self, h, ix)
+
     def from_tensor(self, t, offsets=None, read_len=0):
         """Wrap a uint8 CUDA tensor of ASCII bases (not copied; must stay alive)."""
         self._inputs_ready()
@@ -525,6 +535,80 @@ class _DeviceArray:
     """carrier of a __cuda_array_interface__ description (torch.as_tensor reads it without copying)"""
 
 
+def _device_view(ctx, ptr, shape, typestr):
+    """a tensor over library-owned device memory (no copy): valid while its owner is open"""
+    import torch
+
+    holder = _DeviceArray()
+    holder.__cuda_array_interface__ = dict(shape=tuple(shape), typestr=typestr, data=(int(ptr), False), version=2, strides=None)
+    return torch.as_tensor(holder, device=ctx.torch_device)
+
+
+class TextIndex:
+    """The names and qualities of a parsed text on the device (bl_text_index): what from_text_indexed and
+    Reader.device_batches(indexed=True) return beside the batch.  Close it (or its context) when done; it must outlive every
+    format that reads it."""
+
+    def __init__(self, ctx, handle):
+        self.ctx = ctx
+        self._h = handle
+        self._lib = ctx._lib
+        n, fq, t, nb, r = C.c_uint64(), C.c_int(), C.c_void_p(), C.c_uint64(), C.c_void_p()
+        check(self._lib.bl_text_index_info(handle, C.byref(n), C.byref(fq), C.byref(t), C.byref(nb), C.byref(r)))
+        self.n_records, self.is_fastq, self.n_bytes = int(n.value), bool(fq.value), int(nb.value)
+        self._d_text, self._d_records = t.value, r.value
+        ctx._tables.add(self)
+
+    def close(self):
+        if getattr(self, "_h", None):
+            if getattr(self.ctx, "_h", None):
+                self._lib.bl_text_index_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    @property
+    def offsets(self):
+        """int64 device tensor [n_records + 1]: the offsets of the batch the index was built with, a view of the index's array"""
+        return _device_view(self.ctx, self._lib.bl_text_index_offsets(self._h), (self.n_records + 1,), "<i8")
+
+    def text(self):
+        """the indexed text, downloaded"""
+        if not self.n_bytes:
+            return b""
+        self.ctx.sync()
+        return _device_view(self.ctx, self._d_text, (self.n_bytes,), "|u1").cpu().numpy().tobytes()
+
+    def records(self):
+        """the 16-byte records, downloaded: a numpy structured array (capi.TEXT_RECORD_DTYPE)"""
+        if not self.n_records:
+            return np.zeros(0, dtype=capi.TEXT_RECORD_DTYPE)
+        self.ctx.sync()
+        return _device_view(self.ctx, self._d_records, (self.n_records, 2), "<i8").cpu().numpy().view(capi.TEXT_RECORD_DTYPE).reshape(-1).copy()
+
+    def names(self):
+        """a host list of the names (bytes: the header lines without marker and terminator) — for tests; the writer never needs it"""
+        text = self.text()
+        return [text[int(r["name_begin"]):int(r["name_begin"]) + int(r["name_len"])] for r in self.records()]
+
+
+def _indexed_batch(ctx, h, ix):
+    """(Batch, TextIndex) of the two handles bl_text_index_build returns: the batch gets a device copy of the index's offsets"""
+    index = TextIndex(ctx, ix)
+    b = Batch(ctx, h)
+    d_offsets = index.offsets.clone()
+    n, total = b.n_seqs, b.n_bases
+    if n > 1 and total and total % n == 0 and bool((d_offsets[1:] - d_offsets[:-1] == total // n).all()):
+        b.read_len = total // n  # the library's rule: more than one sequence, all equally long
+    b._d_offsets = d_offsets
+    b._offsets_from_device = True
+    return b, index
+
+
 class CountTable:
     """Sorted distinct keys with 32-bit counts and a prefix index on the device (bl_table).  Close it (or its context) when done; it
     must outlive every asynchronous kmer_counts that reads it."""
@@ -728,6 +812,13 @@ class Unitigs:
     def __init__(self, batch, offsets, count_sums, nodes, stats, n_unitigs, n_bases):
         self.batch, self.offsets, self.count_sums, self.nodes, self.stats = batch, offsets, count_sums, nodes, stats
         self.n_unitigs, self.n_bases = n_unitigs, n_bases
+
+    def write_fasta(self, path, line_width=0):
+        """The unitigs as a FASTA file made on the device (Batch.write): names 0, 1, ... with " LN:i:<bases> KC:i:<count sum>" — BCALM's
+        header without its km and L fields (no floats, no links: GFA and unitig links are not built).  Returns the bytes written."""
+        if self.batch is None:
+            raise ValueError("unitigs(batch=False) holds no strings to write")
+        return self.batch.write(path, fmt="fasta", tags=self.count_sums if self.n_unitigs else None, tag_label="KC:i:", tag_length=True, line_width=line_width)
 
 
 class ReadCounts:
@@ -1103,6 +1194,62 @@ class Batch:
         b._d_offsets = d_out
         b._offsets_from_device = True
         return b, source_index[:n_out]
+
+    # ---- leaving the device: FASTA / FASTQ text
+    def format_raw(self, rule, out=None, capacity=0, index=None, source_index=None, spans=None, tags=None, offsets=None):
+        """bl_batch_format: `rule` a capi.FormatRule, `out` a uint8 device tensor (None: sizing only) of `capacity` bytes, `index` a
+        TextIndex or None, the arrays 64-bit device tensors or None.  Synchronous.  Returns (n_bytes, n_records); the library checks
+        every argument."""
+        nb, nr = C.c_uint64(), C.c_uint64()
+        check(self._lib.bl_batch_format(self.ctx._h, self._h, _ptr(offsets), index._h if index is not None else None, _ptr(source_index), _ptr(spans), _ptr(tags),
+                                        C.byref(rule), _ptr(out), int(capacity), C.byref(nb), C.byref(nr)))
+        return int(nb.value), int(nr.value)
+
+    @staticmethod
+    def format_rule(fmt="fastq", tag_label="", prefix="", first_number=0, line_width=0, quality_fill="I", skip_empty=False, tag_length=False):
+        r = capi.FormatRule()
+        r.format = {"fasta": capi.FORMAT_FASTA, "fastq": capi.FORMAT_FASTQ}[fmt] if isinstance(fmt, str) else int(fmt)
+        r.flags = (capi.FORMAT_SKIP_EMPTY if skip_empty else 0) | (capi.FORMAT_TAG_LENGTH if tag_length else 0)
+        r.line_width = int(line_width)
+        r.quality_fill = quality_fill if isinstance(quality_fill, int) else (quality_fill.encode("latin1") if isinstance(quality_fill, str) else bytes(quality_fill))[0]
+        r.name_prefix = prefix.encode("latin1") if isinstance(prefix, str) else bytes(prefix)  # (16 bytes without a NUL reach the library, which refuses them)
+        r.first_number = int(first_number) & (2**64 - 1)
+        r.tag_label = tag_label.encode("latin1") if isinstance(tag_label, str) else bytes(tag_label)
+        return r
+
+    def format(self, fmt="fastq", index=None, source_index=None, spans=None, tags=None, tag_label="", prefix="", first_number=0, line_width=0, quality_fill="I",
+               skip_empty=False, tag_length=False):
+        """This batch as FASTA / FASTQ text made on the device (bl_batch_format): a uint8 device tensor.  Sequence i becomes
+        marker, name, tags, the bases (FASTA: wrapped at line_width) and for FASTQ "+" and the quality.
+        index         a TextIndex: names (and for FASTQ qualities) come from the indexed text; without one, names are generated,
+                      prefix + decimal(first_number + source read), and the quality is quality_fill
+        source_index  int64 device tensor [n_seqs]: the indexed read of every sequence (what select returned); None: sequence i is read i
+        spans         int64 device tensor [index.n_records, 2]: the spans that went into select — the quality is cut at their begins;
+                      a batch made by apply_edits takes the spans and index of the batch it came from
+        tags          int64 device tensor [n_seqs] (uint64 bits): appends " " + tag_label + decimal(tags[i]); tag_length appends " LN:i:" + length
+        skip_empty    drop empty sequences (otherwise they are written with empty lines, so that mates stay in step)"""
+        import torch
+
+        rule = self.format_rule(fmt, tag_label, prefix, first_number, line_width, quality_fill, skip_empty, tag_length)
+        n = self.n_seqs
+        for name, t, count in (("source_index", source_index, n), ("tags", tags, n), ("spans", spans, None)):
+            if t is not None and not (isinstance(t, torch.Tensor) and t.is_cuda and t.element_size() == 8 and t.is_contiguous() and (count is None or t.numel() >= count)):
+                raise ValueError(name + ": a contiguous 64-bit device tensor")
+        if spans is not None and (index is None or spans.numel() < 2 * index.n_records):
+            raise ValueError("spans: one (begin, end) pair per record of the index")
+        d_offsets = self._device_offsets(None)
+        self.ctx._inputs_ready()
+        n_bytes, _ = self.format_raw(rule, None, 0, index, source_index, spans, tags, d_offsets)
+        out = torch.empty(max(n_bytes, 1), dtype=torch.uint8, device=self.ctx.torch_device)
+        self.format_raw(rule, out, n_bytes, index, source_index, spans, tags, d_offsets)
+        return out[:n_bytes]
+
+    def write(self, path, append=False, **how):
+        """format(**how) written to `path` (bl_text_write: the download in chunks through two pinned buffers, a chunk written while the
+        next copies; no compression).  Returns the bytes written."""
+        text = self.format(**how)
+        check(self._lib.bl_text_write(self.ctx._h, _ptr(text) if text.numel() else None, text.numel(), str(path).encode(), 1 if append else 0))
+        return int(text.numel())
 
     def read_spans_raw(self, records, rule, spans, stat=None, offsets=None):
         """bl_read_spans: `records` are the whole-batch records of read_counts_raw, `rule` a capi.SpanRule, `spans` takes n_seqs pairs of
@@ -1530,9 +1677,16 @@ class Reader:
             check(rc)
             yield C.string_at(p.value, n.value)
 
-    def device_batches(self, ctx, max_text_bytes=0):
+    def device_batches(self, ctx, max_text_bytes=0, indexed=False):
         """yield Batch objects parsed ON THE DEVICE from spans of the decompressed text (regular FASTA / 4-line FASTQ only;
-        names are not kept): parallel inflate -> one H2D copy -> bl_batch_from_text"""
+        names are not kept): parallel inflate -> one H2D copy -> bl_batch_from_text.  indexed=True: yield (Batch, TextIndex) — the same
+        spans, every batch with the names and qualities of its text (bl_reader_next_batch_device_indexed), for Batch.write(append=True)"""
+        while indexed:
+            b, ix, ns, nb = C.c_void_p(), C.c_void_p(), C.c_uint64(), C.c_uint64()
+            check(self._lib.bl_reader_next_batch_device_indexed(ctx._h, self._h, int(max_text_bytes), C.byref(b), C.byref(ix), C.byref(ns), C.byref(nb)))
+            if not b.value:
+                return
+            yield _indexed_batch(ctx, b, ix)
         while True:
             b, ns, nb = C.c_void_p(), C.c_uint64(), C.c_uint64()
             check(self._lib.bl_reader_next_batch_device(ctx._h, self._h, int(max_text_bytes), C.byref(b), C.byref(ns), C.byref(nb)))

@@ -57,7 +57,8 @@ enum {
     BL_ERR_OOM = -3,         /* device or pinned-host allocation failed */
     BL_ERR_CAPACITY = -4,    /* output arrays too small: result.count says how many records exist */
     BL_ERR_NO_DEVICE = -5,   /* no gfx950 device visible */
-    BL_ERR_INTERNAL = -6     /* an internal consistency check failed (never expected; results invalid) */
+    BL_ERR_INTERNAL = -6,    /* an internal consistency check failed (never expected; results invalid) */
+    BL_ERR_IO = -7           /* bl_text_write: the file could not be opened, or a write came back short */
 };
 
 enum {
@@ -564,7 +565,8 @@ int bl_select_read_counts(bl_ctx* ctx, const bl_batch* batch, uint64_t first, ui
  *               or n_seqs empty ones under BL_SELECT_KEEP_EMPTY.
  *   d_out_offsets    (nullable) takes the result's n_seqs_out + 1 offsets; room for the SOURCE's n_seqs + 1 entries
  *   d_source_index   (nullable) takes n_seqs_out entries, the source sequence of every result sequence (the identity under
- *                    BL_SELECT_KEEP_EMPTY); room for the source's n_seqs entries.  The hook for names and qualities kept on the host.
+ *                    BL_SELECT_KEEP_EMPTY); room for the source's n_seqs entries.  The hook for names and qualities: bl_batch_format takes
+ *                    it with the index of the source's text, or the host keeps them.
  *   n_seqs_out, n_bases_out   (nullable) host words
  * Synchronous (the total is needed on the host to allocate); the call first waits for the context's scans in flight, so spans made by
  * bl_read_spans behind a bl_scan_read_counts need no sync.  Temporaries come from the context's scratch.
@@ -709,6 +711,77 @@ int bl_table_unitigs(bl_ctx* ctx, const bl_table* table, uint32_t k, bl_batch** 
                      bl_unitig_node* d_nodes /* n, nullable */, uint64_t* n_unitigs, uint64_t* n_bases,
                      bl_graph_stats* stats /* nullable */);
 
+/* The chain's exit: reads and unitigs leave as FASTA / FASTQ text made on the device, names and qualities included.
+ *
+ * bl_text_index_build is bl_batch_from_text that keeps what that call drops.  It accepts and refuses exactly the same texts with the same
+ * messages, and its batch equals bl_batch_from_text's byte for byte (bases, offsets, the fixed-length rule).  The index owns
+ *   - a device copy of the text in a buffer of its own.  This costs memory: the text stays resident beside the batch, about 2.3 times
+ *     the bases for FASTQ, until bl_text_index_destroy
+ *   - one 16-byte record per sequence: name_begin (u64, the first byte behind '@' / '>'), name_len (u32, the header line without marker
+ *     and terminator, one trailing '\r' dropped) and qual_delta (u32, the quality line's first byte minus name_begin; 0 for FASTA).  No
+ *     quality length: it is the sequence's, by the parser's own check.  A record whose name_len or qual_delta does not fit 32 bits is
+ *     refused with BL_ERR_INVALID
+ *   - the n_records + 1 offsets of the batch it was built with (bl_text_index_offsets, device words): what a ragged batch needs as
+ *     d_offsets, and where the writer reads a source read's length.
+ * bl_text_index_info: every output nullable; d_records points at the 16-byte records.  bl_text_index_destroy waits for the context's
+ * stream first.  An index must be destroyed before its context.
+ * bl_reader_next_batch_device_indexed cuts a file's text exactly as bl_reader_next_batch_device does and returns every span's batch with
+ * its index (*out_batch NULL at the end of the file), so that a file larger than memory is rewritten span by span.
+ *
+ * bl_batch_format writes sequence i of `batch` (length L, offsets as bl_batch_select takes them) as one record:
+ *     marker name [" LN:i:" L] [" " tag_label d_tags[i]] '\n'  bases  '\n'            and for FASTQ     "+\n" quality '\n'
+ *   marker     '>' or '@' by rule->format, whatever the indexed text was: FASTQ -> FASTA and FASTA -> FASTQ are both legal.  All
+ *              terminators are LF.
+ *   source     s = d_source_index[i], or i where that is NULL.  With an index and s below its record count the name is the record's bytes
+ *              of the text; otherwise it is generated, name_prefix + decimal(first_number + s), the quality is the fill, and no record
+ *              of the index is read for s.
+ *   tags       BL_FORMAT_TAG_LENGTH appends " LN:i:" + decimal(L); d_tags appends " " + tag_label + decimal(d_tags[i]).
+ *   bases      the L bytes of the batch verbatim.  FASTA with line_width W > 0: a '\n' behind every W bases and no empty line where W
+ *              divides L; an empty sequence is one empty line.
+ *   quality    with a FASTQ index: the text's bytes [q + b, q + b + L) where q is record s's quality start and b = d_spans[2s] (0 with
+ *              d_spans NULL) — d_spans are the (begin, end) pairs that went into bl_batch_select, one per record of the index.
+ *              bl_batch_apply_edits keeps the geometry: a corrected batch takes the spans and index of the batch it came from.
+ *              A position at or behind the quality line's end, or outside the text, gives quality_fill.  Without index qualities:
+ *              quality_fill L times.
+ *   empty      BL_FORMAT_SKIP_EMPTY drops sequences of length 0; otherwise they are written with empty lines (as
+ *              BL_SELECT_KEEP_EMPTY leaves them: mates stay in step).
+ * *n_bytes always receives the size of the text, *n_records the number of records written (both nullable).  d_out NULL: sizing only.
+ * capacity < *n_bytes: BL_ERR_CAPACITY, d_out untouched.  No byte at or behind d_out[*n_bytes] is ever written.  Synchronous like
+ * bl_batch_select; it first waits for the context's scans in flight.  Results are bit-reproducible: no atomic decides a placement.
+ * The arrays are trusted for content, not for safety (select's policy): offsets are clamped to the batch, name and quality places to the
+ * text; no byte behind the batch's n_bases or the text's n_bytes is read.
+ * BL_ERR_INVALID with a message, nothing launched: a NULL ctx, batch or rule; a batch or index of another context; d_offsets NULL on a
+ * ragged batch; an unknown format or flag; line_width with FASTQ; quality_fill outside 33 .. 126; name_prefix or tag_label without a NUL
+ * inside its 16 bytes; reserved != 0; d_spans or d_out not 16-byte aligned.
+ *
+ * bl_text_write downloads d_text[0, n_bytes) in chunks through two pinned buffers and writes chunk c while chunk c + 1 copies, behind
+ * the work on the context's stream.  append != 0 appends.  BL_ERR_IO where the file cannot be opened or a write comes back short.
+ * No compression: BGZF deflate on the device is NOT built. */
+typedef struct bl_text_index bl_text_index;
+int bl_text_index_build(bl_ctx* ctx, const char* text, uint64_t n_bytes, bl_batch** out_batch, bl_text_index** out_index, uint64_t* n_seqs,
+                        uint64_t* n_bases);
+int bl_text_index_info(const bl_text_index* index, uint64_t* n_records, int* is_fastq, const uint8_t** d_text, uint64_t* n_bytes,
+                       const void** d_records);
+const uint64_t* bl_text_index_offsets(const bl_text_index* index);
+int bl_text_index_destroy(bl_text_index* index);
+int bl_reader_next_batch_device_indexed(bl_ctx* ctx, bl_reader* reader, uint64_t max_text_bytes, bl_batch** out_batch, bl_text_index** out_index,
+                                        uint64_t* n_seqs, uint64_t* n_bases);
+enum { BL_FORMAT_FASTA = 0, BL_FORMAT_FASTQ = 1 };
+enum { BL_FORMAT_SKIP_EMPTY = 1u << 0, BL_FORMAT_TAG_LENGTH = 1u << 1 };
+typedef struct bl_format_rule {
+    uint32_t format, flags;
+    uint32_t line_width;      /* FASTA: bases per line, 0 = one line; must be 0 for FASTQ */
+    uint32_t quality_fill;    /* FASTQ without index qualities: this byte, 33..126 */
+    char     name_prefix[16]; /* generated names: prefix + decimal(first_number + s), NUL-terminated */
+    uint64_t first_number;
+    char     tag_label[16];   /* with d_tags: " " + tag_label + decimal(d_tags[i]), e.g. "KC:i:" */
+    uint64_t reserved;        /* 0 */
+} bl_format_rule;
+int bl_batch_format(bl_ctx* ctx, const bl_batch* batch, const uint64_t* d_offsets, const bl_text_index* index /* nullable */,
+                    const uint64_t* d_source_index /* nullable */, const uint64_t* d_spans /* nullable */, const uint64_t* d_tags /* nullable */,
+                    const bl_format_rule* rule, uint8_t* d_out, uint64_t capacity, uint64_t* n_bytes, uint64_t* n_records);
+int bl_text_write(bl_ctx* ctx, const uint8_t* d_text, uint64_t n_bytes, const char* path, int append);
+
 /* Count reduction across the GPUs of one node: ctxs[g] is the context of device g (all distinct devices),
  * counters holds n_gpu rows of n 64-bit counters — row g = GPU g's local counts in, the column sums out (in every row).  One
  * ncclAllReduce(sum, uint64) per GPU over RCCL / xGMI, called on RCCL's C API directly (librccl.so.1 is loaded on first use);
@@ -836,7 +909,8 @@ int bl_clock_probe_finish(bl_clock_probe* probe, double* shader_ghz);
 /* Device-side parser: copy raw FASTA / FASTQ TEXT (already in host memory, e.g. a read()/mmap of the file) to the GPU
  * and build the batch there: newline index, line classification, prefix sums, gather of the sequence lines.  Same
  * sequences as bl_reader_* for the regular layouts it accepts — FASTQ with exactly 4 lines per record, FASTA with any
- * line wrapping, LF or CRLF — and BL_ERR_INVALID for anything else (never a silent mis-parse).  Names are not kept. */
+ * line wrapping, LF or CRLF — and BL_ERR_INVALID for anything else (never a silent mis-parse).  Names are not kept
+ * (bl_text_index_build keeps them, and the qualities, on the device). */
 int bl_batch_from_text(bl_ctx* ctx, const char* text, uint64_t n_bytes, bl_batch** out, uint64_t* n_seqs, uint64_t* n_bases);
 
 /* ---- spill / wire formats read by biolib's consumers -------------------------------------
