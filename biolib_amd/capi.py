@@ -28,7 +28,7 @@ SYMBOLS = [
     "bl_table_build_u64", "bl_table_build_u128", "bl_table_destroy", "bl_table_info", "bl_table_arrays", "bl_table_lookup_u64", "bl_table_lookup_u128",
     "bl_table_histogram", "bl_scan_kmer_counts", "bl_scan_read_counts", "bl_table_combine", "bl_table_filter",
     "bl_select_read_counts", "bl_batch_select", "bl_read_spans", "bl_scan_read_edits", "bl_batch_apply_edits",
-    "bl_table_adjacency", "bl_table_unitigs",
+    "bl_table_adjacency", "bl_table_unitigs", "bl_unitig_links", "bl_unitigs_format_gfa",
     "bl_text_index_build", "bl_text_index_info", "bl_text_index_offsets", "bl_text_index_destroy", "bl_reader_next_batch_device_indexed", "bl_batch_format",
     "bl_text_write",
 ]
@@ -116,6 +116,25 @@ class FormatRule(C.Structure):
 LINK_NONE = 0xFFFFFFFF
 # bl_unitig_node as a numpy record
 UNITIG_NODE_DTYPE = [("unitig", "<u4"), ("rank_flip", "<u4")]
+
+LINKS_ONCE = 1
+GFA_NO_HEADER = 1
+# bl_unitig_link as a numpy record: (unitig << 1) | orientation, 0 for + and 1 for -
+UNITIG_LINK_DTYPE = [("from", "<u4"), ("to", "<u4")]
+
+
+class LinkStats(C.Structure):
+    """bl_link_stats"""
+    _fields_ = [(name, C.c_uint64) for name in ("n_ends", "n_links", "n_self_reverse", "n_dead_ends", "n_branch_ends")] + [("reserved", C.c_uint64 * 3)]
+
+    def as_dict(self):
+        return {name: int(getattr(self, name)) for name, _ in self._fields_ if name != "reserved"}
+
+
+class GfaRule(C.Structure):
+    """bl_gfa_rule (40 bytes)"""
+    _fields_ = [("flags", C.c_uint32), ("k", C.c_uint32), ("name_prefix", C.c_char * 16), ("first_number", C.c_uint64), ("reserved", C.c_uint64)]
+
 
 TABLE_UNION, TABLE_INTERSECT, TABLE_SUBTRACT, TABLE_COUNT_SUBTRACT = 0, 1, 2, 3
 COUNT_SUM, COUNT_MIN, COUNT_MAX, COUNT_LEFT, COUNT_RIGHT = 0, 1, 2, 3, 4
@@ -274,6 +293,9 @@ def lib():
     if "BIOLIB_AMD_LIB" not in os.environ or hasattr(L, "bl_table_adjacency"):
         L.bl_table_adjacency.argtypes = [vp, vp, u32, vp, vp, C.POINTER(GraphStats)]
         L.bl_table_unitigs.argtypes = [vp, vp, u32, C.POINTER(vp), vp, vp, vp, C.POINTER(u64), C.POINTER(u64), C.POINTER(GraphStats)]
+    if "BIOLIB_AMD_LIB" not in os.environ or hasattr(L, "bl_unitig_links"):
+        L.bl_unitig_links.argtypes = [vp, vp, u32, vp, vp, u64, u32, vp, vp, u64, C.POINTER(u64), C.POINTER(LinkStats)]
+        L.bl_unitigs_format_gfa.argtypes = [vp, vp, vp, u64, vp, vp, u64, C.POINTER(GfaRule), vp, u64, C.POINTER(u64)]
     if "BIOLIB_AMD_LIB" not in os.environ or hasattr(L, "bl_batch_format"):
         L.bl_text_index_build.argtypes = [vp, vp, u64, C.POINTER(vp), C.POINTER(vp), C.POINTER(u64), C.POINTER(u64)]
         L.bl_text_index_info.argtypes = [vp, C.POINTER(u64), C.POINTER(C.c_int), C.POINTER(vp), C.POINTER(u64), C.POINTER(vp)]

@@ -771,7 +771,16 @@ class CountTable:
                                          C.byref(nu), C.byref(nb), C.byref(stats) if stats is not None else None))
         return (h if batch else None), int(nu.value), int(nb.value)
 
-    def unitigs(self, k, nodes=False, batch=True):
+    def unitig_links_raw(self, k, nodes, offsets, n_unitigs, flags=0, link_offsets=None, links=None, capacity=0, stats=None):
+        """bl_unitig_links: `nodes` / `offsets` are what unitigs_raw filled for this table and k, `link_offsets` (or None) takes
+        2 * n_unitigs + 1 64-bit words, `links` (None: sizing only) `capacity` 8-byte records, `stats` (or None) is a capi.LinkStats.
+        Returns n_links.  Synchronous; the library checks every argument."""
+        nl = C.c_uint64()
+        check(self._lib.bl_unitig_links(self.ctx._h, self._h, int(k), _ptr(nodes), _ptr(offsets), int(n_unitigs), int(flags), _ptr(link_offsets), _ptr(links),
+                                        int(capacity), C.byref(nl), C.byref(stats) if stats is not None else None))
+        return int(nl.value)
+
+    def unitigs(self, k, nodes=False, batch=True, links=False, once=False):
         """The unitigs of this table of canonical k-mers (k odd, at most 63): its non-branching paths and cycles compacted on the device,
         every key in exactly one (bl_table_unitigs; the header states the start and orientation rules).  Returns a Unitigs:
         .batch       a device-resident Batch of the unitig strings (L + k - 1 uppercase bases for L keys), numbered by the slot of their
@@ -784,13 +793,20 @@ class CountTable:
         .nodes       with nodes=True an int32 device tensor [n_distinct, 2] (uint32 words): the unitig of every key and
                      (rank << 1) | flip — its place counted from the start key, and whether it is read reverse-complemented
         .stats       n_unitigs, n_cycles and longest_unitig (in keys) besides the six of adjacency
+        With links=True (k >= 3; bl_unitig_links, the header states the definitions) also the edges between unitig ends:
+        .link_offsets  int64 device tensor [2 * n_unitigs + 1]: end e = (unitig << 1) | orientation (0 for +, 1 for -) has the records
+                       link_offsets[e] .. link_offsets[e + 1]
+        .links         int32 device tensor [n_links, 2] (uint32 words): (from, to), both ends as numbered above — the last k - 1 bases of
+                       unitig from >> 1 read in orientation from & 1 are the first k - 1 of unitig to >> 1 read in orientation to & 1.
+                       once=True keeps one record of each reverse pair (from <= to ^ 1)
+        .link_stats    n_ends, n_links, n_self_reverse, n_dead_ends, n_branch_ends
         Filter the table first (filter(2)) to compact the graph of the solid k-mers."""
         import torch
 
         n, dev = self.n_distinct, self.ctx.torch_device
         offsets = torch.empty(n + 1, dtype=torch.int64, device=dev)
         sums = torch.empty(max(n, 1), dtype=torch.int64, device=dev)
-        d_nodes = torch.empty((max(n, 1), 2), dtype=torch.int32, device=dev) if nodes else None
+        d_nodes = torch.empty((max(n, 1), 2), dtype=torch.int32, device=dev) if nodes or links else None
         st = capi.GraphStats()
         self.ctx._inputs_ready()
         h, n_unitigs, n_bases = self.unitigs_raw(k, batch, offsets, sums, d_nodes, st)
@@ -803,22 +819,72 @@ class CountTable:
             b = Batch(self.ctx, h, read_len=fixed)
             b._d_offsets = d_out
             b._offsets_from_device = True
-        return Unitigs(b, d_out, sums[:n_unitigs], d_nodes[:n] if nodes else None, st.as_dict(), n_unitigs, n_bases)
+        u = Unitigs(b, d_out, sums[:n_unitigs], d_nodes[:n] if nodes else None, st.as_dict(), n_unitigs, n_bases)
+        u.k, u._ctx, u._lib = int(k), self.ctx, self._lib
+        if links:
+            # the header's identity gives the record count before the call: one search pass, no sizing call
+            bound = int(st.n_arcs) - int(st.n_linked_sides) + 2 * int(st.n_cycles)
+            link_offsets = torch.empty(2 * n_unitigs + 1, dtype=torch.int64, device=dev)
+            d_links = torch.empty((max(bound, 1), 2), dtype=torch.int32, device=dev)
+            ls = capi.LinkStats()
+            n_links = self.unitig_links_raw(k, d_nodes, d_out, n_unitigs, capi.LINKS_ONCE if once else 0, link_offsets, d_links, bound, ls)
+            u.link_offsets, u.links, u.link_stats = link_offsets, d_links[:n_links], ls.as_dict()
+        return u
 
 
 class Unitigs:
-    """What CountTable.unitigs returns: batch, offsets, count_sums, nodes, stats (and n_unitigs, n_bases)."""
+    """What CountTable.unitigs returns: batch, offsets, count_sums, nodes, stats (and n_unitigs, n_bases); with links=True also
+    link_offsets, links and link_stats."""
 
     def __init__(self, batch, offsets, count_sums, nodes, stats, n_unitigs, n_bases):
         self.batch, self.offsets, self.count_sums, self.nodes, self.stats = batch, offsets, count_sums, nodes, stats
         self.n_unitigs, self.n_bases = n_unitigs, n_bases
+        self.link_offsets = self.links = self.link_stats = None
+        self.k, self._ctx, self._lib = None, None, None
 
     def write_fasta(self, path, line_width=0):
         """The unitigs as a FASTA file made on the device (Batch.write): names 0, 1, ... with " LN:i:<bases> KC:i:<count sum>" — BCALM's
-        header without its km and L fields (no floats, no links: GFA and unitig links are not built).  Returns the bytes written."""
+        header without its km and L fields (no floats; the links between unitigs leave through write_gfa).  Returns the bytes written."""
         if self.batch is None:
             raise ValueError("unitigs(batch=False) holds no strings to write")
         return self.batch.write(path, fmt="fasta", tags=self.count_sums if self.n_unitigs else None, tag_label="KC:i:", tag_length=True, line_width=line_width)
+
+    def format_gfa_raw(self, rule, out=None, capacity=0):
+        """bl_unitigs_format_gfa: `rule` a capi.GfaRule, `out` a uint8 device tensor (None: sizing only) of `capacity` bytes.  Synchronous.
+        Returns n_bytes; the library checks every argument."""
+        nb = C.c_uint64()
+        n_links = int(self.links.shape[0]) if self.links is not None else 0
+        check(self._lib.bl_unitigs_format_gfa(self._ctx._h, self.batch._h, _ptr(self.offsets), int(self.n_unitigs), _ptr(self.count_sums) if self.n_unitigs else None,
+                                              _ptr(self.links) if n_links else None, n_links, C.byref(rule), _ptr(out), int(capacity), C.byref(nb)))
+        return int(nb.value)
+
+    def format_gfa(self, prefix="", first_number=0, header=True):
+        """The unitigs and their links as GFA 1 text made on the device (bl_unitigs_format_gfa): a uint8 device tensor.  One H line
+        (header=False: none), one S line per unitig — name prefix + decimal(first_number + u), the bases, LN:i: and KC:i: (the count
+        sum) — and one L line per link record with the overlap (k - 1)M.  Needs unitigs(k, links=True); once=True writes every edge
+        once."""
+        import torch
+
+        if self.batch is None:
+            raise ValueError("unitigs(batch=False) holds no strings to write")
+        if self.links is None:
+            raise ValueError("unitigs(links=False) holds no links to write")
+        rule = capi.GfaRule()
+        rule.flags = 0 if header else capi.GFA_NO_HEADER
+        rule.k = self.k
+        rule.name_prefix = prefix.encode("latin1") if isinstance(prefix, str) else bytes(prefix)  # (16 bytes without a NUL reach the library, which refuses them)
+        rule.first_number = int(first_number) & (2**64 - 1)
+        self._ctx._inputs_ready()
+        n_bytes = self.format_gfa_raw(rule)
+        out = torch.empty(max(n_bytes, 1), dtype=torch.uint8, device=self._ctx.torch_device)
+        self.format_gfa_raw(rule, out, n_bytes)
+        return out[:n_bytes]
+
+    def write_gfa(self, path, prefix="", first_number=0, header=True):
+        """format_gfa(...) written to `path` (bl_text_write, as Batch.write).  Returns the bytes written."""
+        text = self.format_gfa(prefix, first_number, header)
+        check(self._lib.bl_text_write(self._ctx._h, _ptr(text) if text.numel() else None, text.numel(), str(path).encode(), 0))
+        return int(text.numel())
 
 
 class ReadCounts:

@@ -711,6 +711,69 @@ int bl_table_unitigs(bl_ctx* ctx, const bl_table* table, uint32_t k, bl_batch** 
                      bl_unitig_node* d_nodes /* n, nullable */, uint64_t* n_unitigs, uint64_t* n_bases,
                      bl_graph_stats* stats /* nullable */);
 
+/* The compacted graph as a graph: which unitig end continues into which other unitig, in which orientation (what Bandage, assemblers,
+ * variant callers and tip / bubble removal read), and the whole as GFA 1 text.
+ * SCOPE  the graph of bl_table_unitigs, k odd, 3 <= k <= 63.  k = 1 is refused: two bases can lead to one key there, so two mask bits of
+ *   one side could name the same neighbour side; for k >= 3 they cannot, and link records are unique.
+ * ENDS  unitig u of L keys has two ends.  Its + end is the side by which the walk leaves its last key (rank L - 1): that key's right side
+ *   where its flip is 0, its left side where it is 1.  Its - end is the side by which the walk entered its first key (rank 0): the left
+ *   side where flip is 0, the right side where it is 1.  In one formula, the end at side s of a key with flip f has orientation
+ *   o = (s == left) XOR f, and ends are numbered e = (u << 1) | o, 0 for + and 1 for -.  A cycle's two ends are its start key's left side
+ *   (the cut link) and the out side of its last key.
+ * LINKS  for every end e = (key i, side s) and every set bit c of that side's mask nibble (MASK above), in ascending c, there is one
+ *   record {from, to}: from = e; with (j, t) the neighbour as MASK defines it, to = (unitig(j) << 1) | ((t == right) XOR flip(j)).  (j, t)
+ *   is always an end of its unitig.  `to` is read exactly like `from`: the record (u, a) -> (v, b) says that the last k - 1 bases of u
+ *   read in orientation a equal the first k - 1 bases of v read in orientation b (- : reverse-complemented).  The reverse
+ *   (to ^ 1, from ^ 1) of every record is a record too; a record equal to its own reverse (a hairpin, u+ -> u-) appears once.  A pure
+ *   cycle yields u+ -> u+ and u- -> u-.  n_links = n_arcs - n_linked_sides + 2 * n_cycles of bl_graph_stats.
+ * CSR  d_link_offsets[e], e in 0 .. 2 * n_unitigs, is the index of end e's first record; records are stored in ascending e, then
+ *   ascending c.  BL_LINKS_ONCE keeps a record iff from <= (to ^ 1): one of each reverse pair, a self-reverse record once; the offsets
+ *   then count the kept records only.
+ *
+ * bl_unitig_links: d_nodes (n = n_distinct records) and d_unitig_offsets (n_unitigs + 1 words) are what bl_table_unitigs wrote for the
+ *   same table and k.  The canonical-keys check is not repeated: the nodes prove that bl_table_unitigs accepted the table.  They are
+ *   trusted for content, not for safety (select's policy): a node whose unitig is at or above n_unitigs is ignored (it names no end and
+ *   no record), a rank is only compared; no byte outside the arrays' stated sizes is read or written.  Synchronous; temporaries come from
+ *   the context's scratch (36 bytes per end).  *n_links (nullable) is always written: 0 on a refusal, else the number of records (behind
+ *   BL_LINKS_ONCE where set).  d_links NULL: sizing only.  capacity < *n_links: BL_ERR_CAPACITY, d_links untouched.  No record at or
+ *   behind d_links[*n_links] is written.  d_link_offsets (nullable, 2 * n_unitigs + 1 words) is written whenever the call gets as far as
+ *   the count: by a sizing call and in front of BL_ERR_CAPACITY too.  stats (nullable, host): n_ends = 2 * n_unitigs; n_links as
+ *   *n_links; n_self_reverse, the records equal to their own reverse; n_dead_ends / n_branch_ends, the ends with no record / with two or
+ *   more — both counted before BL_LINKS_ONCE drops anything.  No atomic decides a placement: a rerun is bit-identical.
+ *   BL_ERR_INVALID with a message, nothing launched: NULL ctx or table; a table of another context; k even, 0, 1 or above 63; 2k above
+ *   the table's key_bits; a table of one-word keys with k > 31; 2^31 keys or more; unknown flags; n_unitigs above n_distinct; d_nodes or
+ *   d_unitig_offsets NULL on a table that is not empty.
+ * bl_unitigs_format_gfa writes GFA 1 text, every terminator LF:
+ *     H\tVN:Z:1.0\n                                                       unless BL_GFA_NO_HEADER
+ *     S\t<name u>\t<bases>\tLN:i:<bases' length>[\tKC:i:<d_count_sums[u]>]\n   for u = 0 .. n_unitigs - 1
+ *     L\t<name from >> 1>\t<+|->\t<name to >> 1>\t<+|->\t<k - 1>M\n            for every record, in array order
+ *   A name is name_prefix + decimal(first_number + u), 64-bit wrap as in bl_batch_format.  `unitigs` and d_unitig_offsets are
+ *   bl_table_unitigs's batch and offsets, d_links (NULL iff n_links == 0) bl_unitig_links's records with either flag value.  Sizing and
+ *   refusals follow bl_batch_format: *n_bytes (nullable) always receives the size of the text; d_out NULL: sizing only; capacity <
+ *   *n_bytes: BL_ERR_CAPACITY, d_out untouched; no byte at or behind d_out[*n_bytes] is written; no byte behind the batch's n_bases is
+ *   read (offsets are clamped to it; a link word only becomes a printed number).  bl_text_write carries the text to a file unchanged.
+ *   BL_ERR_INVALID with a message, nothing launched: NULL ctx, unitigs or rule; a batch of another context; unknown flags; rule->k even
+ *   or outside 3 .. 63; name_prefix without a NUL inside its 16 bytes; reserved != 0; d_out not 16-byte aligned; d_unitig_offsets NULL
+ *   with n_unitigs > 0; d_links NULL with n_links > 0.
+ * NOT built: L: fields in BCALM FASTA headers, km:f:, GFA 2, paths and walks, tip and bubble removal, compression. */
+typedef struct bl_unitig_link { uint32_t from, to; /* (unitig << 1) | orientation */ } bl_unitig_link;
+typedef struct bl_link_stats { uint64_t n_ends, n_links, n_self_reverse, n_dead_ends, n_branch_ends, reserved[3]; } bl_link_stats;
+enum { BL_LINKS_ONCE = 1u << 0 };
+int bl_unitig_links(bl_ctx* ctx, const bl_table* table, uint32_t k, const bl_unitig_node* d_nodes /* n_distinct */,
+                    const uint64_t* d_unitig_offsets /* n_unitigs + 1 */, uint64_t n_unitigs, uint32_t flags,
+                    uint64_t* d_link_offsets /* 2 n_unitigs + 1, nullable */, bl_unitig_link* d_links /* nullable: sizing */,
+                    uint64_t capacity, uint64_t* n_links, bl_link_stats* stats /* nullable */);
+enum { BL_GFA_NO_HEADER = 1u << 0 };
+typedef struct bl_gfa_rule {
+    uint32_t flags, k;        /* k: odd, 3 .. 63; the overlap of every L line is (k - 1)M */
+    char     name_prefix[16]; /* names: prefix + decimal(first_number + u), NUL-terminated */
+    uint64_t first_number;
+    uint64_t reserved;        /* 0 */
+} bl_gfa_rule;
+int bl_unitigs_format_gfa(bl_ctx* ctx, const bl_batch* unitigs, const uint64_t* d_unitig_offsets, uint64_t n_unitigs,
+                          const uint64_t* d_count_sums /* nullable */, const bl_unitig_link* d_links /* nullable iff n_links == 0 */,
+                          uint64_t n_links, const bl_gfa_rule* rule, uint8_t* d_out, uint64_t capacity, uint64_t* n_bytes);
+
 /* The chain's exit: reads and unitigs leave as FASTA / FASTQ text made on the device, names and qualities included.
  *
  * bl_text_index_build is bl_batch_from_text that keeps what that call drops.  It accepts and refuses exactly the same texts with the same
