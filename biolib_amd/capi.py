@@ -28,7 +28,7 @@ SYMBOLS = [
     "bl_table_build_u64", "bl_table_build_u128", "bl_table_destroy", "bl_table_info", "bl_table_arrays", "bl_table_lookup_u64", "bl_table_lookup_u128",
     "bl_table_histogram", "bl_scan_kmer_counts", "bl_scan_read_counts", "bl_table_combine", "bl_table_filter",
     "bl_select_read_counts", "bl_batch_select", "bl_read_spans", "bl_scan_read_edits", "bl_batch_apply_edits",
-    "bl_table_adjacency", "bl_table_unitigs", "bl_unitig_links", "bl_unitigs_format_gfa",
+    "bl_table_adjacency", "bl_table_unitigs", "bl_unitig_links", "bl_unitigs_format_gfa", "bl_unitigs_mark", "bl_table_remove_unitigs",
     "bl_text_index_build", "bl_text_index_info", "bl_text_index_offsets", "bl_text_index_destroy", "bl_reader_next_batch_device_indexed", "bl_batch_format",
     "bl_text_write",
 ]
@@ -134,6 +134,24 @@ class LinkStats(C.Structure):
 class GfaRule(C.Structure):
     """bl_gfa_rule (40 bytes)"""
     _fields_ = [("flags", C.c_uint32), ("k", C.c_uint32), ("name_prefix", C.c_char * 16), ("first_number", C.c_uint64), ("reserved", C.c_uint64)]
+
+
+CLEAN_TIPS, CLEAN_ISOLATED, CLEAN_BUBBLES = 1, 2, 4
+MARK_KEEP, MARK_TIP, MARK_ISOLATED, MARK_BUBBLE = 0, 1, 2, 3
+
+
+class CleanRule(C.Structure):
+    """bl_clean_rule (56 bytes)"""
+    _fields_ = [("flags", C.c_uint32), ("k", C.c_uint32)] + [(name, C.c_uint64) for name in ("max_tip_keys", "max_isolated_keys", "max_isolated_mean",
+                                                                                             "max_bubble_keys", "max_bubble_diff", "reserved")]
+
+
+class CleanStats(C.Structure):
+    """bl_clean_stats"""
+    _fields_ = [(name, C.c_uint64) for name in ("n_unitigs", "n_tips", "n_isolated", "n_bubbles", "n_keys_marked", "count_sum_marked")] + [("reserved", C.c_uint64 * 2)]
+
+    def as_dict(self):
+        return {name: int(getattr(self, name)) for name, _ in self._fields_ if name != "reserved"}
 
 
 TABLE_UNION, TABLE_INTERSECT, TABLE_SUBTRACT, TABLE_COUNT_SUBTRACT = 0, 1, 2, 3
@@ -296,6 +314,9 @@ def lib():
     if "BIOLIB_AMD_LIB" not in os.environ or hasattr(L, "bl_unitig_links"):
         L.bl_unitig_links.argtypes = [vp, vp, u32, vp, vp, u64, u32, vp, vp, u64, C.POINTER(u64), C.POINTER(LinkStats)]
         L.bl_unitigs_format_gfa.argtypes = [vp, vp, vp, u64, vp, vp, u64, C.POINTER(GfaRule), vp, u64, C.POINTER(u64)]
+    if "BIOLIB_AMD_LIB" not in os.environ or hasattr(L, "bl_unitigs_mark"):
+        L.bl_unitigs_mark.argtypes = [vp, vp, vp, u64, vp, vp, u64, C.POINTER(CleanRule), vp, C.POINTER(CleanStats)]
+        L.bl_table_remove_unitigs.argtypes = [vp, vp, vp, vp, u64, C.POINTER(vp), C.POINTER(u64)]
     if "BIOLIB_AMD_LIB" not in os.environ or hasattr(L, "bl_batch_format"):
         L.bl_text_index_build.argtypes = [vp, vp, u64, C.POINTER(vp), C.POINTER(vp), C.POINTER(u64), C.POINTER(u64)]
         L.bl_text_index_info.argtypes = [vp, C.POINTER(u64), C.POINTER(C.c_int), C.POINTER(vp), C.POINTER(u64), C.POINTER(vp)]

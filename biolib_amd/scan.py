@@ -829,7 +829,60 @@ class CountTable:
             ls = capi.LinkStats()
             n_links = self.unitig_links_raw(k, d_nodes, d_out, n_unitigs, capi.LINKS_ONCE if once else 0, link_offsets, d_links, bound, ls)
             u.link_offsets, u.links, u.link_stats = link_offsets, d_links[:n_links], ls.as_dict()
+            u._nodes, u._once = d_nodes[:n], bool(once)
         return u
+
+    # ---- cleaning the graph (bl_unitigs_mark, bl_table_remove_unitigs): the marked unitigs' keys leave, an ordinary table remains
+    def remove_unitigs_raw(self, nodes, marks, n_unitigs):
+        """bl_table_remove_unitigs: `nodes` are what unitigs_raw filled for this table, `marks` one byte per unitig.  Returns
+        (handle, n_removed).  Synchronous; the library checks every argument."""
+        h, nr = C.c_void_p(), C.c_uint64()
+        check(self._lib.bl_table_remove_unitigs(self.ctx._h, self._h, _ptr(nodes), _ptr(marks), int(n_unitigs), C.byref(h), C.byref(nr)))
+        return h, int(nr.value)
+
+    def remove_unitigs(self, unitigs, marks):
+        """This table without the keys of the unitigs whose mark is not 0: a new CountTable, the kept keys in order with their counts.
+        `unitigs` is what unitigs(k, nodes=True) or unitigs(k, links=True) returned for THIS table, `marks` a uint8 device tensor
+        [n_unitigs] (Unitigs.mark's, or any selection of your own).  ValueError where the nodes are not one per key of this table or
+        the marks not on its device: the kernels read one node per key and cannot tell."""
+        nodes = unitigs.nodes if unitigs.nodes is not None else unitigs._nodes
+        if nodes is None:
+            raise ValueError("remove_unitigs needs the nodes: unitigs(k, nodes=True) or unitigs(k, links=True)")
+        if int(nodes.shape[0]) != self.n_distinct:  # the library cannot know the length: the kernels read one node per key
+            raise ValueError("these unitigs are of another table: %d nodes for %d keys" % (int(nodes.shape[0]), self.n_distinct))
+        if marks.element_size() != 1 or marks.numel() != unitigs.n_unitigs or not marks.is_contiguous():
+            raise ValueError("marks is a contiguous one-byte tensor with one element per unitig")
+        if marks.device != nodes.device:
+            raise ValueError("marks is a device tensor on the table's device (%s), not on %s" % (nodes.device, marks.device))
+        self.ctx._inputs_ready()
+        return CountTable(self.ctx, self.remove_unitigs_raw(nodes if self.n_distinct else None, marks if self.n_distinct else None, unitigs.n_unitigs)[0])
+
+    def clean(self, k, tips=None, isolated=None, isolated_mean=2**32 - 1, bubbles=None, bubble_diff=0, max_rounds=8):
+        """The table of the cleaned graph: rounds of unitigs(k, batch=False, links=True) -> mark -> remove_unitigs until a round marks
+        nothing or max_rounds have run.  tips / isolated / bubbles are the greatest numbers of keys of a tip, an island and a bubble
+        branch that go (each 2 * k where not given, False switches the rule off; see Unitigs.mark).  Returns (table, history): a new
+        CountTable (this one stays) and the stats of every round, the last round that marked nothing included.  Then unitigs(k) of
+        the result gives the contigs."""
+        tips, isolated, bubbles = (2 * int(k) if x is None else None if x is False else x for x in (tips, isolated, bubbles))
+        table, history, done = self, [], False
+        try:
+            for _ in range(int(max_rounds)):
+                u = table.unitigs(k, batch=False, links=True)
+                marks, stats = u.mark(tips=tips, isolated=isolated, isolated_mean=isolated_mean, bubbles=bubbles, bubble_diff=bubble_diff)
+                history.append(stats)
+                if not (stats["n_tips"] or stats["n_isolated"] or stats["n_bubbles"]):
+                    break
+                cleaner = table.remove_unitigs(u, marks)
+                if table is not self:
+                    table.close()
+                table = cleaner
+            if table is self:  # nothing went: still a table of the caller's own to close
+                table = self.filter()
+            done = True
+            return table, history
+        finally:
+            if not done and table is not self:  # a round raised: the table of the rounds before it is nobody's
+                table.close()
 
 
 class Unitigs:
@@ -841,6 +894,37 @@ class Unitigs:
         self.n_unitigs, self.n_bases = n_unitigs, n_bases
         self.link_offsets = self.links = self.link_stats = None
         self.k, self._ctx, self._lib = None, None, None
+        self._nodes, self._once = None, False
+
+    def mark_raw(self, rule, marks, stats=None):
+        """bl_unitigs_mark: `rule` a capi.CleanRule, `marks` a one-byte device tensor of n_unitigs elements, `stats` (or None) a
+        capi.CleanStats.  Synchronous; the library checks every argument."""
+        n_links = int(self.links.shape[0]) if self.links is not None else 0
+        check(self._lib.bl_unitigs_mark(self._ctx._h, _ptr(self.offsets), _ptr(self.count_sums), int(self.n_unitigs), _ptr(self.link_offsets),
+                                        _ptr(self.links) if n_links else None, n_links, C.byref(rule), _ptr(marks), C.byref(stats) if stats is not None else None))
+
+    def mark(self, tips=None, isolated=None, isolated_mean=None, bubbles=None, bubble_diff=0):
+        """Which unitigs a cleaning round removes (bl_unitigs_mark; the header states the rules): (marks, stats).  marks: a uint8 device
+        tensor [n_unitigs], 0 keep, 1 tip (a dead-end spur of at most `tips` keys beside a real continuation or a better spur), 2
+        isolated (no link at either end, at most `isolated` keys, mean abundance at most `isolated_mean`), 3 bubble (at most `bubbles`
+        keys, between the same two anchors as a branch with a greater mean whose length differs by at most `bubble_diff`).  None
+        switches a rule off (isolated_mean None: no bound).  stats: n_unitigs, n_tips, n_isolated, n_bubbles, n_keys_marked,
+        count_sum_marked.  Needs unitigs(k, links=True) with once=False: the rules read every end's records."""
+        import torch
+
+        if self.links is None or self._once:
+            raise ValueError("mark needs unitigs(k, links=True, once=False): every end's records")
+        rule = capi.CleanRule()
+        rule.flags = (capi.CLEAN_TIPS if tips is not None else 0) | (capi.CLEAN_ISOLATED if isolated is not None else 0) | (capi.CLEAN_BUBBLES if bubbles is not None else 0)
+        rule.k = self.k
+        rule.max_tip_keys, rule.max_isolated_keys, rule.max_bubble_keys = int(tips or 0), int(isolated or 0), int(bubbles or 0)
+        rule.max_isolated_mean = 2**64 - 1 if isolated_mean is None else int(isolated_mean)
+        rule.max_bubble_diff = int(bubble_diff)
+        marks = torch.empty(max(self.n_unitigs, 1), dtype=torch.uint8, device=self._ctx.torch_device)
+        st = capi.CleanStats()
+        self._ctx._inputs_ready()
+        self.mark_raw(rule, marks, st)
+        return marks[:self.n_unitigs], st.as_dict()
 
     def write_fasta(self, path, line_width=0):
         """The unitigs as a FASTA file made on the device (Batch.write): names 0, 1, ... with " LN:i:<bases> KC:i:<count sum>" — BCALM's

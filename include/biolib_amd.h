@@ -755,7 +755,8 @@ int bl_table_unitigs(bl_ctx* ctx, const bl_table* table, uint32_t k, bl_batch** 
  *   BL_ERR_INVALID with a message, nothing launched: NULL ctx, unitigs or rule; a batch of another context; unknown flags; rule->k even
  *   or outside 3 .. 63; name_prefix without a NUL inside its 16 bytes; reserved != 0; d_out not 16-byte aligned; d_unitig_offsets NULL
  *   with n_unitigs > 0; d_links NULL with n_links > 0.
- * NOT built: L: fields in BCALM FASTA headers, km:f:, GFA 2, paths and walks, tip and bubble removal, compression. */
+ * NOT built: L: fields in BCALM FASTA headers, km:f:, GFA 2, paths and walks, compression.  (Tip, island and simple-bubble removal is
+ * bl_unitigs_mark / bl_table_remove_unitigs below; superbubbles are not built.) */
 typedef struct bl_unitig_link { uint32_t from, to; /* (unitig << 1) | orientation */ } bl_unitig_link;
 typedef struct bl_link_stats { uint64_t n_ends, n_links, n_self_reverse, n_dead_ends, n_branch_ends, reserved[3]; } bl_link_stats;
 enum { BL_LINKS_ONCE = 1u << 0 };
@@ -773,6 +774,57 @@ typedef struct bl_gfa_rule {
 int bl_unitigs_format_gfa(bl_ctx* ctx, const bl_batch* unitigs, const uint64_t* d_unitig_offsets, uint64_t n_unitigs,
                           const uint64_t* d_count_sums /* nullable */, const bl_unitig_link* d_links /* nullable iff n_links == 0 */,
                           uint64_t n_links, const bl_gfa_rule* rule, uint8_t* d_out, uint64_t capacity, uint64_t* n_bytes);
+
+/* Cleaning the compacted graph: short dead-end spurs (tips: what a sequencing error that survives bl_table_filter leaves), short isolated
+ * unitigs (islands) and the lesser branches of simple bubbles (a heterozygous SNP or a short indel) are marked from the link records
+ * alone, and their keys leave the table.  The result is an ordinary count table: bl_table_unitigs compacts it again, and a few rounds of
+ * unitigs -> links -> mark -> remove (CountTable.clean in Python) join what the spurs and bubbles had cut.
+ * NOTATION  L(u) = d_unitig_offsets[u + 1] - d_unitig_offsets[u] - (k - 1), the keys of unitig u; S(u) = d_count_sums[u].  Ends and records
+ *   are bl_unitig_links's WITHOUT BL_LINKS_ONCE: out(e) is the records of end e in array order, deg(e) their number.  The end by which a
+ *   record's `to` = x touches the junction is x ^ 1; x itself is its far end.
+ * KEEP ORDER  w precedes u iff (S(w) * L(u), L(w), -w) > (S(u) * L(w), L(u), -u) lexicographically: the greater mean abundance, compared
+ *   exactly by cross multiplication in 128-bit integers (never in floating point); then the longer one; then the smaller number.
+ * ISOLATED (mark 2)  deg(2u) = deg(2u + 1) = 0, L(u) <= max_isolated_keys and S(u) <= max_isolated_mean * L(u).
+ * TIP (mark 1)  exactly one end of u is dead (degree 0), e is the other one, and L(u) <= max_tip_keys: u is a tip candidate with live end
+ *   e.  It is marked iff there are a record e -> f and a record f ^ 1 -> x with w = x >> 1 != u such that w is not a tip candidate with
+ *   live end x ^ 1 (a real continuation leaves the junction), or w is one and precedes u.  So of several short spurs that share a junction
+ *   with nothing else, the first in the keep order stays.
+ * BUBBLE (mark 3)  deg(2u) = deg(2u + 1) = 1 with records 2u -> f0 and 2u + 1 -> f1, f0 >> 1 != u, f1 >> 1 != u and L(u) <= max_bubble_keys.
+ *   u is marked iff there is a record f1 ^ 1 -> x with w = x >> 1 != u such that deg(x) = deg(x ^ 1) = 1, out(x)[0] = f0 and
+ *   out(x ^ 1)[0] = f1 (w lies between the same anchors in the same orientations), L(w) <= max_bubble_keys,
+ *   |L(w) - L(u)| <= max_bubble_diff and w precedes u.  The first branch of a bubble in the keep order is never marked.
+ * Every decision is taken on the input graph at once; no mark depends on another mark, so a rerun is bit-identical, and what only appears
+ * after a removal (a tip on a bubble's branch) is left to the next round.  A rule whose flag is not set marks nothing.
+ *
+ * bl_unitigs_mark: d_unitig_offsets (n_unitigs + 1 words) and d_count_sums (n_unitigs) are bl_table_unitigs's, d_link_offsets
+ *   (2 * n_unitigs + 1) and d_links (n_links records) bl_unitig_links's; the table is no argument.  d_marks takes one byte per unitig
+ *   (BL_MARK_*), no byte behind them is written; stats (nullable, host): n_unitigs, the marked unitigs of each kind, n_keys_marked = the
+ *   sum of their L, count_sum_marked = the sum of their S (both mod 2^64).  The arrays are trusted for content, not for safety (select's
+ *   policy): L is taken mod 2^64 and only compared and multiplied, a link offset is clamped to n_links, only the first four records of an
+ *   end are read (deg is what the clamped offsets say), a `to` at or above 2 * n_unitigs is ignored, and nothing outside the stated sizes
+ *   is read or written.  Synchronous.  n_unitigs = 0 succeeds with zero stats.
+ *   BL_ERR_INVALID with a message, nothing launched: NULL ctx or rule; rule->k even or outside 3 .. 63; unknown flags; reserved != 0;
+ *   n_unitigs >= 2^31; d_unitig_offsets, d_count_sums, d_link_offsets or d_marks NULL with n_unitigs > 0; d_links NULL with n_links > 0.
+ * bl_table_remove_unitigs: *out is a NEW table (bl_table_destroy) of the same key width: key i of `table` is dropped iff
+ *   d_nodes[i].unitig < n_unitigs and d_marks[d_nodes[i].unitig] != 0 (d_nodes: bl_table_unitigs's, n_distinct records; a node at or above
+ *   n_unitigs keeps its key).  The kept keys stay in order with their counts; all keys dropped gives a valid empty table.  *n_removed
+ *   (nullable) = the input's n_distinct minus the output's.  No atomic decides a placement.  Synchronous.
+ *   BL_ERR_INVALID: NULL ctx, table or out; a table of another context; d_nodes or d_marks NULL on a table that is not empty.
+ * NOT built: complex bubbles (superbubbles), coverage-ratio rules such as relative-coverage tip clipping, read-threaded decisions, marking
+ * and removal fused into bl_table_unitigs. */
+enum { BL_CLEAN_TIPS = 1u << 0, BL_CLEAN_ISOLATED = 1u << 1, BL_CLEAN_BUBBLES = 1u << 2 };
+enum { BL_MARK_KEEP = 0, BL_MARK_TIP = 1, BL_MARK_ISOLATED = 2, BL_MARK_BUBBLE = 3 };
+typedef struct bl_clean_rule {
+    uint32_t flags, k; /* BL_CLEAN_*; k: odd, 3 .. 63, the k of the unitigs */
+    uint64_t max_tip_keys, max_isolated_keys, max_isolated_mean, max_bubble_keys, max_bubble_diff;
+    uint64_t reserved; /* 0 */
+} bl_clean_rule;
+typedef struct bl_clean_stats { uint64_t n_unitigs, n_tips, n_isolated, n_bubbles, n_keys_marked, count_sum_marked, reserved[2]; } bl_clean_stats;
+int bl_unitigs_mark(bl_ctx* ctx, const uint64_t* d_unitig_offsets /* n_unitigs + 1 */, const uint64_t* d_count_sums /* n_unitigs */,
+                    uint64_t n_unitigs, const uint64_t* d_link_offsets /* 2 n_unitigs + 1 */, const bl_unitig_link* d_links, uint64_t n_links,
+                    const bl_clean_rule* rule, uint8_t* d_marks /* n_unitigs */, bl_clean_stats* stats /* nullable */);
+int bl_table_remove_unitigs(bl_ctx* ctx, const bl_table* table, const bl_unitig_node* d_nodes /* n_distinct */, const uint8_t* d_marks,
+                            uint64_t n_unitigs, bl_table** out, uint64_t* n_removed /* nullable */);
 
 /* The chain's exit: reads and unitigs leave as FASTA / FASTQ text made on the device, names and qualities included.
  *
