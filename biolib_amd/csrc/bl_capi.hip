@@ -36,6 +36,8 @@ int bl_set_error(int code, const char* msg) { return fail(code, msg ? msg : "");
 struct bl_ctx;
 hipStream_t bl_ctx_stream(bl_ctx* ctx);
 int bl_ctx_device(bl_ctx* ctx);
+void* bl_ctx_pool_alloc(bl_ctx* ctx, size_t bytes);
+void bl_ctx_pool_free(bl_ctx* ctx, void* p);
 
 namespace {
 
@@ -107,6 +109,7 @@ struct bl_ctx {
     // optional per-launch timing of the main scan kernel alone (bl_ctx_kernel_timing)
     bool exact_windows = false;  // bl_ctx_set_exact_windows
     bool position_tiled = false; // bl_ctx_set_option("position_tiled"): never the read-tiled layout
+    bool packed_codes = true;    // bl_ctx_set_option("packed_codes"): 0 = new batches get no packed copy and scans ignore the one a batch has
     int jaccard128_path = 0;     // bl_ctx_set_option("jaccard128_path"): 0 = bl_jaccard_sorted_u128 chooses, 1 = merge kernel, 2 = search kernel
     bool count128_tables = true; // bl_ctx_set_option("count128_tables"): 0 = bl_count_super_kmers128 counts every bucket by sort + run-length
     int table_prefix_bits = -1;  // bl_ctx_set_option("table_prefix_bits"): -1 = bl_table_build_* chooses the width of the prefix index, 0 .. 24 forces it
@@ -135,6 +138,11 @@ struct bl_batch {
     uint8_t* bases = nullptr;
     bool owns_bases = false;
     uint32_t* start_bits = nullptr;  // nullptr: single sequence, or fixed-length reads whose vector has not been needed yet
+    // the packed copy (ScanParams::codes_packed, chunk_bad) of a batch that owns its bases: one allocation, made when the batch is; nullptr:
+    // a borrowed buffer, which its owner may rewrite, or a batch made under bl_ctx_set_option("packed_codes", 0)
+    uint32_t* packed = nullptr;     // the allocation: code words, then bad bits, each with its guard chunks (bl_scan_core.hpp: packed_total)
+    uint32_t* codes = nullptr;      // chunk 0 in it
+    uint32_t* chunk_bad = nullptr;  // the word of chunks 0 .. 31
     uint64_t n_bases = 0;
     uint64_t n_seqs = 0;
     uint64_t read_len = 0;           // != 0: every sequence has this length (the last one may be shorter)
@@ -329,6 +337,23 @@ int make_start_bits(bl_ctx* c, bl_batch* b, const uint64_t* offsets, uint64_t n_
         b->n_seqs = (b->n_bases + read_len - 1) / read_len;
         BL_HIP(hipStreamSynchronize(c->stream));  // the batch may be scanned from either lane
     }
+    return BL_OK;
+}
+
+// The packed copy of a batch that owns its bases (they are written and zero padded on `s`, or complete): 0.26 bytes per base, once per batch
+// instead of an encode per scan.  The caller synchronises `s` before it hands the batch out, so that either lane may scan it.
+// From the context's pool, like the bases of an upload: the few hundred equal spans of a file recycle a few buffers; a copy above 1 GiB (a
+// batch above 4 Gbp: 13 GB for the bench's 50 Gbp) is a plain hipMalloc here and a hipFree when the batch goes, as its bases are.
+int make_packed_codes(bl_ctx* c, bl_batch* b, hipStream_t s)
+{
+    if (!c->packed_codes) return BL_OK;
+    const uint64_t total = (uint64_t)bl::packed_total((int64_t)b->n_bases);  // chunks with the guards on either side: code words, then bad bits
+    b->packed = static_cast<uint32_t*>(bl_ctx_pool_alloc(c, (total + total / 32) * sizeof(uint32_t)));
+    if (!b->packed) return fail(BL_ERR_OOM, "device allocation of the batch's packed codes failed (bl_ctx_set_option(\"packed_codes\", 0) does without)");
+    b->codes = b->packed + bl::PACK_LEAD;
+    b->chunk_bad = b->packed + total + bl::PACK_LEAD / 32;
+    hipError_t e = bl::launch_pack_codes(b->bases, b->n_bases, b->packed, b->packed + total, s);
+    if (e != hipSuccess) return fail(BL_ERR_HIP, std::string("pack_codes: ") + hipGetErrorString(e));
     return BL_OK;
 }
 
@@ -606,6 +631,10 @@ int bl_ctx_set_option(bl_ctx* c, const char* name, int64_t value)
         c->position_tiled = value != 0;
         return BL_OK;
     }
+    if (n == "packed_codes" && (value == 0 || value == 1)) {
+        c->packed_codes = value != 0;
+        return BL_OK;
+    }
     if (n == "count128_tables" && (value == 0 || value == 1)) {
         c->count128_tables = value != 0;
         return BL_OK;
@@ -727,6 +756,8 @@ static int upload_batch(bl_ctx* c, const char* bases, uint64_t n_bases, const ui
     hipError_t e = hipMemsetAsync(b->bases + (n_bases & ~15ull), 0, 64 + (n_bases & 15ull), c->stream);
     if (e == hipSuccess && n_bases) e = hipMemcpyAsync(b->bases, bases, n_bases, hipMemcpyHostToDevice, c->stream);
     if (e != hipSuccess) { bl_batch_destroy(b); return fail(BL_ERR_HIP, std::string("upload: ") + hipGetErrorString(e)); }
+    rc = make_packed_codes(c, b, c->stream);
+    if (rc != BL_OK) { bl_batch_destroy(b); return rc; }
     uint64_t fixed = 0;  // offsets that describe equal-length reads (the usual short-read batch) need no start-bit vector
     if (read_len) {
         if (read_len < n_bases) {
@@ -811,6 +842,8 @@ int bl_batch_synth(bl_ctx* c, uint64_t seed, uint64_t n_bases, uint64_t read_len
     e = hipMemsetAsync(b->bases + (n_bases & ~15ull), 0, 64 + (n_bases & 15ull), c->stream);
     if (e == hipSuccess) e = bl::launch_synth(b->bases, 0, n_bases, seed, c->stream);
     if (e != hipSuccess) { bl_batch_destroy(b); return fail(BL_ERR_HIP, std::string("synth: ") + hipGetErrorString(e)); }
+    rc = make_packed_codes(c, b, c->stream);
+    if (rc != BL_OK) { bl_batch_destroy(b); return rc; }
     if (read_len > 0 && read_len < n_bases) {
         b->read_len = read_len;
         b->n_seqs = (n_bases + read_len - 1) / read_len;
@@ -836,13 +869,16 @@ int bl_batch_adopt_device(bl_ctx* c, void* d_bases, uint64_t n_bases, uint64_t* 
     b->bases = static_cast<uint8_t*>(d_bases);
     b->owns_bases = true;
     b->n_seqs = n_seqs;
+    hipStream_t s = bl_ctx_stream(c);
+    rc = make_packed_codes(c, b, s);
+    if (rc != BL_OK) { bl_ctx_pool_free(c, d_offsets); bl_batch_destroy(b); return rc; }
     if (fixed_len && n_seqs > 1 && fixed_len < n_bases) {
         b->read_len = fixed_len;
         bl_ctx_pool_free(c, d_offsets);
+        if (b->codes && hipStreamSynchronize(s) != hipSuccess) { bl_batch_destroy(b); return fail(BL_ERR_HIP, "adopt: pack_codes failed"); }
         *out = b;
         return BL_OK;
     }
-    hipStream_t s = bl_ctx_stream(c);
     const uint64_t n_words = (n_bases + 31) / 32 + 4;
     b->start_bits = static_cast<uint32_t*>(bl_ctx_pool_alloc(c, n_words * sizeof(uint32_t)));
     hipError_t e = b->start_bits ? hipSuccess : hipErrorOutOfMemory;
@@ -868,6 +904,10 @@ int bl_batch_adopt_like(bl_ctx* c, const bl_batch* like, void* d_bases, uint32_t
     b->n_seqs = like->n_seqs;
     b->read_len = like->read_len;
     b->origin = like->origin;
+    hipStream_t s = bl_ctx_stream(c);
+    rc = make_packed_codes(c, b, s);
+    if (rc == BL_OK && b->codes && hipStreamSynchronize(s) != hipSuccess) rc = fail(BL_ERR_HIP, "adopt: pack_codes failed");
+    if (rc != BL_OK) { bl_batch_destroy(b); return rc; }
     *out = b;
     return BL_OK;
 }
@@ -888,6 +928,7 @@ int bl_batch_destroy(bl_batch* b)
     }
     if (b->owns_bases && b->bases) bl_ctx_pool_free(b->ctx, b->bases);
     if (b->start_bits) bl_ctx_pool_free(b->ctx, b->start_bits);
+    if (b->packed) bl_ctx_pool_free(b->ctx, b->packed);
     delete b;
     return BL_OK;
 }
@@ -1203,6 +1244,10 @@ static int scan_windows(int mode, bl_ctx* c, const bl_batch* b, uint64_t first, 
         if (rc != BL_OK) return rc;
     }
     p.start_bits = b->start_bits;
+    if (c->packed_codes && b->codes && bl::packed_covers(p) && (p.frl || bl::packed_scan_shape(mode, (int)w))) {  // pass 1 stages from the batch's packed copy and hands no codes to pass 2
+        p.codes_packed = b->codes;
+        p.chunk_bad = b->chunk_bad;
+    }
     p.unit = (int32_t)unit;
     p.w = (int32_t)w;
     p.seed = (uint32_t)seed;
@@ -1218,7 +1263,8 @@ static int scan_windows(int mode, bl_ctx* c, const bl_batch* b, uint64_t first, 
     const size_t n_lists = mode == bl::MODE_SUPERKMER ? 3 : 1;
     const size_t slot_entries = nt * (size_t)p.stride;
     const size_t list_bytes = n_lists * slot_entries * sizeof(uint16_t);  // multiple of 32 bytes (stride % 16 == 0)
-    rc = grow(c, reinterpret_cast<void**>(&c->cur->slot_buf), &c->cur->slot_buf_bytes, list_bytes + nt * (size_t)p.slot_chunks * sizeof(uint32_t));
+    const size_t code_bytes = p.codes_packed ? 0 : nt * (size_t)p.slot_chunks * sizeof(uint32_t);  // slots_c: only without a packed copy
+    rc = grow(c, reinterpret_cast<void**>(&c->cur->slot_buf), &c->cur->slot_buf_bytes, list_bytes + code_bytes);
     if (rc != BL_OK) return rc;
     unsigned long long* tb = reinterpret_cast<unsigned long long*>(c->cur->tile_buf);
     p.tile_counts = tb;
@@ -1230,7 +1276,7 @@ static int scan_windows(int mode, bl_ctx* c, const bl_batch* b, uint64_t first, 
     p.slots_a = c->cur->slot_buf;
     p.slots_j = mode == bl::MODE_SUPERKMER ? c->cur->slot_buf + slot_entries : nullptr;
     p.slots_e = mode == bl::MODE_SUPERKMER ? c->cur->slot_buf + 2 * slot_entries : nullptr;
-    p.slots_c = reinterpret_cast<uint32_t*>(reinterpret_cast<unsigned char*>(c->cur->slot_buf) + list_bytes);
+    p.slots_c = p.codes_packed ? nullptr : reinterpret_cast<uint32_t*>(reinterpret_cast<unsigned char*>(c->cur->slot_buf) + list_bytes);
     p.shards = c->shards();
     // count -> tile prefix scan -> emit, all tiles in one group (the prefix scan supports several
     // groups with a running carry; one group is what is used)

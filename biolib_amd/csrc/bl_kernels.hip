@@ -152,15 +152,17 @@ __device__ __forceinline__ void fill_list(uint16_t* dst, const uint16_t* src, ui
 // SY (syncmer scans): 0 = tagged argmins with the exact form inline (also what scan_redo_kernel runs), 1 = closed syncmers
 // (sliding minima), 2 = tagged argmins WITHOUT the exact form: a tile that met a prefix tie is listed for scan_redo_kernel;
 // W = -8 / -16 with SY = 1: closed syncmers for a window count given at run time (phase_sync_closed_rt), two size groups
-template <int MODE, int W, int SY = 0, int U = 0>
+template <int MODE, int W, int SY = 0, int U = 0, bool PACKED = false>
 __device__ __forceinline__ void count_tile(const ScanParams& p, TileShared<MODE, W>& sh, uint32_t tile, int tid)
 {
     const int64_t q0 = p.origin + (int64_t)tile * p.stride;
-    phase_load<MODE, W>(p, sh, tid, q0);
+    static_assert(!PACKED || SY != 0 || U != 0 || packed_scan_shape(MODE, W), "scan_windows hands no packed copy to this shape: its twin is never launched");
+    phase_load<MODE, W, PACKED>(p, sh, tid, q0);
     constexpr bool CS = SY == 1;
     if (SY != 0 && tid == 0) sh.redo = 0;
-    if (MODE != MODE_SYNCMER) {  // hand the packed codes to pass 2 (0.26 B/base instead of re-reading and re-encoding 1 B/base there);
-                                 // a syncmer record is a position: its pass 2 rebuilds nothing and reads no codes
+    if (MODE != MODE_SYNCMER && !PACKED) {  // hand the packed codes to pass 2 (0.26 B/base instead of re-reading and re-encoding 1 B/base
+                                                    // there; a batch with a packed copy: pass 2 reads that); a syncmer record is a position:
+                                                    // its pass 2 rebuilds nothing and reads no codes
         const int needed = staged_chunks(p);
         uint32_t* sc = p.slots_c + (size_t)tile * p.slot_chunks;
         if (tid < needed) sc[tid] = sh.codes[tid];  // own LDS entries: no barrier needed
@@ -227,13 +229,13 @@ __device__ __forceinline__ void count_tile(const ScanParams& p, TileShared<MODE,
 // Pass 1 of one tile in the read-tiled layout (fixed-length short reads, bl_scan_frl.hpp): same outputs as count_tile.
 // APPROX: the windows are decided on murmur64_top (bl_scan_core.hpp), 7 instructions per hash cheaper than the hash; a tile in which
 // some lane could not tell two keys apart is listed for scan_redo_frl_kernel, which runs this function without the flag.
-template <int MODE, int W, int NS, int LIM_LAST, bool GENERIC, bool APPROX = false, int U = 0>
+template <int MODE, int W, int NS, int LIM_LAST, bool GENERIC, bool APPROX = false, int U = 0, bool PACKED = false>
 __device__ __forceinline__ void count_tile_frl(const ScanParams& p, TileShared<MODE, W>& sh, uint32_t tile, int tid)
 {
     const int64_t q0 = tile_q0(p, tile);
-    phase_load_frl<MODE, W>(p, sh, tid, q0);
+    phase_load_frl<MODE, W, PACKED>(p, sh, tid, q0);
     if (APPROX && tid == 0) sh.redo = 0;
-    {   // hand the packed codes to pass 2
+    if (!PACKED) {  // hand the packed codes to pass 2 (a batch with a packed copy: pass 2 reads that)
         uint32_t* sc = p.slots_c + (size_t)tile * p.slot_chunks;
         for (int c = tid; c < p.slot_chunks; c += TPB) sc[c] = sh.codes[c];  // own LDS entries: no barrier needed
     }
@@ -271,7 +273,8 @@ __device__ __forceinline__ void count_tile_frl(const ScanParams& p, TileShared<M
 // codes[C3_RC + 1] on (unit31_canonical), each behind one dword it may read and mask away.
 constexpr int C3_RC = NCHUNK + 4;
 // WIDE: out_records takes the 32-byte record (emit_record128) instead of the 16-byte one.
-template <int MODE, bool LOOPED = false, bool C3 = false, bool WIDE = false>
+// PACKED: the tile's codes come from the batch's packed copy (ScanParams::codes_packed), not from a slot pass 1 filled.
+template <int MODE, bool LOOPED = false, bool C3 = false, bool WIDE = false, bool PACKED = false>
 __device__ __forceinline__ void emit_tile(const ScanParams& p, uint32_t* codes, uint32_t tile, int tid, Digest& dg)
 {
     // one memory round trip for the common case: every load of the tile — counts, offsets, codes, the first 2 * TPB list entries
@@ -283,7 +286,9 @@ __device__ __forceinline__ void emit_tile(const ScanParams& p, uint32_t* codes, 
     const unsigned long long cnt = uniform64(p.tile_counts[tile]);
     const unsigned long long base = uniform64(p.tile_base[tile] + p.block_base[tile / SCAN_BLK]);
     const int needed = staged_chunks(p);
-    const uint32_t* sc = p.slots_c + (size_t)tile * p.slot_chunks;
+    // the tile's codes: pass 1's copy in the tile's slot or, where the batch has a packed copy, its chunks from q0 on (q0 is a multiple of
+    // 16 in both layouts; outside the batch the copy holds guard chunks, zeros as pass 1 stages them: no test of the index)
+    const uint32_t* sc = PACKED ? p.codes_packed + (q0 >> 4) : p.slots_c + (size_t)tile * p.slot_chunks;
     const uint32_t c0 = (MODE != MODE_SYNCMER && tid < needed) ? sc[tid] : 0;
     const uint32_t c1 = (MODE != MODE_SYNCMER && TPB + tid < needed) ? sc[TPB + tid] : 0;
     const uint16_t* la = p.slots_a + slot;
@@ -352,7 +357,9 @@ __device__ __forceinline__ void emit_tile(const ScanParams& p, uint32_t* codes, 
 // parameter block is copied and the fields overwritten with constants, which the inlined phases fold
 // (constant shifts and masks in the roller, no strand selects).  U = 0 / C = -1: taken from the arguments.
 // SY: the syncmer form (count_tile): 1 = closed syncmers (offsets {0, W - 1}; phase_sync_closed), 2 = argmins with the exact form deferred
-template <int MODE, int W, int U, int C, int SY = 0>
+// PACKED (all four pass-1 kernels): the twin that stages from the batch's packed copy and hands no codes to pass 2; launched under the
+// name of the instantiation without it (BL_PK), which is the code of before the copy existed.
+template <bool PACKED, int MODE, int W, int U, int C, int SY = 0>
 __global__ __launch_bounds__(TPB, (MODE == MODE_MINIMIZER && SY == 2 ? BL_POSAX_WAVES : MODE == MODE_SUPERKMER && SY == 2 ? BL_SKAX_WAVES : SY == 1 && W < 0 ? BL_CSRT_WAVES : SY == 1 ? BL_CS_WAVES : SY == 2 ? BL_SY2_WAVES : (MODE == MODE_SYNCMER && W > 0 ? BL_SY0_WAVES : MODE == MODE_SYNCMER || (MODE == MODE_SUPERKMER && W == -32) ? 2 : (W == -32 || (W < 0 && MODE == MODE_SUPERKMER) ? 3 : (W == -16 ? 5 : (W < 0 ? 4 : (W <= 11 ? 5 : (MODE == MODE_SUPERKMER && W == 17 && U == 15 ? BL_C4_WAVES : 4)))))))) void scan_count_kernel(const ScanParams pin, GroupRange g)
 {
     __shared__ TileShared<MODE, W> sh;
@@ -363,12 +370,12 @@ __global__ __launch_bounds__(TPB, (MODE == MODE_MINIMIZER && SY == 2 ? BL_POSAX_
         p.stride = NWAVE * (64 * S - 16 * ((W + 15) / 16));  // plan_scan's value, as a constant
     }
     if (C >= 0) p.canonical = C;
-    if (blockIdx.x < g.count) count_tile<MODE, W, SY, U>(p, sh, g.first + blockIdx.x, threadIdx.x);
+    if (blockIdx.x < g.count) count_tile<MODE, W, SY, U, PACKED>(p, sh, g.first + blockIdx.x, threadIdx.x);
 }
 
 // The tiles a closed-syncmer pass 1 could not decide (p.redo_list), counted again in the exact argmin form: same outputs, written
 // over what pass 1 left for them.  Runs between pass 1 and the prefix scan; clean data lists nothing and every workgroup leaves at once.
-template <int MODE, int W, int U, int C>
+template <bool PACKED, int MODE, int W, int U, int C>
 __global__ __launch_bounds__(TPB, 2) void scan_redo_kernel(const ScanParams pin)
 {
     __shared__ TileShared<MODE, W> sh;
@@ -381,7 +388,7 @@ __global__ __launch_bounds__(TPB, 2) void scan_redo_kernel(const ScanParams pin)
     if (C >= 0) p.canonical = C;
     const unsigned long long n = *p.redo_count;
     for (unsigned long long i = blockIdx.x; i < n; i += gridDim.x) {
-        count_tile<MODE, W>(p, sh, p.redo_list[i], threadIdx.x);
+        count_tile<MODE, W, 0, 0, PACKED>(p, sh, p.redo_list[i], threadIdx.x);
         __syncthreads();  // the lists in LDS have been spilled before the next tile overwrites them
     }
 }
@@ -416,26 +423,26 @@ constexpr int frl_lim_last() { return L != 0 ? (L - U + 1 - W + 1) - ((L - U + 1
 #ifndef BL_FRL_WAVES
 #define BL_FRL_WAVES 5  // waves per SIMD the read-tiled pass 1 with a window of at most 11 is compiled for (6: 80 registers, 60 bytes of scratch, 427 against 486 Gbp/s; 4: the same code as 5)
 #endif
-template <int MODE, int W, int NS, int U, int L, int C, bool APPROX = false>
+template <bool PACKED, int MODE, int W, int NS, int U, int L, int C, bool APPROX = false>
 __global__ __launch_bounds__(TPB, (W <= 11 ? BL_FRL_WAVES : 4)) void scan_count_frl_kernel(const ScanParams pin, GroupRange g)
 {
     __shared__ TileShared<MODE, W> sh;
     const ScanParams p = frl_params<MODE, W, NS, U, L, C>(pin);
     constexpr int LIM_LAST = frl_lim_last<W, NS, U, L>();
     static_assert(L == 0 || (LIM_LAST >= 1 && LIM_LAST <= NS), "read-tiled geometry: the last lane of a read must own 1..NS windows");
-    if (blockIdx.x < g.count) count_tile_frl<MODE, W, NS, LIM_LAST, U == 0, APPROX, U>(p, sh, g.first + blockIdx.x, threadIdx.x);
+    if (blockIdx.x < g.count) count_tile_frl<MODE, W, NS, LIM_LAST, U == 0, APPROX, U, PACKED>(p, sh, g.first + blockIdx.x, threadIdx.x);
 }
 
 // The tiles an APPROX pass 1 listed, counted again on the hashes themselves (same outputs, written over what pass 1 left for them);
 // between pass 1 and the prefix scan, like scan_redo_kernel.  Random reads list a tile in a few hundred.
-template <int MODE, int W, int NS, int U, int L, int C>
+template <bool PACKED, int MODE, int W, int NS, int U, int L, int C>
 __global__ __launch_bounds__(TPB, (W <= 11 ? 5 : 4)) void scan_redo_frl_kernel(const ScanParams pin)
 {
     __shared__ TileShared<MODE, W> sh;
     const ScanParams p = frl_params<MODE, W, NS, U, L, C>(pin);
     const unsigned long long n = *p.redo_count;
     for (unsigned long long i = blockIdx.x; i < n; i += gridDim.x) {
-        count_tile_frl<MODE, W, NS, frl_lim_last<W, NS, U, L>(), U == 0, false, U>(p, sh, p.redo_list[i], threadIdx.x);
+        count_tile_frl<MODE, W, NS, frl_lim_last<W, NS, U, L>(), U == 0, false, U, PACKED>(p, sh, p.redo_list[i], threadIdx.x);
         __syncthreads();  // the lists in LDS have been spilled before the next tile overwrites them
     }
 }
@@ -460,7 +467,8 @@ template <int MODE, int U, int C, int FRL>
 constexpr bool emit_c3() { return MODE == MODE_MINIMIZER && U == 31 && C == 1 && FRL == 1; }
 // WIDE: super-k-mer scans that hand out 32-byte records (p.records128): the one instantiation that packs them (emit_tile) — the
 // others carry no branch for it.
-template <int MODE, int U = 0, int C = -1, int FRL = -1, bool WIDE = false>
+// PACKED: see emit_tile; launched under the name of the instantiation without it.
+template <int MODE, int U = 0, int C = -1, int FRL = -1, bool WIDE = false, bool PACKED = false>
 __global__ __launch_bounds__(TPB) void scan_emit_kernel(const ScanParams pin, GroupRange g)
 {
     static_assert(!WIDE || (MODE == MODE_SUPERKMER && U == 0), "32-byte records are super-k-mer groups; the unit length comes from the arguments");
@@ -481,7 +489,7 @@ __global__ __launch_bounds__(TPB) void scan_emit_kernel(const ScanParams pin, Gr
 #pragma unroll 1
         for (uint32_t k = 0; k < (uint32_t)K && t0 + k < g.count; ++k) {
             Digest d1{0, 0, 0};
-            emit_tile<MODE, true, C3>(p, codes[k & 1], g.first + t0 + k, tid, d1);
+            emit_tile<MODE, true, C3, false, PACKED>(p, codes[k & 1], g.first + t0 + k, tid, d1);
             acc[0][tid] ^= (uint32_t)d1.xv; acc[1][tid] ^= (uint32_t)(d1.xv >> 32);
             acc[2][tid] ^= (uint32_t)d1.xh; acc[3][tid] ^= (uint32_t)(d1.xh >> 32);
             acc[4][tid] ^= (uint32_t)d1.xp; acc[5][tid] ^= (uint32_t)(d1.xp >> 32);
@@ -491,7 +499,7 @@ __global__ __launch_bounds__(TPB) void scan_emit_kernel(const ScanParams pin, Gr
         dg.xp = ((unsigned long long)acc[5][tid] << 32) | acc[4][tid];
     } else {
         if (blockIdx.x >= g.count) return;
-        emit_tile<MODE, false, C3, WIDE>(p, codes[0], g.first + blockIdx.x, tid, dg);
+        emit_tile<MODE, false, C3, WIDE, PACKED>(p, codes[0], g.first + blockIdx.x, tid, dg);
     }
 
     // digest: wave reduce (DPP xor-scan), then one set of atomics per WAVE into a shard line.  Measured alternatives: an LDS stage
@@ -696,6 +704,20 @@ __global__ void start_bits_offsets_kernel(uint32_t* bits, const uint64_t* offset
     if (p < n_bases && offsets[q + 1] > p) atomicOr(&bits[p >> 5], 1u << (p & 31));
 }
 
+// The packed copy of a batch (ScanParams::codes_packed, chunk_bad), guard chunks included: one thread per 16-base chunk, thread t of the
+// launch chunk t - PACK_LEAD, half a wave per word of bad bits.  codes / chunk_bad: packed_total(n_bases) words / bits, from the first
+// guard chunk on.  Not a scan kernel: it runs once, when a batch that owns its bases is created.
+__global__ __launch_bounds__(256) void pack_codes_kernel(const uint8_t* bases, int64_t n_bases, uint32_t* codes, uint32_t* chunk_bad)
+{
+    const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (t >= packed_total(n_bases)) return;  // a multiple of 64: whole waves leave
+    uint32_t code;
+    const bool bad = pack_chunk(bases, n_bases, t - PACK_LEAD, code);  // outside the batch: zeros, bad
+    codes[t] = code;
+    const unsigned long long m = __builtin_amdgcn_ballot_w64(bad);
+    if ((threadIdx.x & 31) == 0) chunk_bad[t >> 5] = (uint32_t)(m >> (threadIdx.x & 32));
+}
+
 // ------------------------------------------------------------------------------------------------
 // launchers
 
@@ -709,6 +731,10 @@ __global__ void start_bits_offsets_kernel(uint32_t* bits, const uint64_t* offset
         if (log) log->add(NAME);                                               \
         hipLaunchKernelGGL(KERNEL, GRID, BLOCK, LDS, stream, __VA_ARGS__);     \
     } while (0)
+// a pass-1 kernel or its PACKED twin (same function type), by whether the scan has the batch's packed copy
+#define BL_PK(KERNEL, ...) (p.codes_packed ? KERNEL<true, __VA_ARGS__> : KERNEL<false, __VA_ARGS__>)
+// ... of the kernels that take the width from the arguments: a shape scan_windows keeps off the packed copy (packed_scan_shape) has no twin
+#define BL_PK_W(KERNEL, MODEV, WV, ...) (p.codes_packed ? KERNEL<packed_scan_shape(MODEV, WV), MODEV, WV, __VA_ARGS__> : KERNEL<false, MODEV, WV, __VA_ARGS__>)
 // the name of a kernel all three modes instantiate
 #define BL_MODE_NAME(HEAD, TAIL) (MODE == MODE_MINIMIZER ? HEAD "MM" TAIL : MODE == MODE_SUPERKMER ? HEAD "SK" TAIL : HEAD "SY" TAIL)
 
@@ -761,10 +787,10 @@ static hipError_t launch_count_frl(int mode, const ScanParams& p, GroupRange g, 
     const dim3 grid(g.count), block(TPB);
     if (mode == MODE_MINIMIZER && p.w == 11 && p.unit == 31 && p.canonical && p.read_len == 150 && p.ns == 15 && p.rpw == 8) {
         if (p.redo_list && g.first == 0 && !p.exact_windows) {  // BASELINE C3 (exact_windows, bl_ctx_set_exact_windows: windows decided on the hashes themselves)
-            BL_LAUNCH("frl<MM,W=11,NS=15,U=31,L=150,approx>", (scan_count_frl_kernel<MODE_MINIMIZER, 11, 15, 31, 150, 1, true>), grid, block, 0, p, g);
-            BL_LAUNCH("frl_redo<MM,W=11,NS=15,U=31,L=150>", (scan_redo_frl_kernel<MODE_MINIMIZER, 11, 15, 31, 150, 1>), dim3(g.count < 512u ? g.count : 512u), block, 0, p);
+            BL_LAUNCH("frl<MM,W=11,NS=15,U=31,L=150,approx>", BL_PK(scan_count_frl_kernel, MODE_MINIMIZER, 11, 15, 31, 150, 1, true), grid, block, 0, p, g);
+            BL_LAUNCH("frl_redo<MM,W=11,NS=15,U=31,L=150>", BL_PK(scan_redo_frl_kernel, MODE_MINIMIZER, 11, 15, 31, 150, 1), dim3(g.count < 512u ? g.count : 512u), block, 0, p);
         } else {
-            BL_LAUNCH("frl<MM,W=11,NS=15,U=31,L=150>", (scan_count_frl_kernel<MODE_MINIMIZER, 11, 15, 31, 150, 1>), grid, block, 0, p, g);
+            BL_LAUNCH("frl<MM,W=11,NS=15,U=31,L=150>", BL_PK(scan_count_frl_kernel, MODE_MINIMIZER, 11, 15, 31, 150, 1), grid, block, 0, p, g);
         }
         return hipGetLastError();
     }
@@ -775,10 +801,10 @@ static hipError_t launch_count_frl(int mode, const ScanParams& p, GroupRange g, 
         const dim3 redo_grid(g.count < 512u ? g.count : 512u);
 #define BL_FRL_SHAPE(NSV)                                                                                                                                    \
     if (approx) {                                                                                                                                            \
-        BL_LAUNCH("frl<MM,W=11,NS=" #NSV ",U=31,approx>", (scan_count_frl_kernel<MODE_MINIMIZER, 11, NSV, 31, 0, 1, true>), grid, block, 0, p, g);            \
-        BL_LAUNCH("frl_redo<MM,W=11,NS=" #NSV ",U=31>", (scan_redo_frl_kernel<MODE_MINIMIZER, 11, NSV, 31, 0, 1>), redo_grid, block, 0, p);                   \
+        BL_LAUNCH("frl<MM,W=11,NS=" #NSV ",U=31,approx>", BL_PK(scan_count_frl_kernel, MODE_MINIMIZER, 11, NSV, 31, 0, 1, true), grid, block, 0, p, g);            \
+        BL_LAUNCH("frl_redo<MM,W=11,NS=" #NSV ",U=31>", BL_PK(scan_redo_frl_kernel, MODE_MINIMIZER, 11, NSV, 31, 0, 1), redo_grid, block, 0, p);                   \
     } else {                                                                                                                                                 \
-        BL_LAUNCH("frl<MM,W=11,NS=" #NSV ",U=31>", (scan_count_frl_kernel<MODE_MINIMIZER, 11, NSV, 31, 0, 1>), grid, block, 0, p, g);                         \
+        BL_LAUNCH("frl<MM,W=11,NS=" #NSV ",U=31>", BL_PK(scan_count_frl_kernel, MODE_MINIMIZER, 11, NSV, 31, 0, 1), grid, block, 0, p, g);                         \
     }
         if (p.ns == 14) { BL_FRL_SHAPE(14) } else if (p.ns == 15) { BL_FRL_SHAPE(15) } else { BL_FRL_SHAPE(16) }
 #undef BL_FRL_SHAPE
@@ -787,14 +813,14 @@ static hipError_t launch_count_frl(int mode, const ScanParams& p, GroupRange g, 
     if (p.ns != S) return hipErrorInvalidValue;  // the general kernels give every lane S unit starts
     if (mode == MODE_MINIMIZER) {
         switch (p.w) {
-            case 5: BL_LAUNCH("frl<MM,W=5>", (scan_count_frl_kernel<MODE_MINIMIZER, 5, S, 0, 0, -1>), grid, block, 0, p, g); break;
-            case 10: BL_LAUNCH("frl<MM,W=10>", (scan_count_frl_kernel<MODE_MINIMIZER, 10, S, 0, 0, -1>), grid, block, 0, p, g); break;
-            case 11: BL_LAUNCH("frl<MM,W=11>", (scan_count_frl_kernel<MODE_MINIMIZER, 11, S, 0, 0, -1>), grid, block, 0, p, g); break;
-            case 19: BL_LAUNCH("frl<MM,W=19>", (scan_count_frl_kernel<MODE_MINIMIZER, 19, S, 0, 0, -1>), grid, block, 0, p, g); break;
+            case 5: BL_LAUNCH("frl<MM,W=5>", BL_PK(scan_count_frl_kernel, MODE_MINIMIZER, 5, S, 0, 0, -1), grid, block, 0, p, g); break;
+            case 10: BL_LAUNCH("frl<MM,W=10>", BL_PK(scan_count_frl_kernel, MODE_MINIMIZER, 10, S, 0, 0, -1), grid, block, 0, p, g); break;
+            case 11: BL_LAUNCH("frl<MM,W=11>", BL_PK(scan_count_frl_kernel, MODE_MINIMIZER, 11, S, 0, 0, -1), grid, block, 0, p, g); break;
+            case 19: BL_LAUNCH("frl<MM,W=19>", BL_PK(scan_count_frl_kernel, MODE_MINIMIZER, 19, S, 0, 0, -1), grid, block, 0, p, g); break;
             default: return hipErrorInvalidValue;
         }
     } else if (mode == MODE_SUPERKMER && p.w == 17) {
-        BL_LAUNCH("frl<SK,W=17>", (scan_count_frl_kernel<MODE_SUPERKMER, 17, S, 0, 0, -1>), grid, block, 0, p, g);
+        BL_LAUNCH("frl<SK,W=17>", BL_PK(scan_count_frl_kernel, MODE_SUPERKMER, 17, S, 0, 0, -1), grid, block, 0, p, g);
     } else {
         return hipErrorInvalidValue;
     }
@@ -809,47 +835,47 @@ static hipError_t launch_count_mode(const ScanParams& p, GroupRange g, hipStream
     if (MODE == MODE_MINIMIZER && p.w == 11 && p.unit == 31 && p.canonical) {
 #ifndef BL_NO_POSAX
         if (p.redo_list && g.first == 0 && !p.exact_windows) {  // long reads, contigs, reads of mixed lengths: windows decided on murmur64_top here too
-            BL_LAUNCH("count<MM,W=11,U=31,C=1,approx>", (scan_count_kernel<MODE_MINIMIZER, 11, 31, 1, 2>), grid, block, 0, p, g);
-            BL_LAUNCH("redo<MM,W=11,U=31,C=1>", (scan_redo_kernel<MODE_MINIMIZER, 11, 31, 1>), dim3(g.count < 512u ? g.count : 512u), block, 0, p);
+            BL_LAUNCH("count<MM,W=11,U=31,C=1,approx>", BL_PK(scan_count_kernel, MODE_MINIMIZER, 11, 31, 1, 2), grid, block, 0, p, g);
+            BL_LAUNCH("redo<MM,W=11,U=31,C=1>", BL_PK(scan_redo_kernel, MODE_MINIMIZER, 11, 31, 1), dim3(g.count < 512u ? g.count : 512u), block, 0, p);
             return hipGetLastError();
         }
 #endif
-        BL_LAUNCH("count<MM,W=11,U=31,C=1>", (scan_count_kernel<MODE, 11, 31, 1>), grid, block, 0, p, g);
+        BL_LAUNCH("count<MM,W=11,U=31,C=1>", BL_PK(scan_count_kernel, MODE, 11, 31, 1), grid, block, 0, p, g);
         return hipGetLastError();
     }
     if (MODE == MODE_SUPERKMER && p.w == 17 && p.unit == 15 && p.canonical) {
 #ifdef BL_SKAX  // measured twice (rounds 3 and 4; this form: 112 registers, no spills, 17 % fewer static instructions): 398.5 / 399.9 against 399.0 / 401.6
                // Gbp/s for the exact kernel, A/B on one box — the super-k-mer scan is not limited by the hash's four instructions.  Not built by default.
         if (p.redo_list && g.first == 0 && !p.exact_windows) {  // BASELINE C4: windows decided on murmur64_top, the listed tiles again on the hashes
-            BL_LAUNCH("count<SK,W=17,U=15,C=1,approx>", (scan_count_kernel<MODE_SUPERKMER, 17, 15, 1, 2>), grid, block, 0, p, g);
-            BL_LAUNCH("redo<SK,W=17,U=15,C=1>", (scan_redo_kernel<MODE_SUPERKMER, 17, 15, 1>), dim3(g.count < 512u ? g.count : 512u), block, 0, p);
+            BL_LAUNCH("count<SK,W=17,U=15,C=1,approx>", BL_PK(scan_count_kernel, MODE_SUPERKMER, 17, 15, 1, 2), grid, block, 0, p, g);
+            BL_LAUNCH("redo<SK,W=17,U=15,C=1>", BL_PK(scan_redo_kernel, MODE_SUPERKMER, 17, 15, 1), dim3(g.count < 512u ? g.count : 512u), block, 0, p);
             return hipGetLastError();
         }
 #endif
-        BL_LAUNCH("count<SK,W=17,U=15,C=1>", (scan_count_kernel<MODE, 17, 15, 1>), grid, block, 0, p, g);
+        BL_LAUNCH("count<SK,W=17,U=15,C=1>", BL_PK(scan_count_kernel, MODE, 17, 15, 1), grid, block, 0, p, g);
         return hipGetLastError();
     }
     if (MODE == MODE_SYNCMER && p.w == 21 && p.unit == 11 && p.canonical) {
         const bool closed = (p.soff == 0 && p.eoff == 20) || (p.soff == 20 && p.eoff == 0);
         const unsigned redo_grid = g.count < 512u ? g.count : 512u;
         if (closed && !p.exact_windows && p.redo_list && g.first == 0) {  // BASELINE C5 (exact_windows: the argmin form)
-            BL_LAUNCH("count<SY,W=21,U=11,C=1,closed>", (scan_count_kernel<MODE_SYNCMER, 21, 11, 1, 1>), grid, block, 0, p, g);
-            BL_LAUNCH("redo<SY,W=21,U=11,C=1>", (scan_redo_kernel<MODE_SYNCMER, 21, 11, 1>), dim3(redo_grid), block, 0, p);
+            BL_LAUNCH("count<SY,W=21,U=11,C=1,closed>", BL_PK(scan_count_kernel, MODE_SYNCMER, 21, 11, 1, 1), grid, block, 0, p, g);
+            BL_LAUNCH("redo<SY,W=21,U=11,C=1>", BL_PK(scan_redo_kernel, MODE_SYNCMER, 21, 11, 1), dim3(redo_grid), block, 0, p);
 #ifndef BL_NO_SY2
         } else if (p.redo_list && g.first == 0) {  // any other pair of offsets: argmins, the exact form in the redo kernel
-            BL_LAUNCH("count<SY,W=21,U=11,C=1,deferred>", (scan_count_kernel<MODE_SYNCMER, 21, 11, 1, 2>), grid, block, 0, p, g);
-            BL_LAUNCH("redo<SY,W=21,U=11,C=1>", (scan_redo_kernel<MODE_SYNCMER, 21, 11, 1>), dim3(redo_grid), block, 0, p);
+            BL_LAUNCH("count<SY,W=21,U=11,C=1,deferred>", BL_PK(scan_count_kernel, MODE_SYNCMER, 21, 11, 1, 2), grid, block, 0, p, g);
+            BL_LAUNCH("redo<SY,W=21,U=11,C=1>", BL_PK(scan_redo_kernel, MODE_SYNCMER, 21, 11, 1), dim3(redo_grid), block, 0, p);
 #endif
         } else {
-            BL_LAUNCH("count<SY,W=21,U=11,C=1>", (scan_count_kernel<MODE, 21, 11, 1>), grid, block, 0, p, g);
+            BL_LAUNCH("count<SY,W=21,U=11,C=1>", BL_PK(scan_count_kernel, MODE, 21, 11, 1), grid, block, 0, p, g);
         }
         return hipGetLastError();
     }
     if (MODE == MODE_SYNCMER && p.w <= 32 && !p.exact_windows && ((p.soff == 0 && p.eoff == p.w - 1) || (p.soff == p.w - 1 && p.eoff == 0))) {
         // closed syncmers of any (k, s): sliding minima over the hashes' high dwords, w by run time; a k-mer whose comparison meets equal
         // dwords is decided on the 64-bit hashes inside the kernel (short s-mers repeat within a window: no second kernel, no listed tiles)
-        if (p.w <= 17) BL_LAUNCH("count<SY,closed,W<=17>", (scan_count_kernel<MODE_SYNCMER, -8, 0, -1, 1>), grid, block, 0, p, g);
-        else BL_LAUNCH("count<SY,closed,W<=32>", (scan_count_kernel<MODE_SYNCMER, -16, 0, -1, 1>), grid, block, 0, p, g);
+        if (p.w <= 17) BL_LAUNCH("count<SY,closed,W<=17>", BL_PK(scan_count_kernel, MODE_SYNCMER, -8, 0, -1, 1), grid, block, 0, p, g);
+        else BL_LAUNCH("count<SY,closed,W<=32>", BL_PK(scan_count_kernel, MODE_SYNCMER, -16, 0, -1, 1), grid, block, 0, p, g);
         return hipGetLastError();
     }
     if (MODE != MODE_SYNCMER && p.w >= 2 && p.w <= 32) {
@@ -858,24 +884,24 @@ static hipError_t launch_count_mode(const ScanParams& p, GroupRange g, hipStream
         // time, ran these widths at 220-340 Gbp/s where a width of its own gives 340-420; 2 x 27 more kernels cost the build half a minute.)
         constexpr int MM = MODE == MODE_SYNCMER ? MODE_MINIMIZER : MODE;  // never instantiated for syncmers
         switch (p.w) {
-#define BL_W(WV) case WV: BL_LAUNCH(BL_MODE_NAME("count<", ",W=" #WV ">"), (scan_count_kernel<MM, WV, 0, -1>), grid, block, 0, p, g); return hipGetLastError();
+#define BL_W(WV) case WV: BL_LAUNCH(BL_MODE_NAME("count<", ",W=" #WV ">"), BL_PK_W(scan_count_kernel, MM, WV, 0, -1), grid, block, 0, p, g); return hipGetLastError();
             BL_W_ALL(BL_W)
 #undef BL_W
         }
     }
     switch (p.w) {
-        case 1: BL_LAUNCH(BL_MODE_NAME("count<", ",W=1>"), (scan_count_kernel<MODE, 1, 0, -1>), grid, block, 0, p, g); break;
-        case 11: BL_LAUNCH(BL_MODE_NAME("count<", ",W=11>"), (scan_count_kernel<MODE, 11, 0, -1>), grid, block, 0, p, g); break;
-        case 17: BL_LAUNCH(BL_MODE_NAME("count<", ",W=17>"), (scan_count_kernel<MODE, 17, 0, -1>), grid, block, 0, p, g); break;
-        case 21: BL_LAUNCH(BL_MODE_NAME("count<", ",W=21>"), (scan_count_kernel<MODE, 21, 0, -1>), grid, block, 0, p, g); break;
+        case 1: BL_LAUNCH(BL_MODE_NAME("count<", ",W=1>"), BL_PK(scan_count_kernel, MODE, 1, 0, -1), grid, block, 0, p, g); break;
+        case 11: BL_LAUNCH(BL_MODE_NAME("count<", ",W=11>"), BL_PK(scan_count_kernel, MODE, 11, 0, -1), grid, block, 0, p, g); break;
+        case 17: BL_LAUNCH(BL_MODE_NAME("count<", ",W=17>"), BL_PK(scan_count_kernel, MODE, 17, 0, -1), grid, block, 0, p, g); break;
+        case 21: BL_LAUNCH(BL_MODE_NAME("count<", ",W=21>"), BL_PK(scan_count_kernel, MODE, 21, 0, -1), grid, block, 0, p, g); break;
         default:
             // runtime window size: sparse-table argmin in registers, one kernel per size group (minimizer and super-k-mer scans come
             // here with widths beyond 32 only)
             if constexpr (MODE == MODE_SYNCMER) {
-                if (p.w <= 16) { BL_LAUNCH("count<SY,W<=16>", (scan_count_kernel<MODE, -8, 0, -1>), grid, block, 0, p, g); break; }
-                if (p.w <= 32) { BL_LAUNCH("count<SY,W<=32>", (scan_count_kernel<MODE, -16, 0, -1>), grid, block, 0, p, g); break; }
+                if (p.w <= 16) { BL_LAUNCH("count<SY,W<=16>", BL_PK(scan_count_kernel, MODE, -8, 0, -1), grid, block, 0, p, g); break; }
+                if (p.w <= 32) { BL_LAUNCH("count<SY,W<=32>", BL_PK(scan_count_kernel, MODE, -16, 0, -1), grid, block, 0, p, g); break; }
             }
-            BL_LAUNCH(BL_MODE_NAME("count<", ",W>32>"), (scan_count_kernel<MODE, -32, 0, -1>), grid, block, 0, p, g);
+            BL_LAUNCH(BL_MODE_NAME("count<", ",W>32>"), BL_PK(scan_count_kernel, MODE, -32, 0, -1), grid, block, 0, p, g);
             break;
     }
     return hipGetLastError();
@@ -907,14 +933,18 @@ static void launch_emit_mode(const ScanParams& p, GroupRange g, hipStream_t stre
     const dim3 grid((g.count + K - 1) / K), block(TPB);
     if (MODE == MODE_MINIMIZER && p.frl && p.unit == 31 && p.canonical) {  // BASELINE C3: code buffers of two strands (emit_c3)
         const uint32_t have_c3 = (uint32_t)(((K > 1 ? 2 : 1) * 2 * C3_RC + (K > 1 ? 6 * TPB : 0)) * sizeof(uint32_t));
-        BL_LAUNCH("emit<MM,C3>", (scan_emit_kernel<MODE_MINIMIZER, 31, 1, 1>), grid, block, lds_per_wg > have_c3 ? lds_per_wg - have_c3 : 0, p, g);
+        if (p.codes_packed) BL_LAUNCH("emit<MM,C3>", (scan_emit_kernel<MODE_MINIMIZER, 31, 1, 1, false, true>), grid, block, lds_per_wg > have_c3 ? lds_per_wg - have_c3 : 0, p, g);
+        else BL_LAUNCH("emit<MM,C3>", (scan_emit_kernel<MODE_MINIMIZER, 31, 1, 1>), grid, block, lds_per_wg > have_c3 ? lds_per_wg - have_c3 : 0, p, g);
         return;
     }
     if (MODE == MODE_SUPERKMER && p.records128) {  // 32-byte records: the instantiation that packs them (same LDS footprint)
-        BL_LAUNCH("emit<SK,wide>", (scan_emit_kernel<MODE_SUPERKMER, 0, -1, -1, true>), grid, block, pad, p, g);
+        if (p.codes_packed) BL_LAUNCH("emit<SK,wide>", (scan_emit_kernel<MODE_SUPERKMER, 0, -1, -1, true, true>), grid, block, pad, p, g);
+        else BL_LAUNCH("emit<SK,wide>", (scan_emit_kernel<MODE_SUPERKMER, 0, -1, -1, true>), grid, block, pad, p, g);
         return;
     }
-    BL_LAUNCH(BL_MODE_NAME("emit<", ">"), (scan_emit_kernel<MODE>), grid, block, pad, p, g);
+    // (a syncmer record is a position: its pass 2 reads no codes)
+    if (MODE != MODE_SYNCMER && p.codes_packed) BL_LAUNCH(BL_MODE_NAME("emit<", ">"), (scan_emit_kernel<MODE, 0, -1, -1, false, MODE != MODE_SYNCMER>), grid, block, pad, p, g);
+    else BL_LAUNCH(BL_MODE_NAME("emit<", ">"), (scan_emit_kernel<MODE>), grid, block, pad, p, g);
 }
 
 hipError_t launch_scan_emit(int mode, const ScanParams& p, GroupRange g, hipStream_t stream, uint32_t lds_per_wg, LaunchLog* log)
@@ -929,6 +959,8 @@ hipError_t launch_scan_emit(int mode, const ScanParams& p, GroupRange g, hipStre
     return hipGetLastError();
 }
 #undef BL_LAUNCH
+#undef BL_PK
+#undef BL_PK_W
 #undef BL_MODE_NAME
 #undef BL_W_ALL
 
@@ -975,6 +1007,14 @@ hipError_t launch_start_bits_offsets(uint32_t* bits, const uint64_t* offsets, ui
 {
     if (n_seqs == 0) return hipSuccess;
     hipLaunchKernelGGL(start_bits_offsets_kernel, dim3((unsigned)((n_seqs + 255) / 256)), dim3(256), 0, stream, bits, offsets, n_seqs, n_bases);
+    return hipGetLastError();
+}
+
+// codes: packed_total(n_bases) words, chunk_bad: as many bits; both from the first guard chunk on
+hipError_t launch_pack_codes(const uint8_t* bases, uint64_t n_bases, uint32_t* codes, uint32_t* chunk_bad, hipStream_t stream)
+{
+    const uint64_t total = (uint64_t)packed_total((int64_t)n_bases);  // a multiple of 64
+    hipLaunchKernelGGL(pack_codes_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, stream, bases, (int64_t)n_bases, codes, chunk_bad);
     return hipGetLastError();
 }
 

@@ -23,4 +23,5 @@ hipError_t launch_reduce_shards(const unsigned long long* shards, unsigned long 
 hipError_t launch_synth(uint8_t* bases, uint64_t first, uint64_t n, uint64_t seed, hipStream_t stream);
 hipError_t launch_start_bits_fixed(uint32_t* bits, uint64_t n_words, uint64_t n_bases, uint64_t read_len, hipStream_t stream);
 hipError_t launch_start_bits_offsets(uint32_t* bits, const uint64_t* offsets, uint64_t n_seqs, uint64_t n_bases, hipStream_t stream);
+hipError_t launch_pack_codes(const uint8_t* bases, uint64_t n_bases, uint32_t* codes, uint32_t* chunk_bad, hipStream_t stream);
 }  // namespace bl

@@ -91,7 +91,7 @@ struct ScanParams {
     uint16_t* slots_a;                // [n_tiles][stride] list_a of every tile (first `starts` entries valid)
     uint16_t* slots_j;                // super-k-mer: list_j
     uint16_t* slots_e;                // super-k-mer: list_e (first `ends` entries valid)
-    uint32_t* slots_c;                // [n_tiles][slot_chunks] the tile's 2-bit codes (pass 2 rebuilds unit values from them)
+    uint32_t* slots_c;                // [n_tiles][slot_chunks] the tile's 2-bit codes (pass 2 rebuilds unit values from them); nullptr with codes_packed
     int32_t slot_chunks;              // chunks a tile stages and hands to pass 2 (<= NCHUNK)
     unsigned long long* shards;       // [NSHARD][8] digest accumulators
     // closed-syncmer scans: tiles in which a comparison met equal high dwords are listed here by pass 1 and counted again, in the
@@ -112,7 +112,31 @@ struct ScanParams {
     // super-k-mer scans that hand out 32-BYTE records (bl_scan_super_kmer_records128: k up to 64, groups of up to 122 bases): out_records
     // takes four words per group (pack_group128) and position-tiled tiles stage WCHUNK chunks per wave (staged_chunks has the bound)
     int32_t records128;
+    // The batch's packed copy (bl_capi.hip: built once when a batch that owns its bases is created; nullptr: the batch has none, or
+    // bl_ctx_set_option("packed_codes", 0)): codes_packed[i] is the word encode16 makes of bases [16 i, 16 i + 16) (bases from n_bases on
+    // read as zeros), bit i of chunk_bad says that one of those sixteen is not ACGTUacgtu or lies at or beyond n_bases.  Both arrays
+    // go on on either side of the batch, PACK_LEAD chunks before chunk 0 and at least PACK_TAIL behind the last (zero codes, bad bits
+    // set), so that every chunk a tile of a scan stages is there to read without a test of its index (packed_covers).  Pass 1 stages
+    // its tiles from them where no lane of the wave meets a bad chunk (stage_chunk, stage_chunk_frl) and hands no codes to pass 2, which
+    // reads them here.
+    const uint32_t* codes_packed;
+    const uint32_t* chunk_bad;
 };
+
+// The packed copy's guard chunks: a position-tiled scan starts up to 16 bases before the batch (plan_scan), and a tile that starts inside
+// the batch stages at most NCHUNK chunks.  PACK_LEAD is one whole word of bad bits.
+constexpr int PACK_LEAD = 32, PACK_TAIL = NCHUNK;
+// chunks of the packed copy, guards included: whole waves of pack_codes_kernel, whole words of bad bits
+BL_DEV int64_t packed_total(int64_t n_bases) { return (PACK_LEAD + ((n_bases + 15) >> 4) + PACK_TAIL + 63) & ~63LL; }
+// Window scans that stay off the packed copy (ASCII staging, codes handed to pass 2 through the tile's slot, as for a batch without one):
+// position-tiled minimizers of width 25.  Without the hand-over's stores that one kernel compiles to 128 registers and 20 bytes of scratch
+// for 95 and none, packed staging or not, and the widths beside it do not; a spill in a hashing kernel costs more than the encode saves.
+constexpr bool packed_scan_shape(int mode, int w) { return !(mode == MODE_MINIMIZER && w == 25); }
+// every tile of the plan in p finds its staged chunks inside the packed copy
+BL_DEV bool packed_covers(const ScanParams& p)
+{
+    return p.n_tiles > 0 && p.origin >= -16 * (int64_t)PACK_LEAD && p.origin + (int64_t)(p.n_tiles - 1) * p.stride < p.n_bases + 16;
+}
 
 // widths the read-tiled kernels are built for (bl_kernels.hip: launch_count_frl; the emulation harness instantiates the same set)
 BL_DEV bool frl_width_built(int mode, int w)

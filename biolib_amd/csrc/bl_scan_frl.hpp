@@ -26,31 +26,39 @@ BL_DEV int64_t tile_q0(const ScanParams& p, uint32_t tile)
 
 // ------------------------------------------------------------------------------------------------
 // Phase 1: coalesced 16-byte loads -> 2-bit codes + good-base bits; true if the chunk holds a break
+template <bool PACKED = false>  // as stage_chunk
 BL_DEV bool stage_chunk_frl(const ScanParams& p, uint32_t* codes, uint32_t* flags, int c, int64_t q0)
 {
-    const int64_t g = q0 + 16 * (int64_t)c;  // >= 0
-    uint32_t d[4] = {0, 0, 0, 0};
-    if (g + 16 <= p.n_bases) {
-        const Vec16 v = *reinterpret_cast<const Vec16*>(p.bases + g);
-        d[0] = v.x; d[1] = v.y; d[2] = v.z; d[3] = v.w;
-    } else if (BL_COLD(g < p.n_bases)) {  // ragged end of the batch: byte-wise, zeros (= breaks) outside
-        for (int b = 0; b < 16; ++b) {
-            const int64_t q = g + b;
-            if (q < p.n_bases) d[b >> 2] |= (uint32_t)p.bases[q] << (8 * (b & 3));
-        }
+    const int64_t g = q0 + 16 * (int64_t)c;  // >= 0, a multiple of 16 (tile_q0)
+    uint32_t code = 0, bad = 0;
+    bool ascii = true;
+    if (PACKED) {
+        const bool pbad = packed_chunk(p, g, code);
+        ascii = BL_COLD(wave_any(pbad));
     }
-    uint32_t code, bad;
-    encode16(d, code, bad);
+    if (ascii) {  // no packed copy, or a lane of the wave meets a break or the end of the batch
+        uint32_t d[4] = {0, 0, 0, 0};
+        if (g + 16 <= p.n_bases) {
+            const Vec16 v = *reinterpret_cast<const Vec16*>(p.bases + g);
+            d[0] = v.x; d[1] = v.y; d[2] = v.z; d[3] = v.w;
+        } else if (BL_COLD(g < p.n_bases)) {  // ragged end of the batch: byte-wise, zeros (= breaks) outside
+            for (int b = 0; b < 16; ++b) {
+                const int64_t q = g + b;
+                if (q < p.n_bases) d[b >> 2] |= (uint32_t)p.bases[q] << (8 * (b & 3));
+            }
+        }
+        encode16(d, code, bad);
+    }
     codes[c] = code;
     flags[c] = ~bad & 0xffffu;
     return bad != 0;
 }
 
-template <int MODE, int W>
+template <int MODE, int W, bool PACKED = false>
 BL_DEV void phase_load_frl(const ScanParams& p, TileShared<MODE, W>& sh, int tid, int64_t q0)
 {
     bool bad = false;
-    for (int c = tid; c < p.slot_chunks; c += TPB) bad |= stage_chunk_frl(p, sh.codes, sh.flags, c, q0);  // 2 rounds at most; the 2nd is a few lanes of wave 0
+    for (int c = tid; c < p.slot_chunks; c += TPB) bad |= stage_chunk_frl<PACKED>(p, sh.codes, sh.flags, c, q0);  // 2 rounds at most; the 2nd is a few lanes of wave 0
     const int wv = wave_index(tid);
 #if defined(__HIP_DEVICE_COMPILE__) && !defined(BL_CPU_EMU)
     const bool any = wave_any(bad);

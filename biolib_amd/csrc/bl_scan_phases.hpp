@@ -70,21 +70,39 @@ struct alignas(16) Vec16 {
     uint32_t x, y, z, w;
 };
 
+// The packed copy's word for chunk ci (g = 16 * ci is the chunk's first base) and its bad bit.  Chunks outside the batch are guard chunks,
+// bad ones (ScanParams; the host hands the copy over only where packed_covers holds): ci = -1 is bit 31 of word -1.
+BL_DEV bool packed_chunk(const ScanParams& p, int64_t g, uint32_t& code)
+{
+    const int64_t ci = g >> 4;
+    code = p.codes_packed[ci];
+    return ((p.chunk_bad[ci >> 5] >> (ci & 31)) & 1u) != 0;
+}
+
+// PACKED: stage from the batch's packed copy (p.codes_packed, p.chunk_bad set; the PACKED twins of the pass-1 kernels, bl_kernels.hip)
+template <bool PACKED = false>
 BL_DEV void stage_chunk(const ScanParams& p, uint32_t* codes, uint32_t* flags, int c, int64_t q0)
 {
     const int64_t g = q0 + 16 * (int64_t)c;
-    uint32_t d[4] = {0, 0, 0, 0};
-    if (g >= 0 && g + 16 <= p.n_bases) {
-        const Vec16 v = *reinterpret_cast<const Vec16*>(p.bases + g);  // one global_load_dwordx4 (a non-temporal load measured no faster)
-        d[0] = v.x; d[1] = v.y; d[2] = v.z; d[3] = v.w;
-    } else if (BL_COLD(g + 16 > 0 && g < p.n_bases)) {  // ragged edge: byte-wise, zeros (= breaks) outside
-        for (int b = 0; b < 16; ++b) {
-            const int64_t q = g + b;
-            if (q >= 0 && q < p.n_bases) d[b >> 2] |= (uint32_t)p.bases[q] << (8 * (b & 3));
-        }
+    uint32_t code = 0, bad = 0;
+    bool ascii = true;
+    if (PACKED) {
+        const bool pbad = packed_chunk(p, g, code);
+        ascii = BL_COLD(wave_any(pbad));
     }
-    uint32_t code, bad;
-    encode16(d, code, bad);
+    if (ascii) {  // no packed copy, or a lane of the wave meets a break or an edge of the batch
+        uint32_t d[4] = {0, 0, 0, 0};
+        if (g >= 0 && g + 16 <= p.n_bases) {
+            const Vec16 v = *reinterpret_cast<const Vec16*>(p.bases + g);  // one global_load_dwordx4 (a non-temporal load measured no faster)
+            d[0] = v.x; d[1] = v.y; d[2] = v.z; d[3] = v.w;
+        } else if (BL_COLD(g + 16 > 0 && g < p.n_bases)) {  // ragged edge: byte-wise, zeros (= breaks) outside
+            for (int b = 0; b < 16; ++b) {
+                const int64_t q = g + b;
+                if (q >= 0 && q < p.n_bases) d[b >> 2] |= (uint32_t)p.bases[q] << (8 * (b & 3));
+            }
+        }
+        encode16(d, code, bad);
+    }
     uint32_t start = 0;
     if (p.start_bits) {
         if (g >= 0 && g < p.n_bases) start = (p.start_bits[g >> 5] >> (g & 31)) & 0xffffu;
@@ -124,6 +142,20 @@ BL_DEV uint32_t codes_of(const Vec16& v)
         code = (code << 8) | ((x * 0x40100401u) >> 24);
     }
     return code;
+}
+
+// One chunk of a batch's packed copy: the word pass 1 stages for bases [16 ci, 16 ci + 16) — encode16 of them, bases from n_bases on
+// read as zeros — and whether the chunk is bad (a base that is not ACGTUacgtu, or one at or beyond n_bases).
+BL_DEV bool pack_chunk(const uint8_t* bases, int64_t n_bases, int64_t ci, uint32_t& code)
+{
+    ScanParams lp{};
+    lp.bases = bases;
+    lp.n_bases = n_bases;
+    const Vec16 v = load_chunk(lp, 0, 16 * ci);
+    const uint32_t d[4] = {v.x, v.y, v.z, v.w};
+    uint32_t bad;
+    encode16(d, code, bad);
+    return bad != 0 || 16 * ci + 16 > n_bases;
 }
 
 // index of the thread's wave inside the workgroup, as a value the compiler knows to be wave-uniform (scalar registers
@@ -166,12 +198,12 @@ BL_DEV int staged_chunks(const ScanParams& p)
 }
 static_assert(3 * 63 + WCHUNK <= NCHUNK_POS && NCHUNK_POS <= 2 * TPB && NCHUNK_POS <= NCHUNK, "a tile's staged chunks fit its slot, two staging rounds and the LDS array");
 
-template <int MODE, int W>
+template <int MODE, int W, bool PACKED = false>
 BL_DEV void phase_load(const ScanParams& p, TileShared<MODE, W>& sh, int tid, int64_t q0)
 {
     const int needed = staged_chunks(p);
-    if (tid < needed) stage_chunk(p, sh.codes, sh.flags, tid, q0);
-    if (TPB + tid < needed) stage_chunk(p, sh.codes, sh.flags, TPB + tid, q0);  // a few lanes of wave 0 only
+    if (tid < needed) stage_chunk<PACKED>(p, sh.codes, sh.flags, tid, q0);
+    if (TPB + tid < needed) stage_chunk<PACKED>(p, sh.codes, sh.flags, TPB + tid, q0);  // a few lanes of wave 0 only
 }
 
 // good / start bit-vectors for the lane's positions i0 .. i0+127 (bit i = wave position 16*lane + i)

@@ -275,6 +275,11 @@ int bl_ctx_set_exact_windows(bl_ctx* ctx, int on);
  *   "lanes"           1 / 2       = bl_ctx_set_lanes
  *   "position_tiled"  0 / 1       1: batches of fixed-length reads are scanned by the position-tiled kernels too (default 0: read-tiled
  *                                 where that layout applies)
+ *   "packed_codes"    0 / 1       1 (default): a batch that owns its bases (upload, synth, the parser, select, apply_edits) keeps a packed
+ *                                 copy of them, 2 bits per base and a bit per 16 bases (+0.26 bytes per base), made once when the batch is,
+ *                                 and the window scans stage their tiles from it.  0: batches made LATER get none, and scans ignore the copy
+ *                                 of a batch that has one.  bl_batch_from_device batches, whose memory is the caller's,
+ *                                 never get one
  *   "emit_lds_bytes"  0 or bytes  two-lane contexts: LDS footprint the record pass's workgroups are padded to, which caps how many of
  *                                 them a CU holds beside the next scan's hashing pass (0: the built-in default per scan kind)
  *   "count128_tables" 0 / 1       0: bl_count_super_kmers128 counts every bucket by expand + sort + run-length instead of the LDS tables

@@ -64,12 +64,13 @@ if os.path.exists(os.path.join(src, "shape_sweep.json")):
     json.dump(sw, open(os.path.join(dst, f"{RND}_shape_sweep.json"), "w"), indent=1)
 
 # kernel key -> substring of the kernel name rocprofv3 reports
+# (bench.py's batches own their bases: pass 1 and the record kernels that read codes run as their PACKED twins)
 kernels = {
-    "c3_count": "scan_count_frl_kernel<0, 11, 15, 31, 150, 1, true>", "c3_emit": "scan_emit_kernel<0, 31, 1, 1>",
+    "c3_count": "scan_count_frl_kernel<true, 0, 11, 15, 31, 150, 1, true>", "c3_emit": "scan_emit_kernel<0, 31, 1, 1, false, true>",
     "c2_kmer": "kmer_kernel",
-    "c4_count": "scan_count_kernel<1, 17, 15, 1, 0>", "c4_emit": "scan_emit_kernel<1, 0, -1, -1>",
-    "c5_count": "scan_count_kernel<2, 21, 11, 1, 1>", "c5_emit": "scan_emit_kernel<2, 0, -1, -1>",
-    "c3_redo": "scan_redo_frl_kernel<0, 11, 15, 31, 150, 1>", "c5_redo": "scan_redo_kernel<2, 21, 11, 1>",  # the tiles pass 1 could not decide, again
+    "c4_count": "scan_count_kernel<true, 1, 17, 15, 1, 0>", "c4_emit": "scan_emit_kernel<1, 0, -1, -1, false, true>",
+    "c5_count": "scan_count_kernel<true, 2, 21, 11, 1, 1>", "c5_emit": "scan_emit_kernel<2, 0, -1, -1, false, false>",
+    "c3_redo": "scan_redo_frl_kernel<true, 0, 11, 15, 31, 150, 1>", "c5_redo": "scan_redo_kernel<true, 2, 21, 11, 1>",  # the tiles pass 1 could not decide, again
 }
 means = {k: {} for k in kernels}
 for d in ("pmc_fetch", "pmc_write", "pmc_sq1", "pmc_sq2", "pmc_sq3"):

@@ -47,11 +47,13 @@ with tempfile.TemporaryDirectory() as tmp:
     asm = os.path.join(tmp, "k.s")
     subprocess.check_call(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-DBL_CENSUS_HOT", "-S", "--cuda-device-only",
                            os.path.join(ROOT, "biolib_amd", "csrc", "bl_kernels.hip"), "-o", asm], stderr=subprocess.DEVNULL)
-    mangled = {"c3_count": r"scan_count_frl_kernelILi0ELi11ELi15ELi31ELi150ELi1ELb1E", "c3_emit": r"scan_emit_kernelILi0ELi31ELi1ELi1E", "c2_kmer": r"kmer_kernel",
-               "c4_count": r"scan_count_kernelILi1ELi17ELi15ELi1ELi0E", "c4_emit": r"scan_emit_kernelILi1ELi0ELin1ELin1E", "c5_count": r"scan_count_kernelILi2ELi21ELi11ELi1ELi1E",
-               "c5_emit": r"scan_emit_kernelILi2ELi0ELin1ELin1E",
+    # the instantiations bench.py's batches run: they own their bases, so pass 1 and the record kernels that read codes are the PACKED twins
+    # (first template argument of the pass-1 kernels, last of scan_emit_kernel)
+    mangled = {"c3_count": r"scan_count_frl_kernelILb1ELi0ELi11ELi15ELi31ELi150ELi1ELb1E", "c3_emit": r"scan_emit_kernelILi0ELi31ELi1ELi1ELb0ELb1E", "c2_kmer": r"kmer_kernel",
+               "c4_count": r"scan_count_kernelILb1ELi1ELi17ELi15ELi1ELi0E", "c4_emit": r"scan_emit_kernelILi1ELi0ELin1ELin1ELb0ELb1E",
+               "c5_count": r"scan_count_kernelILb1ELi2ELi21ELi11ELi1ELi1E", "c5_emit": r"scan_emit_kernelILi2ELi0ELin1ELin1ELb0ELb0E",
                # the tiles pass 1 could not decide, counted again (inside the region bench.py's kernel events bracket): a few launches' worth of waves
-               "c3_redo": r"scan_redo_frl_kernelILi0ELi11ELi15ELi31ELi150ELi1E", "c5_redo": r"scan_redo_kernelILi2ELi21ELi11ELi1E"}
+               "c3_redo": r"scan_redo_frl_kernelILb1ELi0ELi11ELi15ELi31ELi150ELi1E", "c5_redo": r"scan_redo_kernelILb1ELi2ELi21ELi11ELi1E"}
     out = {"provenance": {"pmc": pmc["provenance"], "ubench": f"profiles/{RND}_ubench_valu.json (same collection run)", "census": "hipcc -DBL_CENSUS_HOT -S of biolib_amd/csrc/bl_kernels.hip, tools/isa_census.py",
                           "tool": "tools/valu_model.py"},
            "issue_cycles": {"cheapest_class (v_add/v_sub/v_xor/v_and/v_or/v_mov/v_lshrrev)": round(cheapest, 3), "v_mul_lo_u32": round(cyc["v_mul_lo_u32"], 3),
