@@ -180,7 +180,7 @@ __device__ __forceinline__ void count_tile(const ScanParams& p, TileShared<MODE,
 #endif
     constexpr bool MAX = MODE != MODE_SYNCMER && SY == 2;  // minimizer / super-k-mer scans: windows decided on murmur64_top, the exact form in scan_redo_kernel
     if (DIRECT) phase_hash_closed<MODE, W, (DIRECT ? U : 1), SY == 2, AP>(p, sh, tid, st, &tie);
-    else phase_hash<MODE, W, (MODE != MODE_SYNCMER && U >= 1 && U <= 16 ? U : 0), U == 0, MAX>(p, sh, tid, st);
+    else phase_hash<MODE, W, (MODE != MODE_SYNCMER && U >= 1 && U <= 16 ? U : 0), U == 0, MAX, (MODE != MODE_SYNCMER && U >= 17 && U <= 31 ? U : 0)>(p, sh, tid, st);
 
     uint32_t packed;
     if constexpr (MODE == MODE_SYNCMER && CS && W < 0) {  // closed syncmers for any (k, s): w by run time (W = -8: w <= 17, W = -16: 18 <= w <= 32)

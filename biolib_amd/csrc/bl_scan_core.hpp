@@ -473,6 +473,27 @@ BL_DEV uint32_t funnel_shr(uint32_t hi, uint32_t lo, int n)
 #endif
 }
 
+// The smaller of two units of U <= 31 bases (the canonical form, kmer_view.hpp:196) as ONE instruction on the GPU, where the integer
+// form is a 64-bit compare and two selects (gfx950 has no 64-bit integer minimum).
+// Precondition: a, b < 2^62, which 2 * U <= 62 bits of codes guarantee.  Read as IEEE doubles such patterns have sign 0 and an exponent
+// field of at most 0x3ff: +0, subnormal or normal, never a NaN or an infinity.  Non-negative finite doubles are ordered as their bit
+// patterns are as integers, and v_min_f64 hands back one of its operands bit for bit; the kernels are built with f64 denormals kept
+// (.amdhsa_float_denorm_mode_16_64 3), so patterns below 2^52 (units that begin with five or more A's) come through as they are.
+// (__builtin_fmin would add two canonicalising v_max_f64.)  Units of 32 bases use all 64 bits — sign bit and NaN patterns — and keep
+// the integer form, as do the 128-bit units; so does a unit length known only at run time.  Host and CPU emulation: the integer minimum.
+template <int U>
+BL_DEV uint64_t min62(uint64_t a, uint64_t b)
+{
+    static_assert(U >= 1 && U <= 31, "min62: both values must lie below 2^62 (units of at most 31 bases)");
+#if defined(__HIP_DEVICE_COMPILE__) && !defined(BL_CPU_EMU)
+    uint64_t d;
+    asm("v_min_f64 %0, %1, %2" : "=v"(d) : "v"(a), "v"(b));
+    return d;
+#else
+    return a < b ? a : b;
+#endif
+}
+
 BL_DEV void roller_start(Roller& r, uint32_t c0, uint32_t c1, uint32_t c2, int unit)
 {
     const uint64_t A = ((uint64_t)c0 << 32) | c1;  // bases 0..31

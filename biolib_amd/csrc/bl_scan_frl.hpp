@@ -127,7 +127,7 @@ BL_DEV void phase_hash_frl(const ScanParams& p, TileShared<MODE, W>& sh, int tid
         for (int s = 0; s < NS; ++s) {
             uint64_t fw, rv;
             units_direct<31>(a0, a1, a2, r0, r1, r2, s, fw, rv);
-            const uint64_t v = (p.canonical && rv < fw) ? rv : fw;  // minimizer_view.hpp:236-238
+            const uint64_t v = p.canonical ? min62<31>(rv, fw) : fw;  // minimizer_view.hpp:236-238
             st.h[s] = APPROX ? (uint64_t)murmur64_top<true>(v, p.seed) << 32 : murmur64(v, p.seed);
         }
         return;

@@ -249,7 +249,8 @@ BL_DEV uint32_t revcomp16(uint32_t c)
 // spilled into the hashing loop with it (unit 15, w 10 on 150-bp reads: 381 -> 218 Gbp/s until this was noticed).
 // APPROX (minimizer scans, rolling registers): st.h[s] holds murmur64_top in its high dword (low dword 0) and st.hmax the largest of them, as in
 // phase_hash_frl: the window phase works on those and reports what it cannot decide
-template <int MODE, int W, int U = 0, bool GENERIC = false, bool APPROX = false>
+// U62: the unit length where the kernel fixes it at 17..31 (rolling registers, values below 2^62: the canonical one by min62); 0 otherwise
+template <int MODE, int W, int U = 0, bool GENERIC = false, bool APPROX = false, int U62 = 0>
 BL_DEV void phase_hash(const ScanParams& p, TileShared<MODE, W>& sh, int tid, ThreadState& st)
 {
     const int wv = wave_index(tid), lane = tid & 63;
@@ -298,7 +299,9 @@ BL_DEV void phase_hash(const ScanParams& p, TileShared<MODE, W>& sh, int tid, Th
         for (int s = 0; s < S; ++s) {
             roller_step(r, s);
             const uint64_t fw = roller_fwd(r), rv = roller_rc(r);
-            const uint64_t v = (p.canonical && rv < fw) ? rv : fw;  // minimizer_view.hpp:236-238
+            uint64_t v;  // minimizer_view.hpp:236-238
+            if constexpr (U62 != 0) v = p.canonical ? min62<U62>(rv, fw) : fw;
+            else v = (p.canonical && rv < fw) ? rv : fw;
             if (APPROX) {
                 const uint32_t top = murmur64_top(v, p.seed);
                 hmax = top > hmax ? top : hmax;
@@ -1306,8 +1309,8 @@ BL_DEV Record emit_prepare(const ScanParams& p, const uint32_t* codes, int64_t q
 // The canonical 31-mer at tile-relative base `pos` from the tile's codes AND their reverse complement, both staged in LDS by pass 2
 // (scan_emit_kernel's C3 form): cf[c] = chunk c, cr[c] = revcomp16(chunk nc - 1 - c), so base i of cr is the complement of base
 // 16 nc - 1 - i of cf.  Each strand is the 64 bits that END at its last base — two v_alignbit_b32 over three dwords, whose shift
-// (30 - 2 * (e & 15), taken modulo 32 by the instruction) never needs to be 32 — and a mask of the top pair; one 64-bit compare and
-// two selects pick the canonical one.  extract_unit builds the reverse complement of every record by pair-reversal instead.
+// (30 - 2 * (e & 15), taken modulo 32 by the instruction) never needs to be 32 — and a mask of the top pair; min62 (one v_min_f64)
+// picks the canonical one.  extract_unit builds the reverse complement of every record by pair-reversal instead.
 // cf[-1] and cr[-1] must be readable: a unit that ends in chunk 1 takes (and masks away) up to two bits of the dword in front.
 // FENCED: the forward strand is complete before the reverse one is read (pass 2's looped form lives on 28 registers)
 template <bool FENCED = false>
@@ -1319,7 +1322,7 @@ BL_DEV uint64_t unit31_canonical(const uint32_t* cf, const uint32_t* cr, int nc,
     if (FENCED) BL_SCHED_FENCE();
     const uint32_t rlo = funnel_shr(cr[qr - 1], cr[qr], shr & 31), rhi = funnel_shr(cr[qr - 2], cr[qr - 1], shr & 31) & 0x3fffffffu;
     const uint64_t fw = ((uint64_t)fhi << 32) | flo, rv = ((uint64_t)rhi << 32) | rlo;
-    return rv < fw ? rv : fw;  // numeric min, kmer_view.hpp:196
+    return min62<31>(rv, fw);  // numeric min, kmer_view.hpp:196
 }
 
 // 5a for the C3 shape (minimizers, 31-mers, canonical, read-tiled): the unit from both staged strands (unit31_canonical)

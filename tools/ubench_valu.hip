@@ -150,6 +150,25 @@ KERNELC(k_fmix64, bl::fmix64(x))
 KERNELC(k_murmur64, bl::murmur64(x, seed))
 KERNELC(k_min64, x < k ? x : k)
 
+// v_min_f64 on two 64-bit registers whose values stay below 2^62 (both read as subnormal doubles here, as k-mers that begin
+// with A's do): the one-instruction form of the row above
+__global__ __launch_bounds__(256) void k_min_f64(Stamp* out, uint32_t* sink, uint32_t seed)
+{
+    uint64_t r[UNROLL];
+    for (int i = 0; i < UNROLL; ++i) r[i] = ((uint64_t)seed << 32) + threadIdx.x * 31u + i;
+    uint64_t k = ((uint64_t)seed << 33) | 0x9e3779b1u;
+    asm volatile("" : "+v"(k));
+    unsigned long long c0, t0;
+    stamp_begin(c0, t0);
+    for (int it = 0; it < ITERS; ++it) {
+        _Pragma("unroll") for (int i = 0; i < UNROLL; ++i) asm volatile("v_min_f64 %0, %0, %1" : "+v"(r[i]) : "v"(k));
+    }
+    stamp_end(out, c0, t0);
+    uint64_t acc = 0;
+    for (int i = 0; i < UNROLL; ++i) acc ^= r[i];
+    if (acc == 0x12345678u) sink[0] = (uint32_t)acc;
+}
+
 struct K {
     const char* name;
     void (*fn)(Stamp*, uint32_t*, uint32_t);
@@ -192,6 +211,7 @@ int main(int argc, char** argv)
         {"v_lshl_add_u64", k_lshl_add_u64, 0}, {"v_mov_b64", k_mov_b64, 0},
         {"C: x + k (u64)", k_add64, 1}, {"C: x * const (u64)", k_mul64c, 1}, {"C: mul64c(x, const): mul_lo + 2 mad + mov", k_mul64split, 1}, {"C: x ^ (x >> 33)", k_xorshift33, 1}, {"C: rotl64(x, 31)", k_rotl31, 1},
         {"C: fmix64", k_fmix64, 1}, {"C: murmur64 (whole hash)", k_murmur64, 1}, {"C: min(x, k) (u64)", k_min64, 1},
+        {"v_min_f64", k_min_f64, 0},
     };
     const int wps_list[4] = {1, 2, 4, 8};
     hipEvent_t e0, e1;
