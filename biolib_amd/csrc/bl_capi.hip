@@ -14,6 +14,7 @@
 #include <vector>
 
 #include "../../include/biolib_amd.h"
+#include "bl_host.hpp"
 #include "bl_launch.hpp"
 #include "bl_lookup_launch.hpp"
 #include "bl_read_counts_launch.hpp"
@@ -31,13 +32,8 @@ int fail(int code, const std::string& msg)
 
 }  // namespace
 
-// used by the host-only translation units of the library (bl_ingest.cpp)
+// what this file defines for the other translation units of the library is declared in bl_host.hpp
 int bl_set_error(int code, const char* msg) { return fail(code, msg ? msg : ""); }
-struct bl_ctx;
-hipStream_t bl_ctx_stream(bl_ctx* ctx);
-int bl_ctx_device(bl_ctx* ctx);
-void* bl_ctx_pool_alloc(bl_ctx* ctx, size_t bytes);
-void bl_ctx_pool_free(bl_ctx* ctx, void* p);
 
 namespace {
 
@@ -380,7 +376,6 @@ hipStream_t bl_ctx_stream(bl_ctx* c)
     if (c->n_lanes == 2 && c->lanes[1].scan_recorded) (void)hipStreamWaitEvent(c->lanes[0].own, c->lanes[1].ev_stop, 0);
     return c->lanes[0].own;
 }
-int bl_batch_adopt_device(bl_ctx* ctx, void* d_bases, uint64_t n_bases, uint64_t* d_offsets, uint64_t n_seqs, uint64_t fixed_len, bl_batch** out);
 int bl_ctx_device(bl_ctx* c) { return c->device; }
 int bl_ctx_count128_tables(bl_ctx* c) { return c->count128_tables ? 1 : 0; }  // bl_superkmer128.hip
 int bl_ctx_jaccard128_path(bl_ctx* c) { return c->jaccard128_path; }            // bl_setops128.hip
@@ -410,9 +405,7 @@ int bl_batch_scan_view(bl_ctx* c, const bl_batch* b, int ensure, const uint32_t*
 // Device scratch that lives with the context (slot 0..7), grown on demand and never shrunk: the set operations and the
 // bucketed counter need gigabytes of temporary space per call, and hipMalloc / hipFree of that size costs more than their
 // kernels.  The caller has synchronised its previous use (these entry points are synchronous).  nullptr on failure.
-// Who uses what: 0-3 the k-mer counter and the text parser (which call the set operations while holding them), 4-6 the set
-// operations themselves (4 data, 5 library workspace, 6 counters).  The table algebra, the quantiles, select, the corrector and the
-// table graph (bl_graph.hip: about 133 bytes per key in slot 4) use 4-6 the same way: none of them calls another while holding them.
+// Who uses which slot: the table in bl_host.hpp.
 void* bl_ctx_scratch(bl_ctx* c, int slot, size_t bytes)
 {
     if (!c || slot < 0 || slot >= 8) return nullptr;

@@ -9,18 +9,10 @@
 // No atomic decides a mark or a placement: a rerun is bit-identical.
 #include <hip/hip_runtime.h>
 
-#include <rocprim/device/device_scan.hpp>
-
-#include <new>
-
 #include "../../include/biolib_amd.h"
 #include "bl_clean_core.hpp"
+#include "bl_host.hpp"
 #include "bl_lookup_launch.hpp"
-
-extern int bl_set_error(int code, const char* msg);  // bl_capi.hip
-extern hipStream_t bl_ctx_stream(bl_ctx* ctx);
-extern int bl_ctx_device(bl_ctx* ctx);
-extern void* bl_ctx_scratch(bl_ctx* ctx, int slot, size_t bytes);  // as the graph: 4 data, 5 library workspace, 6 counters
 
 static_assert(sizeof(bl_clean_rule) == sizeof(blcl::Rule) && sizeof(bl_clean_rule) == 56 && sizeof(bl_clean_stats) == 8 * sizeof(uint64_t), "the header's structs");
 static_assert((uint32_t)BL_CLEAN_TIPS == blcl::TIPS && (uint32_t)BL_CLEAN_ISOLATED == blcl::ISOLATED && (uint32_t)BL_CLEAN_BUBBLES == blcl::BUBBLES &&
@@ -107,20 +99,14 @@ __global__ __launch_bounds__(CTPB) void write_kernel(const bllnk::Node* __restri
 
 namespace {
 
-int hip_rc(hipError_t e) { return bl_set_error(e == hipErrorOutOfMemory ? BL_ERR_OOM : BL_ERR_HIP, hipGetErrorString(e)); }
-int invalid(const char* msg) { return bl_set_error(BL_ERR_INVALID, msg); }
+using blh::hip_rc;
+using blh::invalid;
 unsigned blocks_for(uint64_t threads) { return (unsigned)((threads + CTPB - 1) / CTPB); }
-
-#define C_HIP(call)                              \
-    do {                                         \
-        hipError_t e_ = (call);                  \
-        if (e_ != hipSuccess) return hip_rc(e_); \
-    } while (0)
 
 template <int W>
 int remove_marked(bl_ctx* ctx, const bl_table* table, const bllnk::Node* nodes, const uint8_t* marks, uint64_t n_unitigs, bl_table** out, uint64_t* n_removed)
 {
-    C_HIP(hipSetDevice(bl_ctx_device(ctx)));
+    BLH_TRY(hipSetDevice(bl_ctx_device(ctx)));
     hipStream_t s = bl_ctx_stream(ctx);
     const uint64_t n = table->view.n;
     const uint64_t n_tiles = tiles_of<ROWS>(n);
@@ -132,40 +118,23 @@ int remove_marked(bl_ctx* ctx, const bl_table* table, const bllnk::Node* nodes, 
         totals = static_cast<uint64_t*>(bl_ctx_scratch(ctx, 4, 2 * (n_tiles + 1) * sizeof(uint64_t)));
         if (!totals) return bl_set_error(BL_ERR_OOM, "scratch allocation failed");
         bases = totals + n_tiles + 1;
-        C_HIP(hipMemsetAsync(totals + n_tiles, 0, sizeof(uint64_t), s));
+        BLH_TRY(hipMemsetAsync(totals + n_tiles, 0, sizeof(uint64_t), s));
         hipLaunchKernelGGL(count_kernel<ROWS>, dim3(blocks_for(n_tiles * 64)), dim3(CTPB), 0, s, nodes, marks, n_unitigs, n, n_tiles, totals);
-        C_HIP(hipGetLastError());
-        size_t bytes = 0;
-        C_HIP(rocprim::exclusive_scan(nullptr, bytes, totals, bases, (uint64_t)0, (size_t)(n_tiles + 1), rocprim::plus<uint64_t>(), s));
-        void* tmp = bl_ctx_scratch(ctx, 5, bytes ? bytes : 16);
-        if (!tmp) return bl_set_error(BL_ERR_OOM, "scratch allocation failed");
-        C_HIP(rocprim::exclusive_scan(tmp, bytes, totals, bases, (uint64_t)0, (size_t)(n_tiles + 1), rocprim::plus<uint64_t>(), s));
-        C_HIP(hipMemcpyAsync(&n_out, bases + n_tiles, sizeof(n_out), hipMemcpyDeviceToHost, s));
-        C_HIP(hipStreamSynchronize(s));
+        BLH_TRY(hipGetLastError());
+        const int rc = blh::exclusive_sum(ctx, totals, bases, (size_t)(n_tiles + 1), s);
+        if (rc != BL_OK) return rc;
+        BLH_TRY(hipMemcpyAsync(&n_out, bases + n_tiles, sizeof(n_out), hipMemcpyDeviceToHost, s));
+        BLH_TRY(hipStreamSynchronize(s));
         if (n_out > n) return bl_set_error(BL_ERR_INTERNAL, "the count pass kept more keys than the table holds");
     }
-    bl_table* t = new (std::nothrow) bl_table{};
-    if (!t) return bl_set_error(BL_ERR_OOM, "out of host memory");
-    t->ctx = ctx;
-    t->device = bl_ctx_device(ctx);
-    t->view.key_words = table->view.key_words;
-    t->view.key_bits = table->view.key_bits;
-    t->view.n = (uint32_t)n_out;
+    bl_table* t = nullptr;
+    const int rc = bllk::new_table(ctx, table->view.key_words, table->view.key_bits, n_out, &t);
+    if (rc != BL_OK) return rc;
     hipError_t e = hipSuccess;
     if (n_out) {
-        void* keys = nullptr;
-        void* counts = nullptr;
-        e = hipMalloc(&keys, (size_t)n_out * W * sizeof(uint64_t));
-        if (e == hipSuccess) {
-            t->view.keys = static_cast<uint64_t*>(keys);
-            e = hipMalloc(&counts, (size_t)n_out * sizeof(uint32_t));
-        }
-        if (e == hipSuccess) {
-            t->view.counts = static_cast<uint32_t*>(counts);
-            hipLaunchKernelGGL((write_kernel<W, ROWS>), dim3(blocks_for(n_tiles * 64)), dim3(CTPB), 0, s, nodes, marks, n_unitigs, table->view.keys,
-                               table->view.counts, n, n_tiles, bases, (uint64_t)n_out, static_cast<uint64_t*>(keys), static_cast<uint32_t*>(counts));
-            e = hipGetLastError();
-        }
+        hipLaunchKernelGGL((write_kernel<W, ROWS>), dim3(blocks_for(n_tiles * 64)), dim3(CTPB), 0, s, nodes, marks, n_unitigs, table->view.keys,
+                           table->view.counts, n, n_tiles, bases, (uint64_t)n_out, const_cast<uint64_t*>(t->view.keys), const_cast<uint32_t*>(t->view.counts));
+        e = hipGetLastError();
     }
     if (e == hipSuccess) e = bllk::finish_table(ctx, t, s);
     if (e != hipSuccess) {
@@ -199,18 +168,18 @@ extern "C" int bl_unitigs_mark(bl_ctx* ctx, const uint64_t* d_unitig_offsets, co
     if (n_links && !d_links) return invalid("d_links is NULL with n_links > 0");
     if (stats) stats->n_unitigs = n_unitigs;
     if (n_unitigs == 0) return BL_OK;
-    C_HIP(hipSetDevice(bl_ctx_device(ctx)));
+    BLH_TRY(hipSetDevice(bl_ctx_device(ctx)));
     hipStream_t s = bl_ctx_stream(ctx);
     ull* d_counters = static_cast<ull*>(bl_ctx_scratch(ctx, 6, STRIPES * STRIPE_WORDS * sizeof(ull)));
     if (!d_counters) return bl_set_error(BL_ERR_OOM, "scratch allocation failed");
     Graph g{d_unitig_offsets, d_count_sums, d_link_offsets, reinterpret_cast<const bllnk::Link*>(d_links), n_unitigs, n_links};
     Rule r{rule->flags, rule->k, rule->max_tip_keys, rule->max_isolated_keys, rule->max_isolated_mean, rule->max_bubble_keys, rule->max_bubble_diff, 0};
     ull stripes[STRIPES * STRIPE_WORDS] = {}, host[5] = {};
-    C_HIP(hipMemsetAsync(d_counters, 0, sizeof(stripes), s));
+    BLH_TRY(hipMemsetAsync(d_counters, 0, sizeof(stripes), s));
     hipLaunchKernelGGL(mark_kernel, dim3(blocks_for(n_unitigs)), dim3(CTPB), 0, s, g, r, d_marks, d_counters);
-    C_HIP(hipGetLastError());
-    C_HIP(hipMemcpyAsync(stripes, d_counters, sizeof(stripes), hipMemcpyDeviceToHost, s));
-    C_HIP(hipStreamSynchronize(s));
+    BLH_TRY(hipGetLastError());
+    BLH_TRY(hipMemcpyAsync(stripes, d_counters, sizeof(stripes), hipMemcpyDeviceToHost, s));
+    BLH_TRY(hipStreamSynchronize(s));
     for (int i = 0; i < STRIPES; ++i)
         for (int j = 0; j < 5; ++j) host[j] += stripes[i * STRIPE_WORDS + j];
     if (stats) {

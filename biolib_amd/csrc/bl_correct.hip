@@ -12,23 +12,13 @@
 // No atomic decides where anything is stored; the only atomics add to the statistics words.
 #include <hip/hip_runtime.h>
 
-#include <rocprim/device/device_scan.hpp>
 #include <string>
 
 #include "../../include/biolib_amd.h"
 #include "bl_correct_core.hpp"
+#include "bl_host.hpp"
 #include "bl_lookup_launch.hpp"
 #include "bl_tile128.hpp"
-
-extern int bl_set_error(int code, const char* msg);  // bl_capi.hip
-extern hipStream_t bl_ctx_stream(bl_ctx* ctx);
-extern int bl_ctx_device(bl_ctx* ctx);
-extern void* bl_ctx_scratch(bl_ctx* ctx, int slot, size_t bytes);  // 0 candidates, 4 states and workgroup counts, 5 library workspace, 6 statistics
-extern void* bl_ctx_pool_alloc(bl_ctx* ctx, size_t bytes);         // batch buffers
-extern void bl_ctx_pool_free(bl_ctx* ctx, void* p);
-extern int bl_batch_describe(const bl_batch* batch, bl_ctx** ctx, uint64_t* n_bases, uint64_t* n_seqs, uint64_t* read_len);
-extern int bl_batch_scan_view(bl_ctx* ctx, const bl_batch* batch, int ensure, const uint32_t** start_bits);
-extern int bl_batch_adopt_like(bl_ctx* ctx, const bl_batch* like, void* d_bases, uint32_t* d_start_bits, bl_batch** out);
 
 static_assert(sizeof(blcr::Edit) == sizeof(bl_edit) && alignof(blcr::Edit) == 16, "Edit is bl_edit");
 static_assert(sizeof(bl_edit_stats) == blcr::STAT_WORDS * sizeof(uint64_t), "the statistics words are bl_edit_stats");
@@ -155,31 +145,14 @@ __global__ __launch_bounds__(CTPB) void apply_kernel(const Edit* edits, ull n_ed
 
 namespace {
 
-int hip_rc(hipError_t e) { return bl_set_error(e == hipErrorOutOfMemory ? BL_ERR_OOM : BL_ERR_HIP, hipGetErrorString(e)); }
 int invalid(const std::string& msg) { return bl_set_error(BL_ERR_INVALID, msg.c_str()); }
 unsigned blocks_for(ull threads) { return (unsigned)((threads + CTPB - 1) / CTPB); }
 size_t round16(size_t b) { return (b + 15) & ~(size_t)15; }
-
-int exclusive_sum(bl_ctx* ctx, const ull* in, ull* out, size_t n, hipStream_t s)
-{
-    size_t bytes = 0;
-    hipError_t e = rocprim::exclusive_scan(nullptr, bytes, in, out, (ull)0, n, rocprim::plus<ull>(), s);
-    if (e != hipSuccess) return hip_rc(e);
-    void* tmp = bl_ctx_scratch(ctx, 5, bytes ? bytes : 16);
-    if (!tmp) return bl_set_error(BL_ERR_OOM, "scratch allocation failed");
-    e = rocprim::exclusive_scan(tmp, bytes, in, out, (ull)0, n, rocprim::plus<ull>(), s);
-    return e == hipSuccess ? BL_OK : hip_rc(e);
-}
+static_assert(sizeof(ull) == sizeof(uint64_t), "blh::exclusive_sum sums the unit's counters as the 8-byte words they are");
 
 }  // namespace
 
 }  // namespace blcr
-
-#define C_HIP(call)                                   \
-    do {                                              \
-        hipError_t e_ = (call);                       \
-        if (e_ != hipSuccess) return blcr::hip_rc(e_); \
-    } while (0)
 
 extern "C" int bl_scan_read_edits(bl_ctx* ctx, const bl_batch* batch, uint64_t first, uint64_t n, uint32_t k, uint32_t flags, const bl_table* table,
                                   uint32_t min_count, uint32_t min_support, bl_edit* d_edits, uint64_t capacity, bl_edit_stats* stats)
@@ -210,7 +183,7 @@ extern "C" int bl_scan_read_edits(bl_ctx* ctx, const bl_batch* batch, uint64_t f
     const uint32_t* start_bits = nullptr;
     rc = bl_batch_scan_view(ctx, batch, 1, &start_bits);
     if (rc != BL_OK) return rc;
-    C_HIP(hipSetDevice(bl_ctx_device(ctx)));
+    BLH_TRY(hipSetDevice(bl_ctx_device(ctx)));
     hipStream_t s = bl_ctx_stream(ctx);
 
     // the states of the range, one position in front and k + 1 behind
@@ -234,9 +207,9 @@ extern "C" int bl_scan_read_edits(bl_ctx* ctx, const bl_batch* batch, uint64_t f
     sp.table = table->view;
     sp.min_count = min_count;
     sp.states = arena;
-    C_HIP(hipMemsetAsync(d_stats, 0, STAT_WORDS * sizeof(ull), s));
-    C_HIP(hipMemsetAsync(block_counts + n_blocks, 0, sizeof(ull), s));
-    C_HIP(bl::launch_tiles128(state_kernel, sp, sp.km.n_tiles, s));
+    BLH_TRY(hipMemsetAsync(d_stats, 0, STAT_WORDS * sizeof(ull), s));
+    BLH_TRY(hipMemsetAsync(block_counts + n_blocks, 0, sizeof(ull), s));
+    BLH_TRY(bl::launch_tiles128(state_kernel, sp, sp.km.n_tiles, s));
 
     RunParams rp{};
     rp.states = arena;
@@ -247,12 +220,12 @@ extern "C" int bl_scan_read_edits(bl_ctx* ctx, const bl_batch* batch, uint64_t f
     rp.k = k;
     rp.min_support = min_support;
     hipLaunchKernelGGL(run_kernel<false>, dim3((unsigned)n_blocks), dim3(CTPB), 0, s, rp, block_counts, (const ull*)nullptr, (Candidate*)nullptr, (ull)0, d_stats);
-    C_HIP(hipGetLastError());
-    rc = exclusive_sum(ctx, block_counts, block_base, (size_t)(n_blocks + 1), s);
+    BLH_TRY(hipGetLastError());
+    rc = blh::exclusive_sum(ctx, reinterpret_cast<const uint64_t*>(block_counts), reinterpret_cast<uint64_t*>(block_base), (size_t)(n_blocks + 1), s);
     if (rc != BL_OK) return rc;
     ull n_cand = 0;
-    C_HIP(hipMemcpyAsync(&n_cand, block_base + n_blocks, sizeof(n_cand), hipMemcpyDeviceToHost, s));
-    C_HIP(hipStreamSynchronize(s));
+    BLH_TRY(hipMemcpyAsync(&n_cand, block_base + n_blocks, sizeof(n_cand), hipMemcpyDeviceToHost, s));
+    BLH_TRY(hipStreamSynchronize(s));
 
     if (n_cand) {
         // slot 0: candidates | their edits | edit flags | the flags' exclusive sum | verdicts
@@ -265,7 +238,7 @@ extern "C" int bl_scan_read_edits(bl_ctx* ctx, const bl_batch* batch, uint64_t f
         ull* edit_sum = edit_flag + (n_cand + 1);
         uint8_t* verdicts = ca + 2 * rec + 2 * words;
         hipLaunchKernelGGL(run_kernel<true>, dim3((unsigned)n_blocks), dim3(CTPB), 0, s, rp, (ull*)nullptr, (const ull*)block_base, cand, n_cand, (ull*)nullptr);
-        C_HIP(hipGetLastError());
+        BLH_TRY(hipGetLastError());
         TestParams tp{};
         tp.bases = sp.km.bases;
         tp.n_bases = (int64_t)n_bases;
@@ -278,17 +251,17 @@ extern "C" int bl_scan_read_edits(bl_ctx* ctx, const bl_batch* batch, uint64_t f
         tp.edits = edits;
         tp.verdicts = verdicts;
         tp.edit_flag = reinterpret_cast<uint64_t*>(edit_flag);
-        C_HIP(hipMemsetAsync(edit_flag + n_cand, 0, sizeof(ull), s));
+        BLH_TRY(hipMemsetAsync(edit_flag + n_cand, 0, sizeof(ull), s));
         hipLaunchKernelGGL(test_kernel, dim3((unsigned)((n_cand + TEST_WAVES - 1) / TEST_WAVES)), dim3(CTPB), 0, s, tp);
-        C_HIP(hipGetLastError());
-        rc = exclusive_sum(ctx, edit_flag, edit_sum, (size_t)(n_cand + 1), s);
+        BLH_TRY(hipGetLastError());
+        rc = blh::exclusive_sum(ctx, reinterpret_cast<const uint64_t*>(edit_flag), reinterpret_cast<uint64_t*>(edit_sum), (size_t)(n_cand + 1), s);
         if (rc != BL_OK) return rc;
         hipLaunchKernelGGL(compact_kernel, dim3(blocks_for(n_cand)), dim3(CTPB), 0, s, edits, verdicts, (const ull*)edit_sum, n_cand, reinterpret_cast<Edit*>(d_edits), (ull)capacity, d_stats);
-        C_HIP(hipGetLastError());
+        BLH_TRY(hipGetLastError());
     }
     ull host[STAT_WORDS] = {};
-    C_HIP(hipMemcpyAsync(host, d_stats, sizeof(host), hipMemcpyDeviceToHost, s));
-    C_HIP(hipStreamSynchronize(s));
+    BLH_TRY(hipMemcpyAsync(host, d_stats, sizeof(host), hipMemcpyDeviceToHost, s));
+    BLH_TRY(hipStreamSynchronize(s));
     if (stats) {
         stats->n_runs = host[STAT_RUNS];
         stats->n_edits = host[STAT_EDITS];
@@ -317,35 +290,26 @@ extern "C" int bl_batch_apply_edits(bl_ctx* ctx, const bl_batch* batch, const bl
     const uint32_t* start_bits = nullptr;  // (NULL on a fixed-length batch that has not needed them: the copy builds its own on demand)
     rc = bl_batch_scan_view(ctx, batch, 0, &start_bits);
     if (rc != BL_OK) return rc;
-    C_HIP(hipSetDevice(bl_ctx_device(ctx)));
+    BLH_TRY(hipSetDevice(bl_ctx_device(ctx)));
     hipStream_t s = bl_ctx_stream(ctx);
 
     const size_t bit_words = (size_t)((n_bases + 31) / 32 + 4);  // the length every maker of start bits gives them
-    uint8_t* d_bases = static_cast<uint8_t*>(bl_ctx_pool_alloc(ctx, (size_t)n_bases + 64));
-    uint32_t* d_bits = start_bits ? static_cast<uint32_t*>(bl_ctx_pool_alloc(ctx, bit_words * sizeof(uint32_t))) : nullptr;
-    if (!d_bases || (start_bits && !d_bits)) {
-        bl_ctx_pool_free(ctx, d_bases);
-        bl_ctx_pool_free(ctx, d_bits);
-        return bl_set_error(BL_ERR_OOM, "device allocation failed (batch)");
-    }
-    auto fail_free = [&](hipError_t err) {
-        bl_ctx_pool_free(ctx, d_bases);
-        bl_ctx_pool_free(ctx, d_bits);
-        return hip_rc(err);
-    };
+    blh::Pooled<uint8_t> d_bases(ctx, (size_t)n_bases + 64);
+    blh::Pooled<uint32_t> d_bits;
+    if (start_bits) d_bits = blh::Pooled<uint32_t>(ctx, bit_words * sizeof(uint32_t));
+    if (!d_bases || (start_bits && !d_bits)) return bl_set_error(BL_ERR_OOM, "device allocation failed (batch)");
     const uint8_t* src = static_cast<const uint8_t*>(bl_batch_device_bases(batch));
-    hipLaunchKernelGGL(copy_kernel, dim3(blocks_for(n_bases / 16 + 80)), dim3(CTPB), 0, s, src, d_bases, (ull)n_bases, (ull)64);  // 64 bytes of zeros behind the bases
-    hipError_t e = hipGetLastError();
-    if (e == hipSuccess && d_bits) {
-        hipLaunchKernelGGL(copy_kernel, dim3(blocks_for(bit_words * 4 / 16 + 16)), dim3(CTPB), 0, s, reinterpret_cast<const uint8_t*>(start_bits), reinterpret_cast<uint8_t*>(d_bits),
-                           (ull)(bit_words * 4), (ull)0);
-        e = hipGetLastError();
+    hipLaunchKernelGGL(copy_kernel, dim3(blocks_for(n_bases / 16 + 80)), dim3(CTPB), 0, s, src, d_bases.get(), (ull)n_bases, (ull)64);  // 64 bytes of zeros behind the bases
+    BLH_TRY(hipGetLastError());
+    if (d_bits) {
+        hipLaunchKernelGGL(copy_kernel, dim3(blocks_for(bit_words * 4 / 16 + 16)), dim3(CTPB), 0, s, reinterpret_cast<const uint8_t*>(start_bits),
+                           reinterpret_cast<uint8_t*>(d_bits.get()), (ull)(bit_words * 4), (ull)0);
+        BLH_TRY(hipGetLastError());
     }
-    if (e == hipSuccess && n_edits) {
-        hipLaunchKernelGGL(apply_kernel, dim3(blocks_for(n_edits)), dim3(CTPB), 0, s, reinterpret_cast<const Edit*>(d_edits), (ull)n_edits, d_bases, (ull)n_bases);
-        e = hipGetLastError();
+    if (n_edits) {
+        hipLaunchKernelGGL(apply_kernel, dim3(blocks_for(n_edits)), dim3(CTPB), 0, s, reinterpret_cast<const Edit*>(d_edits), (ull)n_edits, d_bases.get(), (ull)n_bases);
+        BLH_TRY(hipGetLastError());
     }
-    if (e == hipSuccess) e = hipStreamSynchronize(s);
-    if (e != hipSuccess) return fail_free(e);
-    return bl_batch_adopt_like(ctx, batch, d_bases, d_bits, out);  // takes ownership of both
+    BLH_TRY(hipStreamSynchronize(s));
+    return bl_batch_adopt_like(ctx, batch, d_bases.release(), d_bits.release(), out);  // takes ownership of both
 }

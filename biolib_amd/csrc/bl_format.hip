@@ -12,20 +12,13 @@
 #include <cerrno>
 #include <cstdio>
 #include <cstring>
-#include <rocprim/device/device_scan.hpp>
 #include <string>
 
 #include "../../include/biolib_amd.h"
 #include "bl_format_core.hpp"
+#include "bl_host.hpp"
 #include "bl_parse_core.hpp"
 
-extern int bl_set_error(int code, const char* msg);  // bl_capi.hip
-extern hipStream_t bl_ctx_stream(bl_ctx* ctx);
-extern int bl_ctx_device(bl_ctx* ctx);
-extern void* bl_ctx_scratch(bl_ctx* ctx, int slot, size_t bytes);  // as select: 4 data, 5 library workspace, 6 counters
-extern void* bl_ctx_pool_alloc(bl_ctx* ctx, size_t bytes);
-extern void bl_ctx_pool_free(bl_ctx* ctx, void* p);
-extern int bl_batch_describe(const bl_batch* batch, bl_ctx** ctx, uint64_t* n_bases, uint64_t* n_seqs, uint64_t* read_len);
 int bl_parse_device_text_lines(bl_ctx* ctx, const uint8_t* d_text_in, uint64_t n_bytes, char first_byte, const char* ends, uint64_t ends_n, bl_batch** out,
                                uint64_t* n_seqs, uint64_t* n_bases, bl_parse::LineIndex* lines);  // bl_parse.hip
 
@@ -123,20 +116,10 @@ __global__ __launch_bounds__(TPB) void format_kernel(const FormatParams p)
 
 namespace {
 
-int hip_rc(hipError_t e) { return bl_set_error(e == hipErrorOutOfMemory ? BL_ERR_OOM : BL_ERR_HIP, hipGetErrorString(e)); }
-int invalid(const char* msg) { return bl_set_error(BL_ERR_INVALID, msg); }
+using blh::exclusive_sum;
+using blh::hip_rc;
+using blh::invalid;
 unsigned blocks_for(uint64_t threads) { return (unsigned)((threads + TPB - 1) / TPB); }
-
-int exclusive_sum(bl_ctx* ctx, const uint64_t* in, uint64_t* out, size_t n, hipStream_t s)
-{
-    size_t bytes = 0;
-    hipError_t e = rocprim::exclusive_scan(nullptr, bytes, in, out, (uint64_t)0, n, rocprim::plus<uint64_t>(), s);
-    if (e != hipSuccess) return hip_rc(e);
-    void* tmp = bl_ctx_scratch(ctx, 5, bytes ? bytes : 16);
-    if (!tmp) return bl_set_error(BL_ERR_OOM, "scratch allocation failed");
-    e = rocprim::exclusive_scan(tmp, bytes, in, out, (uint64_t)0, n, rocprim::plus<uint64_t>(), s);
-    return e == hipSuccess ? BL_OK : hip_rc(e);
-}
 
 // a NUL inside the 16 bytes: the length; none: -1
 int terminated_length(const char* s)
@@ -395,7 +378,7 @@ extern "C" int bl_text_write(bl_ctx* ctx, const uint8_t* d_text, uint64_t n_byte
     constexpr size_t WRITE_CHUNK = (size_t)8 << 20;
     if (!ctx || !path || (n_bytes && !d_text)) return bl_set_error(BL_ERR_INVALID, "NULL argument");
     hipError_t e = hipSetDevice(bl_ctx_device(ctx));
-    if (e != hipSuccess) return blfmt::hip_rc(e);
+    if (e != hipSuccess) return blh::hip_rc(e);
     FILE* f = std::fopen(path, append ? "ab" : "wb");
     if (!f) return bl_set_error(BL_ERR_IO, (std::string("cannot open ") + path + ": " + std::strerror(errno)).c_str());
     hipStream_t s = bl_ctx_stream(ctx);
@@ -406,7 +389,7 @@ extern "C" int bl_text_write(bl_ctx* ctx, const uint8_t* d_text, uint64_t n_byte
     for (int i = 0; i < 2 && rc == BL_OK && n_bytes; ++i) {
         e = hipHostMalloc(reinterpret_cast<void**>(&buf[i]), chunk ? chunk : 1, hipHostMallocDefault);
         if (e == hipSuccess) e = hipEventCreateWithFlags(&done[i], hipEventDisableTiming);
-        if (e != hipSuccess) rc = blfmt::hip_rc(e);
+        if (e != hipSuccess) rc = blh::hip_rc(e);
     }
     const uint64_t n_chunks = n_bytes ? (n_bytes + chunk - 1) / chunk : 0;
     auto enqueue = [&](uint64_t c) {
@@ -417,15 +400,15 @@ extern "C" int bl_text_write(bl_ctx* ctx, const uint8_t* d_text, uint64_t n_byte
     };
     if (rc == BL_OK && n_chunks) {
         e = enqueue(0);
-        if (e != hipSuccess) rc = blfmt::hip_rc(e);
+        if (e != hipSuccess) rc = blh::hip_rc(e);
     }
     for (uint64_t c = 0; c < n_chunks && rc == BL_OK; ++c) {
         if (c + 1 < n_chunks) {  // (buffer (c + 1) & 1 was written out in the step before)
             e = enqueue(c + 1);
-            if (e != hipSuccess) { rc = blfmt::hip_rc(e); break; }
+            if (e != hipSuccess) { rc = blh::hip_rc(e); break; }
         }
         e = hipEventSynchronize(done[c & 1]);
-        if (e != hipSuccess) { rc = blfmt::hip_rc(e); break; }
+        if (e != hipSuccess) { rc = blh::hip_rc(e); break; }
         const uint64_t at = c * chunk, n = n_bytes - at < chunk ? n_bytes - at : chunk;
         if (std::fwrite(buf[c & 1], 1, n, f) != n) rc = bl_set_error(BL_ERR_IO, (std::string("short write to ") + path + ": " + std::strerror(errno)).c_str());
     }

@@ -18,21 +18,12 @@
 // No atomic decides a placement: a rerun is bit-identical.
 #include <hip/hip_runtime.h>
 
-#include <rocprim/device/device_scan.hpp>
-
 #include <string>
 
 #include "../../include/biolib_amd.h"
 #include "bl_graph_core.hpp"
+#include "bl_host.hpp"
 #include "bl_lookup_launch.hpp"
-
-extern int bl_set_error(int code, const char* msg);  // bl_capi.hip
-extern hipStream_t bl_ctx_stream(bl_ctx* ctx);
-extern int bl_ctx_device(bl_ctx* ctx);
-extern void* bl_ctx_scratch(bl_ctx* ctx, int slot, size_t bytes);  // as the set operations: 4 data, 5 library workspace, 6 counters
-extern void* bl_ctx_pool_alloc(bl_ctx* ctx, size_t bytes);         // batch buffers
-extern void bl_ctx_pool_free(bl_ctx* ctx, void* p);
-extern int bl_batch_adopt_device(bl_ctx* ctx, void* d_bases, uint64_t n_bases, uint64_t* d_offsets, uint64_t n_seqs, uint64_t fixed_len, bl_batch** out);
 
 static_assert(BL_LINK_NONE == blgr::LINK_NONE, "the header's constant");
 static_assert(sizeof(bl_unitig_node) == 8 && sizeof(bl_graph_stats) == 12 * sizeof(uint64_t), "the device words are the caller's");
@@ -174,20 +165,10 @@ __global__ __launch_bounds__(GTPB) void uniform_kernel(const uint64_t* offsets, 
 
 namespace {
 
-int hip_rc(hipError_t e) { return bl_set_error(e == hipErrorOutOfMemory ? BL_ERR_OOM : BL_ERR_HIP, hipGetErrorString(e)); }
-int invalid(const char* msg) { return bl_set_error(BL_ERR_INVALID, msg); }
+using blh::exclusive_sum;
+using blh::hip_rc;
+using blh::invalid;
 unsigned blocks_for(uint64_t threads) { return (unsigned)((threads + GTPB - 1) / GTPB); }
-
-int exclusive_sum(bl_ctx* ctx, const uint64_t* in, uint64_t* out, size_t n, hipStream_t s)
-{
-    size_t bytes = 0;
-    hipError_t e = rocprim::exclusive_scan(nullptr, bytes, in, out, (uint64_t)0, n, rocprim::plus<uint64_t>(), s);
-    if (e != hipSuccess) return hip_rc(e);
-    void* tmp = bl_ctx_scratch(ctx, 5, bytes ? bytes : 16);
-    if (!tmp) return bl_set_error(BL_ERR_OOM, "scratch allocation failed");
-    e = rocprim::exclusive_scan(tmp, bytes, in, out, (uint64_t)0, n, rocprim::plus<uint64_t>(), s);
-    return e == hipSuccess ? BL_OK : hip_rc(e);
-}
 
 // what both calls refuse before anything runs
 int check_arguments(bl_ctx* ctx, const bl_table* table, uint32_t k)
@@ -222,39 +203,33 @@ struct AdjBuffers {
     uint32_t* links;  // 2n, nullable
 };
 
-#define G_HIP(call)                              \
-    do {                                         \
-        hipError_t e_ = (call);                  \
-        if (e_ != hipSuccess) return hip_rc(e_); \
-    } while (0)
-
 // the key check, the mask pass, the link pass and the first six statistics (n > 0; the device is set); waits for the stream
 template <int W>
 int adjacency(const TableView& t, uint32_t k, const AdjBuffers& b, ull* d_counters, bl_graph_stats* stats, hipStream_t s)
 {
     const uint64_t n = t.n;
     uint32_t* d_words = reinterpret_cast<uint32_t*>(d_counters) + C_WORDS32;
-    G_HIP(hipMemsetAsync(d_counters, 0, 8 * sizeof(ull), s));
-    G_HIP(hipMemsetAsync(d_words, 0xFF, sizeof(uint32_t), s));
+    BLH_TRY(hipMemsetAsync(d_counters, 0, 8 * sizeof(ull), s));
+    BLH_TRY(hipMemsetAsync(d_words, 0xFF, sizeof(uint32_t), s));
     hipLaunchKernelGGL(check_kernel<W>, dim3(blocks_for(n)), dim3(GTPB), 0, s, t, k, d_words);
-    G_HIP(hipGetLastError());
+    BLH_TRY(hipGetLastError());
     uint32_t first_bad = 0;
-    G_HIP(hipMemcpyAsync(&first_bad, d_words, sizeof(first_bad), hipMemcpyDeviceToHost, s));
-    G_HIP(hipStreamSynchronize(s));
+    BLH_TRY(hipMemcpyAsync(&first_bad, d_words, sizeof(first_bad), hipMemcpyDeviceToHost, s));
+    BLH_TRY(hipStreamSynchronize(s));
     if (first_bad != LINK_NONE)
         return invalid(("the key at slot " + std::to_string(first_bad) + " has a bit at or above 2k or exceeds its own reverse complement: not a table of canonical k-mers of this k").c_str());
     hipLaunchKernelGGL(mask_kernel<W>, dim3(blocks_for(n)), dim3(GTPB), 0, s, t, k, b.mask, reinterpret_cast<uint2*>(b.nbr));
-    G_HIP(hipGetLastError());
+    BLH_TRY(hipGetLastError());
     if (b.links) {
         hipLaunchKernelGGL(link_kernel, dim3(blocks_for(2 * n)), dim3(GTPB), 0, s, b.mask, b.nbr, b.links, 2 * n);
-        G_HIP(hipGetLastError());
+        BLH_TRY(hipGetLastError());
     }
     if (stats) {
         hipLaunchKernelGGL(stats_kernel, dim3(blocks_for(n)), dim3(GTPB), 0, s, b.mask, b.links, n, d_counters);
-        G_HIP(hipGetLastError());
+        BLH_TRY(hipGetLastError());
         ull host[5] = {};
-        G_HIP(hipMemcpyAsync(host, d_counters, sizeof(host), hipMemcpyDeviceToHost, s));
-        G_HIP(hipStreamSynchronize(s));
+        BLH_TRY(hipMemcpyAsync(host, d_counters, sizeof(host), hipMemcpyDeviceToHost, s));
+        BLH_TRY(hipStreamSynchronize(s));
         stats->n_keys = n;
         stats->n_arcs = host[0];
         stats->n_isolated = host[1];
@@ -269,15 +244,15 @@ int adjacency(const TableView& t, uint32_t k, const AdjBuffers& b, ull* d_counte
 int label(const uint32_t* links, Rec*& cur, Rec*& nxt, uint64_t n_states, uint32_t rounds, uint32_t* d_flag, bool& settled, hipStream_t s)
 {
     hipLaunchKernelGGL(label_init_kernel, dim3(blocks_for(n_states)), dim3(GTPB), 0, s, links, cur, n_states);
-    G_HIP(hipGetLastError());
+    BLH_TRY(hipGetLastError());
     settled = false;
     for (uint32_t r = 0; r < rounds && !settled; ++r) {
-        G_HIP(hipMemsetAsync(d_flag, 0, sizeof(uint32_t), s));
+        BLH_TRY(hipMemsetAsync(d_flag, 0, sizeof(uint32_t), s));
         hipLaunchKernelGGL(label_step_kernel, dim3(blocks_for(n_states)), dim3(GTPB), 0, s, cur, nxt, n_states, d_flag);
-        G_HIP(hipGetLastError());
+        BLH_TRY(hipGetLastError());
         uint32_t any = 0;
-        G_HIP(hipMemcpyAsync(&any, d_flag, sizeof(any), hipMemcpyDeviceToHost, s));
-        G_HIP(hipStreamSynchronize(s));
+        BLH_TRY(hipMemcpyAsync(&any, d_flag, sizeof(any), hipMemcpyDeviceToHost, s));
+        BLH_TRY(hipStreamSynchronize(s));
         Rec* swap = cur;
         cur = nxt;
         nxt = swap;
@@ -289,22 +264,17 @@ int label(const uint32_t* links, Rec*& cur, Rec*& nxt, uint64_t n_states, uint32
 // the empty table's result: a valid batch of 0 bases and 0 sequences, as bl_batch_select makes one
 int empty_result(bl_ctx* ctx, bl_batch** out, uint64_t* d_out_offsets, hipStream_t s)
 {
-    if (d_out_offsets) G_HIP(hipMemsetAsync(d_out_offsets, 0, sizeof(uint64_t), s));
+    if (d_out_offsets) BLH_TRY(hipMemsetAsync(d_out_offsets, 0, sizeof(uint64_t), s));
     if (out) {
-        uint8_t* d_bases = static_cast<uint8_t*>(bl_ctx_pool_alloc(ctx, 64));
-        uint64_t* d_offs = static_cast<uint64_t*>(bl_ctx_pool_alloc(ctx, sizeof(uint64_t)));
-        hipError_t e = d_bases && d_offs ? hipSuccess : hipErrorOutOfMemory;
-        if (e == hipSuccess) e = hipMemsetAsync(d_bases, 0, 64, s);
-        if (e == hipSuccess) e = hipMemsetAsync(d_offs, 0, sizeof(uint64_t), s);
-        if (e == hipSuccess) e = hipStreamSynchronize(s);
-        if (e != hipSuccess) {
-            bl_ctx_pool_free(ctx, d_bases);
-            bl_ctx_pool_free(ctx, d_offs);
-            return hip_rc(e);
-        }
-        return bl_batch_adopt_device(ctx, d_bases, 0, d_offs, 0, 0, out);  // takes ownership of both
+        blh::Pooled<uint8_t> d_bases(ctx, 64);
+        blh::Pooled<uint64_t> d_offs(ctx, sizeof(uint64_t));
+        if (!d_bases || !d_offs) return hip_rc(hipErrorOutOfMemory);
+        BLH_TRY(hipMemsetAsync(d_bases.get(), 0, 64, s));
+        BLH_TRY(hipMemsetAsync(d_offs.get(), 0, sizeof(uint64_t), s));
+        BLH_TRY(hipStreamSynchronize(s));
+        return bl_batch_adopt_device(ctx, d_bases.release(), 0, d_offs.release(), 0, 0, out);  // takes ownership of both
     }
-    G_HIP(hipStreamSynchronize(s));
+    BLH_TRY(hipStreamSynchronize(s));
     return BL_OK;
 }
 
@@ -353,9 +323,9 @@ int unitigs(bl_ctx* ctx, const bl_table* table, uint32_t k, bl_batch** out, uint
     if (rc != BL_OK) return rc;
     if (!settled) {
         hipLaunchKernelGGL(cut_kernel, dim3(blocks_for(n)), dim3(GTPB), 0, s, cur, b.links, n, d_counters);
-        G_HIP(hipGetLastError());
-        G_HIP(hipMemcpyAsync(&cuts, d_counters + C_CUTS, sizeof(cuts), hipMemcpyDeviceToHost, s));
-        G_HIP(hipStreamSynchronize(s));
+        BLH_TRY(hipGetLastError());
+        BLH_TRY(hipMemcpyAsync(&cuts, d_counters + C_CUTS, sizeof(cuts), hipMemcpyDeviceToHost, s));
+        BLH_TRY(hipStreamSynchronize(s));
         if (cuts) {
             rc = label(b.links, cur, nxt, 2 * n, bound + 1, d_flag, settled, s);
             if (rc != BL_OK) return rc;
@@ -364,68 +334,53 @@ int unitigs(bl_ctx* ctx, const bl_table* table, uint32_t k, bl_batch** out, uint
     }
 
     hipLaunchKernelGGL(place_kernel, dim3(blocks_for(n + 1)), dim3(GTPB), 0, s, cur, n, placed, is_start);
-    G_HIP(hipGetLastError());
+    BLH_TRY(hipGetLastError());
     rc = exclusive_sum(ctx, is_start, number, (size_t)(n + 1), s);
     if (rc != BL_OK) return rc;
     hipLaunchKernelGGL(number_kernel, dim3(blocks_for(n + 1)), dim3(GTPB), 0, s, placed, number, n, k, nodes, lengths, d_counters);
-    G_HIP(hipGetLastError());
+    BLH_TRY(hipGetLastError());
     ull n_unitigs = 0, longest = 0, total = 0;
-    G_HIP(hipMemcpyAsync(&n_unitigs, number + n, sizeof(n_unitigs), hipMemcpyDeviceToHost, s));
-    G_HIP(hipMemcpyAsync(&longest, d_counters + C_LONGEST, sizeof(longest), hipMemcpyDeviceToHost, s));
-    G_HIP(hipStreamSynchronize(s));
+    BLH_TRY(hipMemcpyAsync(&n_unitigs, number + n, sizeof(n_unitigs), hipMemcpyDeviceToHost, s));
+    BLH_TRY(hipMemcpyAsync(&longest, d_counters + C_LONGEST, sizeof(longest), hipMemcpyDeviceToHost, s));
+    BLH_TRY(hipStreamSynchronize(s));
     rc = exclusive_sum(ctx, lengths, offsets, (size_t)(n_unitigs + 1), s);
     if (rc != BL_OK) return rc;
-    G_HIP(hipMemcpyAsync(&total, offsets + n_unitigs, sizeof(total), hipMemcpyDeviceToHost, s));
-    G_HIP(hipStreamSynchronize(s));
+    BLH_TRY(hipMemcpyAsync(&total, offsets + n_unitigs, sizeof(total), hipMemcpyDeviceToHost, s));
+    BLH_TRY(hipStreamSynchronize(s));
     if (stats) {
         stats->n_unitigs = n_unitigs;
         stats->n_cycles = cuts;
         stats->longest_unitig = longest;
     }
-    if (d_out_offsets) G_HIP(hipMemcpyAsync(d_out_offsets, offsets, (size_t)(n_unitigs + 1) * sizeof(uint64_t), hipMemcpyDeviceToDevice, s));
+    if (d_out_offsets) BLH_TRY(hipMemcpyAsync(d_out_offsets, offsets, (size_t)(n_unitigs + 1) * sizeof(uint64_t), hipMemcpyDeviceToDevice, s));
 
-    uint8_t* d_bases = nullptr;
-    uint64_t* d_offs = nullptr;
-    auto fail_free = [&](hipError_t err) {
-        bl_ctx_pool_free(ctx, d_bases);
-        bl_ctx_pool_free(ctx, d_offs);
-        return hip_rc(err);
-    };
-#define U_HIP(call)                                 \
-    do {                                            \
-        hipError_t e_ = (call);                     \
-        if (e_ != hipSuccess) return fail_free(e_); \
-    } while (0)
+    blh::Pooled<uint8_t> d_bases;  // (both stay empty without `out`)
+    blh::Pooled<uint64_t> d_offs;
     if (out) {
-        d_bases = static_cast<uint8_t*>(bl_ctx_pool_alloc(ctx, (size_t)total + 64));
-        d_offs = static_cast<uint64_t*>(bl_ctx_pool_alloc(ctx, (size_t)(n_unitigs + 1) * sizeof(uint64_t)));
-        if (!d_bases || !d_offs) {
-            bl_ctx_pool_free(ctx, d_bases);
-            bl_ctx_pool_free(ctx, d_offs);
-            return bl_set_error(BL_ERR_OOM, "device allocation failed (batch)");
-        }
-        U_HIP(hipMemsetAsync(d_bases + total, 0, 64, s));  // the zero padding every batch has behind its bases
-        U_HIP(hipMemcpyAsync(d_offs, offsets, (size_t)(n_unitigs + 1) * sizeof(uint64_t), hipMemcpyDeviceToDevice, s));
+        d_bases = blh::Pooled<uint8_t>(ctx, (size_t)total + 64);
+        d_offs = blh::Pooled<uint64_t>(ctx, (size_t)(n_unitigs + 1) * sizeof(uint64_t));
+        if (!d_bases || !d_offs) return bl_set_error(BL_ERR_OOM, "device allocation failed (batch)");
+        BLH_TRY(hipMemsetAsync(d_bases.get() + total, 0, 64, s));  // the zero padding every batch has behind its bases
+        BLH_TRY(hipMemcpyAsync(d_offs.get(), offsets, (size_t)(n_unitigs + 1) * sizeof(uint64_t), hipMemcpyDeviceToDevice, s));
     }
-    if (d_count_sums) U_HIP(hipMemsetAsync(d_count_sums, 0, (size_t)n_unitigs * sizeof(uint64_t), s));
+    if (d_count_sums) BLH_TRY(hipMemsetAsync(d_count_sums, 0, (size_t)n_unitigs * sizeof(uint64_t), s));
     if (out || d_count_sums) {
-        hipLaunchKernelGGL(emit_kernel<W>, dim3(blocks_for(n)), dim3(GTPB), 0, s, t, k, nodes, offsets, d_bases, reinterpret_cast<ull*>(d_count_sums));
-        U_HIP(hipGetLastError());
+        hipLaunchKernelGGL(emit_kernel<W>, dim3(blocks_for(n)), dim3(GTPB), 0, s, t, k, nodes, offsets, d_bases.get(), reinterpret_cast<ull*>(d_count_sums));
+        BLH_TRY(hipGetLastError());
     }
     // unitigs of one length make a fixed-length batch (the parser's rule), any other result carries start bits
     uint64_t fixed_len = out && n_unitigs > 1 && total % n_unitigs == 0 ? total / n_unitigs : 0;
     uint32_t ragged = 0;
     if (fixed_len) {
-        U_HIP(hipMemsetAsync(d_flag, 0, sizeof(uint32_t), s));
+        BLH_TRY(hipMemsetAsync(d_flag, 0, sizeof(uint32_t), s));
         hipLaunchKernelGGL(uniform_kernel, dim3(blocks_for(n_unitigs)), dim3(GTPB), 0, s, offsets, (uint64_t)n_unitigs, fixed_len, d_flag);
-        U_HIP(hipGetLastError());
-        U_HIP(hipMemcpyAsync(&ragged, d_flag, sizeof(ragged), hipMemcpyDeviceToHost, s));
+        BLH_TRY(hipGetLastError());
+        BLH_TRY(hipMemcpyAsync(&ragged, d_flag, sizeof(ragged), hipMemcpyDeviceToHost, s));
     }
-    U_HIP(hipStreamSynchronize(s));
-#undef U_HIP
+    BLH_TRY(hipStreamSynchronize(s));
     if (ragged) fixed_len = 0;
     if (out) {
-        rc = bl_batch_adopt_device(ctx, d_bases, total, d_offs, n_unitigs, fixed_len, out);  // takes ownership of both
+        rc = bl_batch_adopt_device(ctx, d_bases.release(), total, d_offs.release(), n_unitigs, fixed_len, out);  // takes ownership of both
         if (rc != BL_OK) return rc;
     }
     if (n_unitigs_out) *n_unitigs_out = n_unitigs;

@@ -1,0 +1,21 @@
+// bl_host.hip — the host helpers of bl_host.hpp that instantiate device code: blh::exclusive_sum, so that rocPRIM's scan of 8-byte words
+// is compiled once for the library and not once per unit that sums tile totals.
+#include <hip/hip_runtime.h>
+
+#include <rocprim/device/device_scan.hpp>
+
+#include "bl_host.hpp"
+
+namespace blh {
+
+int exclusive_sum(bl_ctx* ctx, const uint64_t* in, uint64_t* out, size_t n, hipStream_t s)
+{
+    size_t bytes = 0;
+    BLH_TRY(rocprim::exclusive_scan(nullptr, bytes, in, out, (uint64_t)0, n, rocprim::plus<uint64_t>(), s));
+    void* tmp = bl_ctx_scratch(ctx, 5, bytes ? bytes : 16);
+    if (!tmp) return bl_set_error(BL_ERR_OOM, "scratch allocation failed");
+    BLH_TRY(rocprim::exclusive_scan(tmp, bytes, in, out, (uint64_t)0, n, rocprim::plus<uint64_t>(), s));
+    return BL_OK;
+}
+
+}  // namespace blh

@@ -1,0 +1,99 @@
+// bl_host.hpp — what the translation units of the library share on the HOST side: the functions bl_capi.hip defines for the other units,
+// declared once, and the few helpers every entry point repeats (namespace blh).  Internal; never included from a *_core.hpp (those
+// compile without HIP in tests/emu).
+#pragma once
+#include <hip/hip_runtime_api.h>
+
+#include <cstddef>
+#include <cstdint>
+
+#include "../../include/biolib_amd.h"
+
+// ------------------------------------------------------------------------------------------------ defined in bl_capi.hip
+int bl_set_error(int code, const char* msg);  // the thread's bl_last_error(); returns code
+// The stream every non-scan entry point enqueues on: the borrowed one or lane 0's, made to wait for a scan still running on lane 1.
+hipStream_t bl_ctx_stream(bl_ctx* ctx);
+int bl_ctx_device(bl_ctx* ctx);
+int bl_ctx_count128_tables(bl_ctx* ctx);    // the "count128_tables" option
+int bl_ctx_jaccard128_path(bl_ctx* ctx);    // the "jaccard128_path" option
+int bl_ctx_table_prefix_bits(bl_ctx* ctx);  // the "table_prefix_bits" option
+
+// Grow-only device scratch that lives with the context; NULL on failure.  The caller has synchronised the slot's previous use (the entry
+// points that use it are synchronous).
+//   slot   holds                                       used by
+//   0      candidates                                  bl_correct
+//   0-3    arenas, library workspace, keys, counts,    the k-mer counters (bl_superkmer*.hip; the 128-bit one keeps its run count in 7) and
+//          the text (3)                                the text parser, which call the set operations while they hold them
+//   4      data                                        the set operations, the table build and algebra, the quantiles, select, format,
+//   5      library workspace (rocPRIM):                the corrector, the graph (about 133 bytes per key in slot 4), links and clean:
+//          blh::exclusive_sum takes it                 none of them calls another while it holds 4-6
+//   6      counters, flags, statistics
+void* bl_ctx_scratch(bl_ctx* ctx, int slot, size_t bytes);
+
+// Device memory of short-lived batch buffers, recycled between batches.  bl_ctx_pool_free takes NULL, and hipFree()s what is not the pool's.
+void* bl_ctx_pool_alloc(bl_ctx* ctx, size_t bytes);
+void bl_ctx_pool_free(bl_ctx* ctx, void* p);
+
+// New batches around pool buffers the caller filled on bl_ctx_stream (bases: >= n_bases + 64 bytes, zero padded).  Ownership: both calls
+// take their buffers whatever they return — on success the batch owns them (adopt_device frees the offsets once the start bits are built),
+// on failure they have been freed.  The caller release()s its blh::Pooled holders into the call and never frees afterwards.
+//   adopt_device   DEVICE offsets[n_seqs + 1]; fixed_len != 0: every sequence is that long, the batch is a fixed-length one
+//   adopt_like     the geometry of `like` (n_bases, n_seqs, read length, origin); d_start_bits: a pool copy of like's, or NULL
+int bl_batch_adopt_device(bl_ctx* ctx, void* d_bases, uint64_t n_bases, uint64_t* d_offsets, uint64_t n_seqs, uint64_t fixed_len, bl_batch** out);
+int bl_batch_adopt_like(bl_ctx* ctx, const bl_batch* like, void* d_bases, uint32_t* d_start_bits, bl_batch** out);
+int bl_batch_describe(const bl_batch* batch, bl_ctx** ctx, uint64_t* n_bases, uint64_t* n_seqs, uint64_t* read_len);
+// the start-bit vector the position-tiled scans read (NULL: one sequence).  ensure: build it where a fixed-length batch has not needed it yet
+int bl_batch_scan_view(bl_ctx* ctx, const bl_batch* batch, int ensure, const uint32_t** start_bits);
+// (bl_batch_device_bases is public: include/biolib_amd.h)
+
+// ------------------------------------------------------------------------------------------------ helpers
+namespace blh {
+
+inline int hip_rc(hipError_t e) { return bl_set_error(e == hipErrorOutOfMemory ? BL_ERR_OOM : BL_ERR_HIP, hipGetErrorString(e)); }
+inline int invalid(const char* msg) { return bl_set_error(BL_ERR_INVALID, msg); }
+
+// One bl_ctx_pool_alloc buffer, freed on scope exit unless release()d (into bl_batch_adopt_*, or to a caller that frees it itself).
+template <typename T>
+class Pooled {
+public:
+    Pooled() = default;
+    Pooled(bl_ctx* ctx, size_t bytes) : ctx_(ctx), p_(static_cast<T*>(bl_ctx_pool_alloc(ctx, bytes))) {}
+    Pooled(Pooled&& o) noexcept : ctx_(o.ctx_), p_(o.release()) {}
+    Pooled& operator=(Pooled&& o) noexcept
+    {
+        if (this != &o) {
+            bl_ctx_pool_free(ctx_, p_);
+            ctx_ = o.ctx_;
+            p_ = o.release();
+        }
+        return *this;
+    }
+    Pooled(const Pooled&) = delete;
+    Pooled& operator=(const Pooled&) = delete;
+    ~Pooled() { bl_ctx_pool_free(ctx_, p_); }
+
+    T* get() const { return p_; }
+    explicit operator bool() const { return p_ != nullptr; }
+    T* release()
+    {
+        T* p = p_;
+        p_ = nullptr;
+        return p;
+    }
+
+private:
+    bl_ctx* ctx_ = nullptr;
+    T* p_ = nullptr;
+};
+
+// Exclusive sum of n 8-byte words on `stream` (rocPRIM; its workspace is scratch slot 5, which a second sum on the same stream may take
+// again at once).  Defined in bl_host.hip: the library's one instantiation of that scan.
+int exclusive_sum(bl_ctx* ctx, const uint64_t* in, uint64_t* out, size_t n, hipStream_t stream);
+
+}  // namespace blh
+
+#define BLH_TRY(call)                                 \
+    do {                                              \
+        hipError_t e_ = (call);                       \
+        if (e_ != hipSuccess) return blh::hip_rc(e_); \
+    } while (0)

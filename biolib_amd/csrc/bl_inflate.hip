@@ -10,11 +10,8 @@
 #include <cstring>
 
 #include "../../include/biolib_amd.h"
+#include "bl_host.hpp"
 #include "bl_inflate_core.hpp"
-
-extern int bl_set_error(int code, const char* msg);  // bl_capi.hip
-extern hipStream_t bl_ctx_stream(bl_ctx* ctx);
-extern int bl_ctx_device(bl_ctx* ctx);
 int bl_bgzf_inflate_on(hipStream_t s, const void* d_packed, uint64_t packed_bytes, const bl_bgzf_member* d_members, uint64_t n_members, void* d_text,
                        uint64_t text_bytes, uint32_t* d_status);
 

@@ -51,11 +51,9 @@
 
 #include "../../include/biolib_amd.h"
 #include "bl_crc32.hpp"
+#include "bl_host.hpp"
 #include "bl_pgzip.hpp"
 
-extern int bl_set_error(int code, const char* msg);  // bl_capi.hip
-extern hipStream_t bl_ctx_stream(bl_ctx* ctx);
-extern int bl_ctx_device(bl_ctx* ctx);
 extern int bl_bgzf_inflate_on(hipStream_t s, const void* d_packed, uint64_t packed_bytes, const bl_bgzf_member* d_members, uint64_t n_members, void* d_text,
                               uint64_t text_bytes, uint32_t* d_status);  // bl_inflate.hip
 extern int bl_parse_device_text(bl_ctx* ctx, const uint8_t* d_text, uint64_t n_bytes, char first_byte, const char* ends, uint64_t ends_n, bl_batch** out,
@@ -1975,23 +1973,17 @@ int bl_reader_next_text(bl_reader* r, uint64_t max_bytes, const char** text, uin
 
 namespace {
 
-#define R_HIP(call)                                                                                        \
-    do {                                                                                                   \
-        const hipError_t e_ = (call);                                                                      \
-        if (e_ != hipSuccess) return bl_set_error(e_ == hipErrorOutOfMemory ? BL_ERR_OOM : BL_ERR_HIP, hipGetErrorString(e_)); \
-    } while (0)
-
 // page-locked host memory of at least `need` bytes (contents not kept)
 int pinned_reserve_raw(void** p, size_t* cap, size_t need)
 {
     if (need <= *cap) return BL_OK;
     size_t want = *cap ? *cap : 4096;
     while (want < need) want *= 2;
-    if (*p) R_HIP(hipHostFree(*p));
+    if (*p) BLH_TRY(hipHostFree(*p));
     *p = nullptr;
     *cap = 0;
     void* q = nullptr;
-    R_HIP(hipHostMalloc(&q, want, hipHostMallocPortable));
+    BLH_TRY(hipHostMalloc(&q, want, hipHostMallocPortable));
     *p = q;
     *cap = want;
     return BL_OK;
@@ -2005,13 +1997,13 @@ int device_reserve(void** p, size_t* cap, size_t need, size_t keep, hipStream_t 
     size_t want = *cap ? *cap : (size_t)1 << 20;
     while (want < need) want *= 2;
     void* q = nullptr;
-    R_HIP(hipMalloc(&q, want));
+    BLH_TRY(hipMalloc(&q, want));
     if (keep) {
         const hipError_t e = hipMemcpyAsync(q, *p, keep, hipMemcpyDeviceToDevice, s);
         if (e != hipSuccess) { (void)hipFree(q); return bl_set_error(BL_ERR_HIP, hipGetErrorString(e)); }
     }
-    R_HIP(hipStreamSynchronize(s));  // nothing queued may still use the old buffer
-    if (*p) R_HIP(hipFree(*p));
+    BLH_TRY(hipStreamSynchronize(s));  // nothing queued may still use the old buffer
+    if (*p) BLH_TRY(hipFree(*p));
     *p = q;
     *cap = want;
     return BL_OK;
@@ -2041,16 +2033,16 @@ int launch_packed(DeviceBgzf& d, int buf, size_t offset)
         if (rc == BL_OK) rc = device_reserve(&d.d_members, &d.members_cap, n_members * (sizeof(bl_bgzf_member) + sizeof(uint32_t)), 0, s);
         if (rc != BL_OK) return rc;
         d.d_status = reinterpret_cast<uint32_t*>(static_cast<char*>(d.d_members) + n_members * sizeof(bl_bgzf_member));
-        R_HIP(hipMemcpyAsync(d.d_packed, sp->p, sp->n, hipMemcpyHostToDevice, s));
+        BLH_TRY(hipMemcpyAsync(d.d_packed, sp->p, sp->n, hipMemcpyHostToDevice, s));
         rc = pinned_reserve(&d.members_up, &d.members_up_cap, n_members * sizeof(bl_bgzf_member));
         if (rc != BL_OK) return rc;
         std::memcpy(d.members_up, sp->members.data(), n_members * sizeof(bl_bgzf_member));  // (the previous table's copy was waited for)
-        R_HIP(hipMemcpyAsync(d.d_members, d.members_up, n_members * sizeof(bl_bgzf_member), hipMemcpyHostToDevice, s));
+        BLH_TRY(hipMemcpyAsync(d.d_members, d.members_up, n_members * sizeof(bl_bgzf_member), hipMemcpyHostToDevice, s));
         rc = bl_bgzf_inflate_on(s, d.d_packed, sp->n, static_cast<const bl_bgzf_member*>(d.d_members), n_members, d.d_text[buf] + offset, add, d.d_status);
         if (rc != BL_OK) return rc;
         rc = pinned_reserve(&d.status, &d.status_cap, n_members * sizeof(uint32_t));
         if (rc != BL_OK) return rc;
-        R_HIP(hipMemcpyAsync(d.status, d.d_status, n_members * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+        BLH_TRY(hipMemcpyAsync(d.status, d.d_status, n_members * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
     }
     d.pending.active = true;
     d.pending.n_members = n_members;
@@ -2067,8 +2059,8 @@ int next_batch_packed(bl_ctx* ctx, bl_reader* r, bl_batch** out, bl_text_index**
 {
     DeviceBgzf& d = *r->packed;
     if (d.ctx != ctx) return bl_set_error(BL_ERR_INVALID, "a reader's device batches must all go to the same context");
-    R_HIP(hipSetDevice(bl_ctx_device(ctx)));
-    if (!d.stream) R_HIP(hipStreamCreateWithFlags(&d.stream, hipStreamNonBlocking));
+    BLH_TRY(hipSetDevice(bl_ctx_device(ctx)));
+    if (!d.stream) BLH_TRY(hipStreamCreateWithFlags(&d.stream, hipStreamNonBlocking));
     hipStream_t s = d.stream;
     auto now = [] { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
     for (;;) {
@@ -2084,7 +2076,7 @@ int next_batch_packed(bl_ctx* ctx, bl_reader* r, bl_batch** out, bl_text_index**
         uint8_t* const text = d.d_text[d.pending.buf];
         d.cur = d.pending.buf;
         if (filled == 0) {
-            R_HIP(hipStreamSynchronize(s));  // (members without text: the end-of-file marker)
+            BLH_TRY(hipStreamSynchronize(s));  // (members without text: the end-of-file marker)
             for (size_t i = 0; i < n_members; ++i)
                 if (d.status[i] != 0) return bl_set_error(BL_ERR_INVALID, "error reading the (compressed) stream");
             if (d.eof) return BL_OK;  // end of file
@@ -2097,10 +2089,10 @@ int next_batch_packed(bl_ctx* ctx, bl_reader* r, bl_batch** out, bl_text_index**
                 rc = pinned_reserve(&d.first_back, &one, 64);
             }
             if (rc != BL_OK) return rc;
-            R_HIP(hipMemcpyAsync(d.window, text + from, n, hipMemcpyDeviceToHost, s));
-            if (!d.first_byte) R_HIP(hipMemcpyAsync(d.first_back, text, 1, hipMemcpyDeviceToHost, s));
+            BLH_TRY(hipMemcpyAsync(d.window, text + from, n, hipMemcpyDeviceToHost, s));
+            if (!d.first_byte) BLH_TRY(hipMemcpyAsync(d.first_back, text, 1, hipMemcpyDeviceToHost, s));
             const double t0 = now();
-            R_HIP(hipStreamSynchronize(s));
+            BLH_TRY(hipStreamSynchronize(s));
             d.t_wait += now() - t0;
             if (!d.first_byte) d.first_byte = d.first_back[0];
             for (size_t i = 0; i < n_members; ++i)
@@ -2133,8 +2125,8 @@ int next_batch_packed(bl_ctx* ctx, bl_reader* r, bl_batch** out, bl_text_index**
             const int rc = device_reserve(&p, &d.text_cap[other], rest + 64, 0, s);
             d.d_text[other] = static_cast<uint8_t*>(p);
             if (rc != BL_OK) return rc;
-            if (rest) R_HIP(hipMemcpyAsync(d.d_text[other], text + at, rest, hipMemcpyDeviceToDevice, s));
-            R_HIP(hipStreamSynchronize(s));
+            if (rest) BLH_TRY(hipMemcpyAsync(d.d_text[other], text + at, rest, hipMemcpyDeviceToDevice, s));
+            BLH_TRY(hipStreamSynchronize(s));
             d.cur = other;
             d.carry_n = rest;
             if (d.ext_start != (size_t)-1) d.ext_start = d.ext_start > at ? d.ext_start - at : 0;
@@ -2185,7 +2177,7 @@ int next_batch_packed(bl_ctx* ctx, bl_reader* r, bl_batch** out, bl_text_index**
             const int rc = device_reserve(&p, &d.text_cap[other], rest + 64, 0, s);
             d.d_text[other] = static_cast<uint8_t*>(p);
             if (rc != BL_OK) return rc;
-            R_HIP(hipMemcpyAsync(d.d_text[other], text + cut, rest, hipMemcpyDeviceToDevice, s));
+            BLH_TRY(hipMemcpyAsync(d.d_text[other], text + cut, rest, hipMemcpyDeviceToDevice, s));
         }
         d.cur = other;
         d.carry_n = rest;

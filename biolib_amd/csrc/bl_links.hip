@@ -12,18 +12,11 @@
 // No atomic decides a placement: a rerun is bit-identical.
 #include <hip/hip_runtime.h>
 
-#include <rocprim/device/device_scan.hpp>
-
 #include "../../include/biolib_amd.h"
 #include "bl_gfa_core.hpp"
+#include "bl_host.hpp"
 #include "bl_links_core.hpp"
 #include "bl_lookup_launch.hpp"
-
-extern int bl_set_error(int code, const char* msg);  // bl_capi.hip
-extern hipStream_t bl_ctx_stream(bl_ctx* ctx);
-extern int bl_ctx_device(bl_ctx* ctx);
-extern void* bl_ctx_scratch(bl_ctx* ctx, int slot, size_t bytes);  // as the graph: 4 data, 5 library workspace, 6 counters
-extern int bl_batch_describe(const bl_batch* batch, bl_ctx** ctx, uint64_t* n_bases, uint64_t* n_seqs, uint64_t* read_len);
 
 static_assert(sizeof(bl_unitig_link) == sizeof(bllnk::Link) && sizeof(bl_unitig_link) == sizeof(blgfa::LinkWords) && sizeof(bl_unitig_node) == sizeof(bllnk::Node),
               "the device words are the caller's");
@@ -81,28 +74,11 @@ __global__ __launch_bounds__(LTPB) void link_emit_kernel(const uint64_t* __restr
 
 namespace {
 
-int hip_rc(hipError_t e) { return bl_set_error(e == hipErrorOutOfMemory ? BL_ERR_OOM : BL_ERR_HIP, hipGetErrorString(e)); }
-int invalid(const char* msg) { return bl_set_error(BL_ERR_INVALID, msg); }
+using blh::exclusive_sum;
+using blh::invalid;
 unsigned blocks_for(uint64_t threads) { return (unsigned)((threads + LTPB - 1) / LTPB); }
 
-int exclusive_sum(bl_ctx* ctx, const uint64_t* in, uint64_t* out, size_t n, hipStream_t s)
-{
-    size_t bytes = 0;
-    hipError_t e = rocprim::exclusive_scan(nullptr, bytes, in, out, (uint64_t)0, n, rocprim::plus<uint64_t>(), s);
-    if (e != hipSuccess) return hip_rc(e);
-    void* tmp = bl_ctx_scratch(ctx, 5, bytes ? bytes : 16);
-    if (!tmp) return bl_set_error(BL_ERR_OOM, "scratch allocation failed");
-    e = rocprim::exclusive_scan(tmp, bytes, in, out, (uint64_t)0, n, rocprim::plus<uint64_t>(), s);
-    return e == hipSuccess ? BL_OK : hip_rc(e);
-}
-
 size_t aligned(size_t bytes) { return (bytes + 255) & ~(size_t)255; }
-
-#define L_HIP(call)                              \
-    do {                                         \
-        hipError_t e_ = (call);                  \
-        if (e_ != hipSuccess) return hip_rc(e_); \
-    } while (0)
 
 }  // namespace
 
@@ -134,11 +110,11 @@ extern "C" int bl_unitig_links(bl_ctx* ctx, const bl_table* table, uint32_t k, c
     if (stats) *stats = bl_link_stats{};
     const uint64_t n_ends = 2 * n_unitigs;
     if (stats) stats->n_ends = n_ends;
-    L_HIP(hipSetDevice(bl_ctx_device(ctx)));
+    BLH_TRY(hipSetDevice(bl_ctx_device(ctx)));
     hipStream_t s = bl_ctx_stream(ctx);
     if (n_ends == 0) {
-        if (d_link_offsets) L_HIP(hipMemsetAsync(d_link_offsets, 0, sizeof(uint64_t), s));
-        L_HIP(hipStreamSynchronize(s));
+        if (d_link_offsets) BLH_TRY(hipMemsetAsync(d_link_offsets, 0, sizeof(uint64_t), s));
+        BLH_TRY(hipStreamSynchronize(s));
         return BL_OK;
     }
     // slot 4: the end keys, the degrees, their sums and the parked words: 36 bytes per end
@@ -152,22 +128,22 @@ extern "C" int bl_unitig_links(bl_ctx* ctx, const bl_table* table, uint32_t k, c
     Parked* parked = reinterpret_cast<Parked*>(arena + b_keys + 2 * b_sum);
     const Node* nodes = reinterpret_cast<const Node*>(d_nodes);
 
-    L_HIP(hipMemsetAsync(end_key, 0xFF, n_ends * sizeof(uint32_t), s));
-    L_HIP(hipMemsetAsync(d_counters, 0, 4 * sizeof(ull), s));
+    BLH_TRY(hipMemsetAsync(end_key, 0xFF, n_ends * sizeof(uint32_t), s));
+    BLH_TRY(hipMemsetAsync(d_counters, 0, 4 * sizeof(ull), s));
     hipLaunchKernelGGL(end_key_kernel, dim3(blocks_for(n)), dim3(LTPB), 0, s, nodes, d_unitig_offsets, n_unitigs, k, n, end_key);
-    L_HIP(hipGetLastError());
+    BLH_TRY(hipGetLastError());
     if (t.key_words == 2)
         hipLaunchKernelGGL(end_search_kernel<2>, dim3(blocks_for(n_ends + 1)), dim3(LTPB), 0, s, t, k, nodes, n_unitigs, end_key, flags, degree, parked, d_counters);
     else
         hipLaunchKernelGGL(end_search_kernel<1>, dim3(blocks_for(n_ends + 1)), dim3(LTPB), 0, s, t, k, nodes, n_unitigs, end_key, flags, degree, parked, d_counters);
-    L_HIP(hipGetLastError());
+    BLH_TRY(hipGetLastError());
     int rc = exclusive_sum(ctx, degree, offsets, (size_t)(n_ends + 1), s);
     if (rc != BL_OK) return rc;
     ull total = 0, host[4] = {};
-    L_HIP(hipMemcpyAsync(&total, offsets + n_ends, sizeof(total), hipMemcpyDeviceToHost, s));
-    L_HIP(hipMemcpyAsync(host, d_counters, sizeof(host), hipMemcpyDeviceToHost, s));
-    if (d_link_offsets) L_HIP(hipMemcpyAsync(d_link_offsets, offsets, (size_t)(n_ends + 1) * sizeof(uint64_t), hipMemcpyDeviceToDevice, s));
-    L_HIP(hipStreamSynchronize(s));
+    BLH_TRY(hipMemcpyAsync(&total, offsets + n_ends, sizeof(total), hipMemcpyDeviceToHost, s));
+    BLH_TRY(hipMemcpyAsync(host, d_counters, sizeof(host), hipMemcpyDeviceToHost, s));
+    if (d_link_offsets) BLH_TRY(hipMemcpyAsync(d_link_offsets, offsets, (size_t)(n_ends + 1) * sizeof(uint64_t), hipMemcpyDeviceToDevice, s));
+    BLH_TRY(hipStreamSynchronize(s));
     if (n_links) *n_links = total;
     if (stats) {
         stats->n_links = total;
@@ -179,8 +155,8 @@ extern "C" int bl_unitig_links(bl_ctx* ctx, const bl_table* table, uint32_t k, c
     if (capacity < total) return bl_set_error(BL_ERR_CAPACITY, "bl_unitig_links: d_links is smaller than the records (*n_links says how many there are)");
     if (total == 0) return BL_OK;
     hipLaunchKernelGGL(link_emit_kernel, dim3(blocks_for(n_ends)), dim3(LTPB), 0, s, offsets, parked, n_ends, (uint64_t)total, reinterpret_cast<Link*>(d_links));
-    L_HIP(hipGetLastError());
-    L_HIP(hipStreamSynchronize(s));
+    BLH_TRY(hipGetLastError());
+    BLH_TRY(hipStreamSynchronize(s));
     return BL_OK;
 }
 
@@ -255,8 +231,8 @@ __global__ __launch_bounds__(TPB) void gfa_kernel(const GfaParams p)
 
 namespace {
 
-int hip_rc(hipError_t e) { return bl_set_error(e == hipErrorOutOfMemory ? BL_ERR_OOM : BL_ERR_HIP, hipGetErrorString(e)); }
-int invalid(const char* msg) { return bl_set_error(BL_ERR_INVALID, msg); }
+using blh::hip_rc;
+using blh::invalid;
 unsigned blocks_for(uint64_t threads) { return (unsigned)((threads + TPB - 1) / TPB); }
 
 // a NUL inside the 16 bytes: the length; none: -1
@@ -322,14 +298,10 @@ extern "C" int bl_unitigs_format_gfa(bl_ctx* ctx, const bl_batch* unitigs, const
     hipLaunchKernelGGL(line_length_kernel, dim3(blocks_for(n1)), dim3(TPB), 0, s, p);
     e = hipGetLastError();
     if (e != hipSuccess) return hip_rc(e);
-    size_t bytes = 0;
-    e = rocprim::exclusive_scan(nullptr, bytes, p.line_len, line_off, (uint64_t)0, (size_t)n1, rocprim::plus<uint64_t>(), s);
-    if (e != hipSuccess) return hip_rc(e);
-    void* tmp = bl_ctx_scratch(ctx, 5, bytes ? bytes : 16);
-    if (!tmp) return bl_set_error(BL_ERR_OOM, "scratch allocation failed");
-    e = rocprim::exclusive_scan(tmp, bytes, p.line_len, line_off, (uint64_t)0, (size_t)n1, rocprim::plus<uint64_t>(), s);
+    const int rc = blh::exclusive_sum(ctx, p.line_len, line_off, (size_t)n1, s);
+    if (rc != BL_OK) return rc;
     unsigned long long total = 0;
-    if (e == hipSuccess) e = hipMemcpyAsync(&total, line_off + p.n_lines, sizeof(total), hipMemcpyDeviceToHost, s);
+    e = hipMemcpyAsync(&total, line_off + p.n_lines, sizeof(total), hipMemcpyDeviceToHost, s);
     if (e == hipSuccess) e = hipStreamSynchronize(s);
     if (e != hipSuccess) return hip_rc(e);
     if (n_bytes) *n_bytes = total;

@@ -14,14 +14,9 @@
 #include <new>
 
 #include "../../include/biolib_amd.h"
+#include "bl_host.hpp"
 #include "bl_lookup_launch.hpp"
 #include "bl_tile128.hpp"
-
-extern int bl_set_error(int code, const char* msg);  // bl_capi.hip
-extern hipStream_t bl_ctx_stream(bl_ctx* ctx);
-extern int bl_ctx_device(bl_ctx* ctx);
-extern void* bl_ctx_scratch(bl_ctx* ctx, int slot, size_t bytes);  // slots 4-6 are the set operations': 4 data, 5 library workspace, 6 counters
-extern int bl_ctx_table_prefix_bits(bl_ctx* ctx);                  // the "table_prefix_bits" option
 
 namespace bllk {
 
@@ -120,6 +115,32 @@ void free_table(bl_table* t)
     delete t;
 }
 
+int new_table(bl_ctx* ctx, uint32_t key_words, uint32_t key_bits, uint64_t n, bl_table** out)
+{
+    *out = nullptr;
+    bl_table* t = new (std::nothrow) bl_table{};
+    if (!t) return bl_set_error(BL_ERR_OOM, "out of host memory");
+    t->ctx = ctx;
+    t->device = bl_ctx_device(ctx);
+    t->view.key_words = key_words;
+    t->view.key_bits = key_bits;
+    t->view.n = (uint32_t)n;
+    if (n) {
+        void* keys = nullptr;
+        void* counts = nullptr;
+        hipError_t e = hipMalloc(&keys, (size_t)n * key_words * sizeof(uint64_t));
+        t->view.keys = static_cast<uint64_t*>(keys);
+        if (e == hipSuccess) e = hipMalloc(&counts, (size_t)n * sizeof(uint32_t));
+        t->view.counts = static_cast<uint32_t*>(counts);
+        if (e != hipSuccess) {
+            free_table(t);
+            return blh::hip_rc(e);
+        }
+    }
+    *out = t;
+    return BL_OK;
+}
+
 hipError_t finish_table(bl_ctx* ctx, bl_table* t, hipStream_t s)
 {
     t->view.prefix_bits = choose_prefix_bits(bl_ctx_table_prefix_bits(ctx), t->view.n, t->view.key_bits);
@@ -145,7 +166,7 @@ struct SatAdd {
     }
 };
 
-int hip_rc(hipError_t e) { return bl_set_error(e == hipErrorOutOfMemory ? BL_ERR_OOM : BL_ERR_HIP, hipGetErrorString(e)); }
+using blh::hip_rc;
 bool misaligned(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) != 0; }
 size_t round16(size_t b) { return (b + 15) & ~(size_t)15; }
 unsigned blocks_for(ull n) { return (unsigned)((n + LTPB - 1) / LTPB < TABLE_GRID_MAX ? (n + LTPB - 1) / LTPB : TABLE_GRID_MAX); }
@@ -163,17 +184,12 @@ int build(bl_ctx* ctx, const uint64_t* d_keys, const uint32_t* d_counts, uint64_
     if (e != hipSuccess) return hip_rc(e);
     hipStream_t s = bl_ctx_stream(ctx);
 
-    bl_table* t = new (std::nothrow) bl_table{};
-    if (!t) return bl_set_error(BL_ERR_OOM, "out of host memory");
-    t->ctx = ctx;
-    t->device = bl_ctx_device(ctx);
-    t->view.key_words = W;
-    t->view.key_bits = key_bits;
-
     ull distinct = 0;
+    KeyT* merged = nullptr;  // slot 4: the distinct keys and their counts
+    uint32_t* merged_c = nullptr;
     if (n) {
         ull* d_words = static_cast<ull*>(bl_ctx_scratch(ctx, 6, 64));  // [0] OR of low words, [1] OR of high words, [2] distinct keys
-        if (!d_words) { free_table(t); return bl_set_error(BL_ERR_OOM, "scratch allocation failed"); }
+        if (!d_words) return bl_set_error(BL_ERR_OOM, "scratch allocation failed");
         // the key_bits promise, before the sort that relies on it
         ull host[3] = {0, 0, 0};
         e = hipMemsetAsync(d_words, 0, 3 * sizeof(ull), s);
@@ -183,17 +199,17 @@ int build(bl_ctx* ctx, const uint64_t* d_keys, const uint32_t* d_counts, uint64_
         }
         if (e == hipSuccess) e = hipMemcpyAsync(host, d_words, 2 * sizeof(ull), hipMemcpyDeviceToHost, s);
         if (e == hipSuccess) e = hipStreamSynchronize(s);
-        if (e != hipSuccess) { free_table(t); return hip_rc(e); }
-        if (above_key_bits(host[0], host[1], key_bits)) { free_table(t); return bl_set_error(BL_ERR_INVALID, "a key has a bit set at or above key_bits"); }
+        if (e != hipSuccess) return hip_rc(e);
+        if (above_key_bits(host[0], host[1], key_bits)) return bl_set_error(BL_ERR_INVALID, "a key has a bit set at or above key_bits");
 
         // slot 4: sorted keys | merged keys | sorted counts | merged counts
         const size_t kb = round16((size_t)n * sizeof(KeyT)), cb = round16((size_t)n * sizeof(uint32_t));
         unsigned char* data = static_cast<unsigned char*>(bl_ctx_scratch(ctx, 4, 2 * kb + 2 * cb));
-        if (!data) { free_table(t); return bl_set_error(BL_ERR_OOM, "scratch allocation failed"); }
+        if (!data) return bl_set_error(BL_ERR_OOM, "scratch allocation failed");
         KeyT* sorted = reinterpret_cast<KeyT*>(data);
-        KeyT* merged = reinterpret_cast<KeyT*>(data + kb);
+        merged = reinterpret_cast<KeyT*>(data + kb);
         uint32_t* sorted_c = reinterpret_cast<uint32_t*>(data + 2 * kb);
-        uint32_t* merged_c = reinterpret_cast<uint32_t*>(data + 2 * kb + cb);
+        merged_c = reinterpret_cast<uint32_t*>(data + 2 * kb + cb);
         const KeyT* in = reinterpret_cast<const KeyT*>(d_keys);
         const rocprim::constant_iterator<uint32_t> ones(1u);
         size_t sort_bytes = 0, reduce_bytes = 0;
@@ -213,23 +229,17 @@ int build(bl_ctx* ctx, const uint64_t* d_keys, const uint32_t* d_counts, uint64_
         if (e == hipSuccess) e = rocprim::reduce_by_key(ws, reduce_bytes, sorted, sorted_c, (size_t)n, merged, merged_c, d_words + 2, SatAdd(), rocprim::equal_to<KeyT>(), s);
         if (e == hipSuccess) e = hipMemcpyAsync(&distinct, d_words + 2, sizeof(ull), hipMemcpyDeviceToHost, s);
         if (e == hipSuccess) e = hipStreamSynchronize(s);
-        if (e != hipSuccess) { free_table(t); return hip_rc(e); }
-        if (distinct == 0 || distinct > n) { free_table(t); return bl_set_error(BL_ERR_INTERNAL, "reduce_by_key returned an impossible number of keys"); }
-        void* keys = nullptr;
-        void* counts = nullptr;
-        e = hipMalloc(&keys, (size_t)distinct * sizeof(KeyT));
-        if (e == hipSuccess) {
-            t->view.keys = static_cast<uint64_t*>(keys);
-            e = hipMalloc(&counts, (size_t)distinct * sizeof(uint32_t));
-        }
-        if (e == hipSuccess) {
-            t->view.counts = static_cast<uint32_t*>(counts);
-            e = hipMemcpyAsync(keys, merged, (size_t)distinct * sizeof(KeyT), hipMemcpyDeviceToDevice, s);
-        }
-        if (e == hipSuccess) e = hipMemcpyAsync(counts, merged_c, (size_t)distinct * sizeof(uint32_t), hipMemcpyDeviceToDevice, s);
+        if (e != hipSuccess) return hip_rc(e);
+        if (distinct == 0 || distinct > n) return bl_set_error(BL_ERR_INTERNAL, "reduce_by_key returned an impossible number of keys");
+    }
+    bl_table* t = nullptr;
+    const int rc = new_table(ctx, W, key_bits, distinct, &t);
+    if (rc != BL_OK) return rc;
+    if (distinct) {
+        e = hipMemcpyAsync(const_cast<uint64_t*>(t->view.keys), merged, (size_t)distinct * sizeof(KeyT), hipMemcpyDeviceToDevice, s);
+        if (e == hipSuccess) e = hipMemcpyAsync(const_cast<uint32_t*>(t->view.counts), merged_c, (size_t)distinct * sizeof(uint32_t), hipMemcpyDeviceToDevice, s);
         if (e != hipSuccess) { free_table(t); return hip_rc(e); }
     }
-    t->view.n = (uint32_t)distinct;
     e = finish_table(ctx, t, s);
     if (e != hipSuccess) { free_table(t); return hip_rc(e); }
     *out = t;

@@ -26,8 +26,7 @@
 #include <vector>
 
 #include "../../include/biolib_amd.h"
-
-extern int bl_set_error(int code, const char* msg);  // bl_capi.hip
+#include "bl_host.hpp"
 
 #ifndef BL_HAVE_RCCL_HEADER
 extern "C" int bl_count_allreduce(bl_ctx* const*, int, uint64_t*, int)
@@ -35,9 +34,6 @@ extern "C" int bl_count_allreduce(bl_ctx* const*, int, uint64_t*, int)
     return bl_set_error(BL_ERR_HIP, "bl_count_allreduce: this library was built without <rccl/rccl.h> (RCCL development header absent at build time)");
 }
 #else
-struct bl_ctx;
-hipStream_t bl_ctx_stream(bl_ctx* ctx);
-int bl_ctx_device(bl_ctx* ctx);
 
 namespace {
 

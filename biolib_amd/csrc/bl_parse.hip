@@ -20,16 +20,8 @@
 #include <string>
 
 #include "../../include/biolib_amd.h"
+#include "bl_host.hpp"
 #include "bl_parse_core.hpp"
-
-extern int bl_set_error(int code, const char* msg);
-extern hipStream_t bl_ctx_stream(bl_ctx* ctx);
-extern int bl_ctx_device(bl_ctx* ctx);
-extern void* bl_ctx_scratch(bl_ctx* ctx, int slot, size_t bytes);  // bl_capi.hip: grow-only device scratch that lives with the context
-extern void* bl_ctx_pool_alloc(bl_ctx* ctx, size_t bytes);          // bl_capi.hip: batch buffers, recycled between batches
-extern void bl_ctx_pool_free(bl_ctx* ctx, void* p);
-extern int bl_batch_adopt_device(bl_ctx* ctx, void* d_bases, uint64_t n_bases, uint64_t* d_offsets, uint64_t n_seqs, uint64_t fixed_len,
-                                 bl_batch** out);  // bl_capi.hip
 
 namespace {
 
@@ -113,11 +105,17 @@ __global__ void gather_bases_kernel(const uint8_t* text, const unsigned long lon
     if (x0 < total) gather16(text, line_end, dst, seq_len, n_lines, bases, total, x0);
 }
 
-#define P_HIP(call)                                                                                                       \
-    do {                                                                                                                  \
-        hipError_t e_ = (call);                                                                                           \
-        if (e_ != hipSuccess) { cleanup(); return bl_set_error(e_ == hipErrorOutOfMemory ? BL_ERR_OOM : BL_ERR_HIP, hipGetErrorString(e_)); } \
-    } while (0)
+// Waits for the stream on the way out of the parser, once: nothing may still be running on the scratch, or on the outputs when they go.
+struct Drain {
+    hipStream_t s;
+    bool armed = true;
+    void now()
+    {
+        if (armed) (void)hipStreamSynchronize(s);
+        armed = false;
+    }
+    ~Drain() { now(); }
+};
 
 }  // namespace
 
@@ -178,65 +176,56 @@ int bl_parse_device_text_lines(bl_ctx* ctx, const uint8_t* d_text_in, uint64_t n
     // workspace; slot 3 holds the text when it came from the host): a file is parsed span after span, and a dozen hipMalloc /
     // hipFree per span cost more than the kernels.  Only the two arrays the batch keeps are allocated here.
     const uint8_t* d_text = nullptr;
-    unsigned long long *d_blk = nullptr, *d_line_end = nullptr, *d_len = nullptr, *d_hdr = nullptr, *d_rec = nullptr, *d_dst = nullptr, *d_offsets = nullptr;
+    unsigned long long *d_blk = nullptr, *d_line_end = nullptr, *d_len = nullptr, *d_hdr = nullptr, *d_rec = nullptr, *d_dst = nullptr;
     unsigned int* d_err = nullptr;
     void* d_tmp = nullptr;
-    uint8_t* d_bases = nullptr;
-    bool handed_over = false;  // d_bases / d_offsets now belong to the batch
-    auto cleanup = [&]() {     // every exit path: nothing may still be running on the scratch; the outputs go unless adopted
-        (void)hipStreamSynchronize(s);
-        if (!handed_over) {
-            bl_ctx_pool_free(ctx, d_bases);
-            bl_ctx_pool_free(ctx, d_offsets);
-            d_bases = nullptr;
-            d_offsets = nullptr;
-        }
-    };
-    auto fail_free = [&](int code, const char* msg) {
-        cleanup();
-        return bl_set_error(code, msg);
-    };
+    blh::Pooled<uint8_t> d_bases;  // the outputs go on every exit path unless adopted ...
+    blh::Pooled<unsigned long long> d_offsets;
+    Drain drain{s};  // ... behind the wait for the stream (declared last: it goes first)
     auto up256 = [](size_t x) { return (x + 255) & ~(size_t)255; };
 
-    P_HIP(hipSetDevice(bl_ctx_device(ctx)));
+    BLH_TRY(hipSetDevice(bl_ctx_device(ctx)));
     const uint64_t n = n_bytes;
     const unsigned n_blocks = (unsigned)((n + BYTES_PER_BLOCK - 1) / BYTES_PER_BLOCK);
     const size_t blk_bytes = up256(2 * ((size_t)n_blocks + 1) * sizeof(unsigned long long));
     unsigned char* a0 = static_cast<unsigned char*>(bl_ctx_scratch(ctx, 0, blk_bytes + 256));
-    if (!a0) return fail_free(BL_ERR_OOM, "device allocation failed (block scratch)");
+    if (!a0) return bl_set_error(BL_ERR_OOM, "device allocation failed (block scratch)");
     d_text = d_text_in;
     d_blk = reinterpret_cast<unsigned long long*>(a0);  // counts, then their exclusive prefix
     d_err = reinterpret_cast<unsigned int*>(a0 + blk_bytes);
     unsigned long long* d_blk_base = d_blk + n_blocks + 1;
-    P_HIP(hipMemsetAsync(d_blk + n_blocks, 0, sizeof(unsigned long long), s));
-    P_HIP(hipMemsetAsync(d_err, 0, sizeof(unsigned int), s));
+    BLH_TRY(hipMemsetAsync(d_blk + n_blocks, 0, sizeof(unsigned long long), s));
+    BLH_TRY(hipMemsetAsync(d_err, 0, sizeof(unsigned int), s));
     hipLaunchKernelGGL(count_newlines_kernel, dim3(n_blocks), dim3(PB), 0, s, d_text, n, d_blk);
 
     // scans: one scratch buffer sized for the largest of them (n_lines <= n)
     size_t tmp_bytes = 0, need = 0;
-    P_HIP(rocprim::exclusive_scan(nullptr, need, d_blk, d_blk_base, 0ull, (size_t)n_blocks + 1, rocprim::plus<unsigned long long>(), s));
+    BLH_TRY(rocprim::exclusive_scan(nullptr, need, d_blk, d_blk_base, 0ull, (size_t)n_blocks + 1, rocprim::plus<unsigned long long>(), s));
     tmp_bytes = need;
     // the other two scans run over n_lines <= n_blocks * BYTES_PER_BLOCK items; their workspace is asked for again below
     d_tmp = bl_ctx_scratch(ctx, 2, tmp_bytes ? tmp_bytes : 16);
-    if (!d_tmp) return fail_free(BL_ERR_OOM, "device allocation failed (scan scratch)");
-    P_HIP(rocprim::exclusive_scan(d_tmp, tmp_bytes, d_blk, d_blk_base, 0ull, (size_t)n_blocks + 1, rocprim::plus<unsigned long long>(), s));
+    if (!d_tmp) return bl_set_error(BL_ERR_OOM, "device allocation failed (scan scratch)");
+    BLH_TRY(rocprim::exclusive_scan(d_tmp, tmp_bytes, d_blk, d_blk_base, 0ull, (size_t)n_blocks + 1, rocprim::plus<unsigned long long>(), s));
     unsigned long long n_newlines = 0;
-    P_HIP(hipMemcpyAsync(&n_newlines, d_blk_base + n_blocks, sizeof(n_newlines), hipMemcpyDeviceToHost, s));
-    P_HIP(hipStreamSynchronize(s));
+    BLH_TRY(hipMemcpyAsync(&n_newlines, d_blk_base + n_blocks, sizeof(n_newlines), hipMemcpyDeviceToHost, s));
+    BLH_TRY(hipStreamSynchronize(s));
     const uint64_t n_lines_raw = n_newlines + (open_last_line ? 1 : 0);
     uint64_t n_lines = n_lines_raw;
     if (fastq && (n_lines & 3)) {  // blank lines after the last record are tolerated, anything else is not 4-line FASTQ
         const uint64_t excess = n_lines & 3;
         if (!trailing_lines_blank(ends, ends_n, n_bytes, open_last_line, excess))
-            return fail_free(BL_ERR_INVALID, "FASTQ text is not made of 4-line records: use bl_reader_*");
+            return bl_set_error(BL_ERR_INVALID, "FASTQ text is not made of 4-line records: use bl_reader_*");
         n_lines -= excess;
-        if (n_lines == 0) return bl_batch_upload(ctx, "", 0, nullptr, 0, out);  // a span of the blank lines behind a file's last record
+        if (n_lines == 0) {  // a span of the blank lines behind a file's last record
+            drain.armed = false;  // (the stream has just been waited for)
+            return bl_batch_upload(ctx, "", 0, nullptr, 0, out);
+        }
     }
 
     {
         const size_t per = up256((n_lines_raw + 2) * sizeof(unsigned long long));
         unsigned char* a1 = static_cast<unsigned char*>(bl_ctx_scratch(ctx, 1, 5 * per));
-        if (!a1) return fail_free(BL_ERR_OOM, "device allocation failed (line scratch)");
+        if (!a1) return bl_set_error(BL_ERR_OOM, "device allocation failed (line scratch)");
         d_line_end = reinterpret_cast<unsigned long long*>(a1);
         d_len = reinterpret_cast<unsigned long long*>(a1 + per);
         d_hdr = reinterpret_cast<unsigned long long*>(a1 + 2 * per);
@@ -244,68 +233,67 @@ int bl_parse_device_text_lines(bl_ctx* ctx, const uint8_t* d_text_in, uint64_t n
         d_dst = reinterpret_cast<unsigned long long*>(a1 + 4 * per);
     }
     hipLaunchKernelGGL(newline_positions_kernel, dim3(n_blocks), dim3(PB), 0, s, d_text, n, d_blk_base, d_line_end);
-    if (open_last_line) P_HIP(hipMemcpyAsync(d_line_end + n_newlines, &n, sizeof(unsigned long long), hipMemcpyHostToDevice, s));  // virtual '\n'
-    P_HIP(hipMemsetAsync(d_len + n_lines, 0, sizeof(unsigned long long), s));
+    if (open_last_line) BLH_TRY(hipMemcpyAsync(d_line_end + n_newlines, &n, sizeof(unsigned long long), hipMemcpyHostToDevice, s));  // virtual '\n'
+    BLH_TRY(hipMemsetAsync(d_len + n_lines, 0, sizeof(unsigned long long), s));
     const unsigned lb = (unsigned)((n_lines + 255) / 256);
     hipLaunchKernelGGL(classify_lines_kernel, dim3(lb), dim3(256), 0, s, d_text, d_line_end, n_lines, fastq ? 1 : 0, d_len, d_hdr, d_err);
 
-    P_HIP(rocprim::inclusive_scan(nullptr, need, d_hdr, d_rec, (size_t)n_lines, rocprim::plus<unsigned long long>(), s));
+    BLH_TRY(rocprim::inclusive_scan(nullptr, need, d_hdr, d_rec, (size_t)n_lines, rocprim::plus<unsigned long long>(), s));
     if (need > tmp_bytes) {
-        P_HIP(hipStreamSynchronize(s));
+        BLH_TRY(hipStreamSynchronize(s));
         tmp_bytes = need;
         d_tmp = bl_ctx_scratch(ctx, 2, tmp_bytes);
-        if (!d_tmp) return fail_free(BL_ERR_OOM, "device allocation failed (scan scratch)");
+        if (!d_tmp) return bl_set_error(BL_ERR_OOM, "device allocation failed (scan scratch)");
     }
-    P_HIP(rocprim::inclusive_scan(d_tmp, need, d_hdr, d_rec, (size_t)n_lines, rocprim::plus<unsigned long long>(), s));
+    BLH_TRY(rocprim::inclusive_scan(d_tmp, need, d_hdr, d_rec, (size_t)n_lines, rocprim::plus<unsigned long long>(), s));
     if (!fastq) hipLaunchKernelGGL(mask_leading_lines_kernel, dim3(lb), dim3(256), 0, s, d_rec, d_len, n_lines);
-    P_HIP(rocprim::exclusive_scan(nullptr, need, d_len, d_dst, 0ull, (size_t)n_lines + 1, rocprim::plus<unsigned long long>(), s));
+    BLH_TRY(rocprim::exclusive_scan(nullptr, need, d_len, d_dst, 0ull, (size_t)n_lines + 1, rocprim::plus<unsigned long long>(), s));
     if (need > tmp_bytes) {
-        P_HIP(hipStreamSynchronize(s));
+        BLH_TRY(hipStreamSynchronize(s));
         tmp_bytes = need;
         d_tmp = bl_ctx_scratch(ctx, 2, tmp_bytes);
-        if (!d_tmp) return fail_free(BL_ERR_OOM, "device allocation failed (scan scratch)");
+        if (!d_tmp) return bl_set_error(BL_ERR_OOM, "device allocation failed (scan scratch)");
     }
-    P_HIP(rocprim::exclusive_scan(d_tmp, need, d_len, d_dst, 0ull, (size_t)n_lines + 1, rocprim::plus<unsigned long long>(), s));
+    BLH_TRY(rocprim::exclusive_scan(d_tmp, need, d_len, d_dst, 0ull, (size_t)n_lines + 1, rocprim::plus<unsigned long long>(), s));
 
     unsigned long long total = 0, n_records = 0;
     unsigned int err = 0;
-    P_HIP(hipMemcpyAsync(&total, d_dst + n_lines, sizeof(total), hipMemcpyDeviceToHost, s));
-    P_HIP(hipMemcpyAsync(&n_records, d_rec + (n_lines - 1), sizeof(n_records), hipMemcpyDeviceToHost, s));
-    P_HIP(hipMemcpyAsync(&err, d_err, sizeof(err), hipMemcpyDeviceToHost, s));
-    P_HIP(hipStreamSynchronize(s));
-    if (err & ERR_MASK) return fail_free(BL_ERR_INVALID, refusal_message(err));
+    BLH_TRY(hipMemcpyAsync(&total, d_dst + n_lines, sizeof(total), hipMemcpyDeviceToHost, s));
+    BLH_TRY(hipMemcpyAsync(&n_records, d_rec + (n_lines - 1), sizeof(n_records), hipMemcpyDeviceToHost, s));
+    BLH_TRY(hipMemcpyAsync(&err, d_err, sizeof(err), hipMemcpyDeviceToHost, s));
+    BLH_TRY(hipStreamSynchronize(s));
+    if (err & ERR_MASK) return bl_set_error(BL_ERR_INVALID, refusal_message(err));
     const bool lone_cr_seen = (err & NOTE_FASTA_LONE_CR) != 0;  // FASTA only: refused where such a line opens its record
 
-    d_bases = static_cast<uint8_t*>(bl_ctx_pool_alloc(ctx, total + 64));
-    d_offsets = static_cast<unsigned long long*>(bl_ctx_pool_alloc(ctx, (n_records + 1) * sizeof(unsigned long long)));
-    if (!d_bases || !d_offsets) return fail_free(BL_ERR_OOM, "device allocation failed (batch)");
-    P_HIP(hipMemsetAsync(d_bases + (total & ~15ull), 0, 64 + (total & 15ull), s));
+    d_bases = blh::Pooled<uint8_t>(ctx, total + 64);
+    d_offsets = blh::Pooled<unsigned long long>(ctx, (n_records + 1) * sizeof(unsigned long long));
+    if (!d_bases || !d_offsets) return bl_set_error(BL_ERR_OOM, "device allocation failed (batch)");
+    BLH_TRY(hipMemsetAsync(d_bases.get() + (total & ~15ull), 0, 64 + (total & 15ull), s));
     if (total) {
         const uint64_t threads = (total + 15) / 16;
         hipLaunchKernelGGL(gather_bases_kernel, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, s, d_text, d_line_end, d_dst, d_len, n_lines,
-                           d_bases, (uint64_t)total);
+                           d_bases.get(), (uint64_t)total);
     }
-    hipLaunchKernelGGL(record_offsets_kernel, dim3(lb), dim3(256), 0, s, d_hdr, d_rec, d_dst, n_lines, d_offsets, (uint64_t)n_records, (uint64_t)total);
+    hipLaunchKernelGGL(record_offsets_kernel, dim3(lb), dim3(256), 0, s, d_hdr, d_rec, d_dst, n_lines, d_offsets.get(), (uint64_t)n_records, (uint64_t)total);
     // reads of one length (the usual short-read file) make a fixed-length batch: the read-tiled scan kernels, no start-bit vector
     if (lone_cr_seen) {
-        hipLaunchKernelGGL(lone_cr_lines_kernel, dim3(lb), dim3(256), 0, s, d_text, d_line_end, d_hdr, d_rec, d_dst, d_offsets, n_lines, d_err);
-        P_HIP(hipMemcpyAsync(&err, d_err, sizeof(err), hipMemcpyDeviceToHost, s));
+        hipLaunchKernelGGL(lone_cr_lines_kernel, dim3(lb), dim3(256), 0, s, d_text, d_line_end, d_hdr, d_rec, d_dst, d_offsets.get(), n_lines, d_err);
+        BLH_TRY(hipMemcpyAsync(&err, d_err, sizeof(err), hipMemcpyDeviceToHost, s));
     }
     uint64_t fixed_len = n_records > 1 && total % n_records == 0 ? total / n_records : 0;
     unsigned int ragged = 0;
     if (fixed_len) {
-        P_HIP(hipMemsetAsync(d_err + 1, 0, sizeof(unsigned int), s));
-        hipLaunchKernelGGL(uniform_length_kernel, dim3(uniform_length_blocks(n_records)), dim3(256), 0, s, d_offsets, (uint64_t)n_records, fixed_len, d_err + 1);
-        P_HIP(hipMemcpyAsync(&ragged, d_err + 1, sizeof(ragged), hipMemcpyDeviceToHost, s));
+        BLH_TRY(hipMemsetAsync(d_err + 1, 0, sizeof(unsigned int), s));
+        hipLaunchKernelGGL(uniform_length_kernel, dim3(uniform_length_blocks(n_records)), dim3(256), 0, s, d_offsets.get(), (uint64_t)n_records, fixed_len, d_err + 1);
+        BLH_TRY(hipMemcpyAsync(&ragged, d_err + 1, sizeof(ragged), hipMemcpyDeviceToHost, s));
     }
-    P_HIP(hipGetLastError());
-    P_HIP(hipStreamSynchronize(s));
-    if (err & ERR_MASK) return fail_free(BL_ERR_INVALID, refusal_message(err));
+    BLH_TRY(hipGetLastError());
+    BLH_TRY(hipStreamSynchronize(s));
+    if (err & ERR_MASK) return bl_set_error(BL_ERR_INVALID, refusal_message(err));
     if (ragged) fixed_len = 0;
-    handed_over = true;
-    cleanup();
+    drain.now();
     if (lines) *lines = bl_parse::LineIndex{d_line_end, d_hdr, d_rec, d_dst, n_lines, n_records, total, fastq ? 1 : 0};
-    int rc = bl_batch_adopt_device(ctx, d_bases, total, reinterpret_cast<uint64_t*>(d_offsets), n_records, fixed_len, out);  // takes ownership of both
+    int rc = bl_batch_adopt_device(ctx, d_bases.release(), total, reinterpret_cast<uint64_t*>(d_offsets.release()), n_records, fixed_len, out);  // takes ownership of both
     if (rc != BL_OK) return rc;
     if (n_seqs) *n_seqs = n_records;
     if (n_bases) *n_bases = total;

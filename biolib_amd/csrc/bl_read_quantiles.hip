@@ -10,13 +10,8 @@
 #include <string>
 
 #include "../../include/biolib_amd.h"
+#include "bl_host.hpp"
 #include "bl_read_quantiles_core.hpp"
-
-extern int bl_set_error(int code, const char* msg);  // bl_capi.hip
-extern hipStream_t bl_ctx_stream(bl_ctx* ctx);
-extern int bl_ctx_device(bl_ctx* ctx);
-extern void* bl_ctx_scratch(bl_ctx* ctx, int slot, size_t bytes);  // as the set operations: 4 data, 6 counters
-extern int bl_batch_describe(const bl_batch* batch, bl_ctx** ctx, uint64_t* n_bases, uint64_t* n_seqs, uint64_t* read_len);
 
 namespace blrq {
 
@@ -236,8 +231,8 @@ __global__ __launch_bounds__(WG_TPB) void select_wg_kernel(const SelectParams p)
 
 namespace {
 
-int hip_rc(hipError_t e) { return bl_set_error(e == hipErrorOutOfMemory ? BL_ERR_OOM : BL_ERR_HIP, hipGetErrorString(e)); }
-int invalid(const char* msg) { return bl_set_error(BL_ERR_INVALID, msg); }
+using blh::hip_rc;
+using blh::invalid;
 
 }  // namespace
 

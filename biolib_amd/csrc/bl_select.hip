@@ -10,20 +10,11 @@
 #include <hip/hip_runtime.h>
 
 #include <cstring>
-#include <rocprim/device/device_scan.hpp>
 #include <string>
 
 #include "../../include/biolib_amd.h"
+#include "bl_host.hpp"
 #include "bl_select_core.hpp"
-
-extern int bl_set_error(int code, const char* msg);  // bl_capi.hip
-extern hipStream_t bl_ctx_stream(bl_ctx* ctx);
-extern int bl_ctx_device(bl_ctx* ctx);
-extern void* bl_ctx_scratch(bl_ctx* ctx, int slot, size_t bytes);  // as the set operations: 4 data, 5 library workspace, 6 counters
-extern void* bl_ctx_pool_alloc(bl_ctx* ctx, size_t bytes);         // batch buffers
-extern void bl_ctx_pool_free(bl_ctx* ctx, void* p);
-extern int bl_batch_describe(const bl_batch* batch, bl_ctx** ctx, uint64_t* n_bases, uint64_t* n_seqs, uint64_t* read_len);
-extern int bl_batch_adopt_device(bl_ctx* ctx, void* d_bases, uint64_t n_bases, uint64_t* d_offsets, uint64_t n_seqs, uint64_t fixed_len, bl_batch** out);
 
 static_assert(sizeof(blsel::Record) == sizeof(bl_read_counts), "Record is bl_read_counts");
 static_assert(sizeof(blsel::SpanRule) == sizeof(bl_span_rule), "SpanRule is bl_span_rule");
@@ -107,20 +98,10 @@ __global__ __launch_bounds__(TPB) void gather_kernel(const SelectParams p)
 
 namespace {
 
-int hip_rc(hipError_t e) { return bl_set_error(e == hipErrorOutOfMemory ? BL_ERR_OOM : BL_ERR_HIP, hipGetErrorString(e)); }
-int invalid(const char* msg) { return bl_set_error(BL_ERR_INVALID, msg); }
+using blh::exclusive_sum;
+using blh::hip_rc;
+using blh::invalid;
 unsigned blocks_for(uint64_t threads) { return (unsigned)((threads + TPB - 1) / TPB); }
-
-int exclusive_sum(bl_ctx* ctx, const uint64_t* in, uint64_t* out, size_t n, hipStream_t s)
-{
-    size_t bytes = 0;
-    hipError_t e = rocprim::exclusive_scan(nullptr, bytes, in, out, (uint64_t)0, n, rocprim::plus<uint64_t>(), s);
-    if (e != hipSuccess) return hip_rc(e);
-    void* tmp = bl_ctx_scratch(ctx, 5, bytes ? bytes : 16);
-    if (!tmp) return bl_set_error(BL_ERR_OOM, "scratch allocation failed");
-    e = rocprim::exclusive_scan(tmp, bytes, in, out, (uint64_t)0, n, rocprim::plus<uint64_t>(), s);
-    return e == hipSuccess ? BL_OK : hip_rc(e);
-}
 
 // what both calls check of (ctx, batch, d_offsets); fills the source's description
 int describe_source(bl_ctx* ctx, const bl_batch* batch, const uint64_t* d_offsets, uint64_t& n_bases, uint64_t& n_seqs, uint64_t& read_len)
@@ -138,12 +119,6 @@ int describe_source(bl_ctx* ctx, const bl_batch* batch, const uint64_t* d_offset
 }  // namespace
 
 }  // namespace blsel
-
-#define S_HIP(call)                                 \
-    do {                                            \
-        hipError_t e_ = (call);                     \
-        if (e_ != hipSuccess) return fail_free(e_); \
-    } while (0)
 
 extern "C" int bl_batch_select(bl_ctx* ctx, const bl_batch* batch, const uint64_t* d_offsets, const uint64_t* d_spans, uint32_t flags, bl_batch** out,
                                uint64_t* d_out_offsets, uint64_t* d_source_index, uint64_t* n_seqs_out, uint64_t* n_bases_out)
@@ -181,55 +156,43 @@ extern "C" int bl_batch_select(bl_ctx* ctx, const bl_batch* batch, const uint64_
     p.keep_sum = keep_sum;
     p.src_start = arena + 5 * n1;
 
-    uint8_t* d_bases = nullptr;
-    uint64_t* d_offs = nullptr;
-    auto fail_free = [&](hipError_t err) {
-        bl_ctx_pool_free(ctx, d_bases);
-        bl_ctx_pool_free(ctx, d_offs);
-        return hip_rc(err);
-    };
-
     hipLaunchKernelGGL(span_lengths_kernel, dim3(blocks_for(n1)), dim3(TPB), 0, s, p);
-    S_HIP(hipGetLastError());
+    BLH_TRY(hipGetLastError());
     rc = exclusive_sum(ctx, p.len, len_sum, (size_t)n1, s);
     if (rc == BL_OK) rc = exclusive_sum(ctx, p.keep, keep_sum, (size_t)n1, s);  // (the first sum is done with slot 5: same stream)
     if (rc != BL_OK) return rc;
     unsigned long long total = 0, n_out = 0;
-    S_HIP(hipMemcpyAsync(&total, len_sum + p.n_seqs, sizeof(total), hipMemcpyDeviceToHost, s));
-    S_HIP(hipMemcpyAsync(&n_out, keep_sum + p.n_seqs, sizeof(n_out), hipMemcpyDeviceToHost, s));
-    S_HIP(hipStreamSynchronize(s));
+    BLH_TRY(hipMemcpyAsync(&total, len_sum + p.n_seqs, sizeof(total), hipMemcpyDeviceToHost, s));
+    BLH_TRY(hipMemcpyAsync(&n_out, keep_sum + p.n_seqs, sizeof(n_out), hipMemcpyDeviceToHost, s));
+    BLH_TRY(hipStreamSynchronize(s));
     p.total = total;
     p.n_out = n_out;
 
-    d_bases = static_cast<uint8_t*>(bl_ctx_pool_alloc(ctx, (size_t)total + 64));
-    d_offs = static_cast<uint64_t*>(bl_ctx_pool_alloc(ctx, (size_t)(n_out + 1) * sizeof(uint64_t)));
-    if (!d_bases || !d_offs) {
-        bl_ctx_pool_free(ctx, d_bases);
-        bl_ctx_pool_free(ctx, d_offs);
-        return bl_set_error(BL_ERR_OOM, "device allocation failed (batch)");
-    }
-    p.out = d_bases;
-    p.out_offsets = d_offs;
-    S_HIP(hipMemsetAsync(d_bases + (total & ~15ull), 0, 64 + (total & 15ull), s));  // (the last chunk's store comes after it and repeats its zeros)
+    blh::Pooled<uint8_t> d_bases(ctx, (size_t)total + 64);
+    blh::Pooled<uint64_t> d_offs(ctx, (size_t)(n_out + 1) * sizeof(uint64_t));
+    if (!d_bases || !d_offs) return bl_set_error(BL_ERR_OOM, "device allocation failed (batch)");
+    p.out = d_bases.get();
+    p.out_offsets = d_offs.get();
+    BLH_TRY(hipMemsetAsync(d_bases.get() + (total & ~15ull), 0, 64 + (total & 15ull), s));  // (the last chunk's store comes after it and repeats its zeros)
     hipLaunchKernelGGL(place_kernel, dim3(blocks_for(n1)), dim3(TPB), 0, s, p);
-    S_HIP(hipGetLastError());
+    BLH_TRY(hipGetLastError());
     if (total) {
         const uint64_t waves = (total + WAVE_BYTES - 1) / WAVE_BYTES;
         hipLaunchKernelGGL(gather_kernel, dim3(blocks_for(waves * 64)), dim3(TPB), 0, s, p);
-        S_HIP(hipGetLastError());
+        BLH_TRY(hipGetLastError());
     }
     // sequences of one length make a fixed-length batch (the parser's rule): the read-tiled scan kernels, no start-bit vector
     uint64_t fixed_len = n_out > 1 && total != 0 && total % n_out == 0 ? total / n_out : 0;
     unsigned int ragged = 0;
     if (fixed_len) {
-        S_HIP(hipMemsetAsync(d_flag, 0, sizeof(unsigned int), s));
-        hipLaunchKernelGGL(uniform_kernel, dim3(blocks_for(n_out + 1)), dim3(TPB), 0, s, d_offs, (uint64_t)n_out, fixed_len, d_flag);
-        S_HIP(hipGetLastError());
-        S_HIP(hipMemcpyAsync(&ragged, d_flag, sizeof(ragged), hipMemcpyDeviceToHost, s));
+        BLH_TRY(hipMemsetAsync(d_flag, 0, sizeof(unsigned int), s));
+        hipLaunchKernelGGL(uniform_kernel, dim3(blocks_for(n_out + 1)), dim3(TPB), 0, s, d_offs.get(), (uint64_t)n_out, fixed_len, d_flag);
+        BLH_TRY(hipGetLastError());
+        BLH_TRY(hipMemcpyAsync(&ragged, d_flag, sizeof(ragged), hipMemcpyDeviceToHost, s));
     }
-    S_HIP(hipStreamSynchronize(s));
+    BLH_TRY(hipStreamSynchronize(s));
     if (ragged) fixed_len = 0;
-    rc = bl_batch_adopt_device(ctx, d_bases, total, d_offs, n_out, fixed_len, out);  // takes ownership of both
+    rc = bl_batch_adopt_device(ctx, d_bases.release(), total, d_offs.release(), n_out, fixed_len, out);  // takes ownership of both
     if (rc != BL_OK) return rc;
     if (n_seqs_out) *n_seqs_out = n_out;
     if (n_bases_out) *n_bases_out = total;

@@ -13,11 +13,7 @@
 #include <rocprim/device/device_select.hpp>
 
 #include "../../include/biolib_amd.h"
-
-extern int bl_set_error(int code, const char* msg);
-extern hipStream_t bl_ctx_stream(bl_ctx* ctx);  // bl_capi.hip
-extern int bl_ctx_device(bl_ctx* ctx);
-extern void* bl_ctx_scratch(bl_ctx* ctx, int slot, size_t bytes);  // bl_capi.hip: grow-only device scratch of the context (slots 4-6 are ours)
+#include "bl_host.hpp"
 
 namespace {
 
@@ -39,12 +35,6 @@ __global__ void intersect_count_kernel(const unsigned long long* a, unsigned lon
     if ((threadIdx.x & 63) == 0 && local) atomicAdd(out, local);
 }
 
-#define SET_HIP(call)                                                                                    \
-    do {                                                                                                 \
-        hipError_t e_ = (call);                                                                          \
-        if (e_ != hipSuccess) return bl_set_error(e_ == hipErrorOutOfMemory ? BL_ERR_OOM : BL_ERR_HIP, hipGetErrorString(e_)); \
-    } while (0)
-
 }  // namespace
 
 extern "C" {
@@ -54,7 +44,7 @@ int bl_sort_unique_u64(bl_ctx* ctx, uint64_t* d_keys, uint64_t n, uint64_t* n_un
     if (!ctx || !n_unique || (n && !d_keys)) return bl_set_error(BL_ERR_INVALID, "NULL argument");
     *n_unique = 0;
     if (n == 0) return BL_OK;
-    SET_HIP(hipSetDevice(bl_ctx_device(ctx)));
+    BLH_TRY(hipSetDevice(bl_ctx_device(ctx)));
     hipStream_t s = bl_ctx_stream(ctx);
     unsigned long long* keys = reinterpret_cast<unsigned long long*>(d_keys);
     unsigned long long* tmp = nullptr;
@@ -87,7 +77,7 @@ int bl_jaccard_sorted_u64(bl_ctx* ctx, const uint64_t* d_a, uint64_t na, const u
                           uint64_t* union_size)
 {
     if (!ctx || !intersection || !union_size || (na && !d_a) || (nb && !d_b)) return bl_set_error(BL_ERR_INVALID, "NULL argument");
-    SET_HIP(hipSetDevice(bl_ctx_device(ctx)));
+    BLH_TRY(hipSetDevice(bl_ctx_device(ctx)));
     hipStream_t s = bl_ctx_stream(ctx);
     unsigned long long* d_out = static_cast<unsigned long long*>(bl_ctx_scratch(ctx, 6, 64));
     if (!d_out) return bl_set_error(BL_ERR_OOM, "scratch allocation failed");
@@ -136,7 +126,7 @@ extern "C" {
 int bl_partition_u64(bl_ctx* ctx, const uint64_t* d_keys, uint64_t n, uint32_t parts, uint64_t seed, uint64_t* d_out, uint64_t* counts)
 {
     if (!ctx || !counts || parts == 0 || parts > blpart::MAX_PARTS || (n && (!d_keys || !d_out))) return bl_set_error(BL_ERR_INVALID, "bad argument (1 <= parts <= 64)");
-    SET_HIP(hipSetDevice(bl_ctx_device(ctx)));
+    BLH_TRY(hipSetDevice(bl_ctx_device(ctx)));
     const unsigned long long* keys = reinterpret_cast<const unsigned long long*>(d_keys);
     unsigned long long host[blpart::MAX_PARTS];
     const hipError_t e = blpart::partition(keys, (unsigned long long)n, parts, KeyHashOwner{keys, (uint32_t)seed}, reinterpret_cast<unsigned long long*>(d_out), host,
@@ -152,7 +142,7 @@ int bl_count_sorted_u64(bl_ctx* ctx, const uint64_t* d_sorted, uint64_t n, uint6
     if (!ctx || !n_unique || (n && (!d_sorted || !d_unique || !d_counts))) return bl_set_error(BL_ERR_INVALID, "NULL argument");
     *n_unique = 0;
     if (n == 0) return BL_OK;
-    SET_HIP(hipSetDevice(bl_ctx_device(ctx)));
+    BLH_TRY(hipSetDevice(bl_ctx_device(ctx)));
     hipStream_t s = bl_ctx_stream(ctx);
     unsigned long long* d_runs = nullptr;
     void* tmp = nullptr;
@@ -180,7 +170,7 @@ int bl_sort_u64(bl_ctx* ctx, uint64_t* d_keys, uint64_t n)
 {
     if (!ctx || (n && !d_keys)) return bl_set_error(BL_ERR_INVALID, "NULL argument");
     if (n == 0) return BL_OK;
-    SET_HIP(hipSetDevice(bl_ctx_device(ctx)));
+    BLH_TRY(hipSetDevice(bl_ctx_device(ctx)));
     hipStream_t s = bl_ctx_stream(ctx);
     unsigned long long* keys = reinterpret_cast<unsigned long long*>(d_keys);
     unsigned long long* tmp = nullptr;
@@ -232,7 +222,7 @@ __global__ __launch_bounds__(256) void stream_read_kernel(const Quad* __restrict
 extern "C" int bl_probe_hbm(bl_ctx* ctx, uint64_t n_bytes, int iters, double* read_gbps, double* copy_gbps)
 {
     if (!ctx || !read_gbps || !copy_gbps || iters < 1 || n_bytes < (1u << 20)) return bl_set_error(BL_ERR_INVALID, "bad argument (>= 1 MiB, >= 1 iteration)");
-    SET_HIP(hipSetDevice(bl_ctx_device(ctx)));
+    BLH_TRY(hipSetDevice(bl_ctx_device(ctx)));
     hipStream_t s = bl_ctx_stream(ctx);
     n_bytes &= ~(uint64_t)15;
     void *a = nullptr, *b = nullptr;
@@ -310,7 +300,7 @@ extern "C" int bl_clock_probe_start(bl_ctx* ctx, uint32_t duration_ms, bl_clock_
 {
     if (!ctx || !out || duration_ms == 0 || duration_ms > 5000) return bl_set_error(BL_ERR_INVALID, "clock probe: need a context and 1..5000 ms");
     *out = nullptr;
-    SET_HIP(hipSetDevice(bl_ctx_device(ctx)));
+    BLH_TRY(hipSetDevice(bl_ctx_device(ctx)));
     bl_clock_probe* p = new (std::nothrow) bl_clock_probe{bl_ctx_device(ctx), nullptr, nullptr};
     if (!p) return bl_set_error(BL_ERR_OOM, "host allocation failed");
     hipError_t e = hipStreamCreateWithFlags(&p->stream, hipStreamNonBlocking);
@@ -365,10 +355,10 @@ extern "C" int bl_read_file_u64(bl_ctx* ctx, const char* path, int with_count, u
     std::vector<uint64_t> host(cnt);
     rc = bl_read_file_u64_host(path, with_count, host.data(), cnt, nullptr);
     if (rc != BL_OK) return rc;
-    SET_HIP(hipSetDevice(bl_ctx_device(ctx)));
+    BLH_TRY(hipSetDevice(bl_ctx_device(ctx)));
     hipStream_t s = bl_ctx_stream(ctx);
-    SET_HIP(hipMemcpyAsync(d_out, host.data(), cnt * sizeof(uint64_t), hipMemcpyHostToDevice, s));
-    SET_HIP(hipStreamSynchronize(s));  // `host` goes away
+    BLH_TRY(hipMemcpyAsync(d_out, host.data(), cnt * sizeof(uint64_t), hipMemcpyHostToDevice, s));
+    BLH_TRY(hipStreamSynchronize(s));  // `host` goes away
     return BL_OK;
 }
 
@@ -390,7 +380,7 @@ extern "C" int bl_merge_runs_u64(bl_ctx* ctx, const char* const* paths, uint32_t
         int rc = bl_read_file_u64(ctx, paths[i], 0, d_out + off[i], len[i], nullptr);
         if (rc != BL_OK) return rc;
     }
-    SET_HIP(hipSetDevice(bl_ctx_device(ctx)));
+    BLH_TRY(hipSetDevice(bl_ctx_device(ctx)));
     hipStream_t s = bl_ctx_stream(ctx);
     // runs = [off[i], off[i+1]); merge neighbours pairwise, ping-ponging between d_out and a scratch array
     unsigned long long* a = reinterpret_cast<unsigned long long*>(d_out);

@@ -20,15 +20,10 @@
 #include <vector>
 
 #include "../../include/biolib_amd.h"
+#include "bl_host.hpp"
 #include "bl_kmers128_core.hpp"
 #include "bl_partition.hpp"
 #include "bl_setops128_core.hpp"
-
-extern int bl_set_error(int code, const char* msg);  // bl_capi.hip
-extern hipStream_t bl_ctx_stream(bl_ctx* ctx);
-extern int bl_ctx_device(bl_ctx* ctx);
-extern void* bl_ctx_scratch(bl_ctx* ctx, int slot, size_t bytes);  // slots 4-6 are the set operations': 4 data, 5 library workspace, 6 counters
-extern int bl_ctx_jaccard128_path(bl_ctx* ctx);                    // the "jaccard128_path" option
 
 namespace {
 
@@ -91,7 +86,7 @@ struct Key128HashOwner {
     }
 };
 
-int hip_rc(hipError_t e) { return bl_set_error(e == hipErrorOutOfMemory ? BL_ERR_OOM : BL_ERR_HIP, hipGetErrorString(e)); }
+using blh::hip_rc;
 bool misaligned(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) != 0; }
 int bad_alignment() { return bl_set_error(BL_ERR_INVALID, "arrays of 16-byte keys must be 16-byte aligned"); }
 

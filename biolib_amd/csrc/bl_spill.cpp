@@ -13,8 +13,7 @@
 #include <vector>
 
 #include "../../include/biolib_amd.h"
-
-extern int bl_set_error(int code, const char* msg);  // bl_capi.hip
+#include "bl_host.hpp"
 
 extern "C" {
 

@@ -22,24 +22,14 @@
 #include <vector>
 
 #include "../../include/biolib_amd.h"
+#include "bl_host.hpp"
 #include "bl_partition.hpp"
 #include "bl_scan_core.hpp"
-
-extern int bl_set_error(int code, const char* msg);  // bl_capi.hip
-extern hipStream_t bl_ctx_stream(bl_ctx* ctx);
-extern int bl_ctx_device(bl_ctx* ctx);
-extern void* bl_ctx_scratch(bl_ctx* ctx, int slot, size_t bytes);  // bl_capi.hip: device scratch that lives with the context
 
 namespace {
 
 constexpr int MAX_PARTS = 64;
 constexpr int MAX_BASES = 59;
-
-#define SK_HIP(call)                                                                                                             \
-    do {                                                                                                                         \
-        hipError_t e_ = (call);                                                                                                  \
-        if (e_ != hipSuccess) return bl_set_error(e_ == hipErrorOutOfMemory ? BL_ERR_OOM : BL_ERR_HIP, hipGetErrorString(e_));    \
-    } while (0)
 
 __device__ __forceinline__ unsigned code_of(unsigned char c) { return ((c >> 1) ^ (c >> 2)) & 3u; }  // A0 C1 G2 T/U3 (constants.hpp:12-21)
 
@@ -625,12 +615,12 @@ int bl_pack_super_kmers(bl_ctx* ctx, const bl_batch* batch, const uint64_t* d_fi
     if (n_groups && !d_mm_pos) return bl_set_error(BL_ERR_INVALID, "d_mm_pos is required: the record's owner finds the minimizer through it");
     if (k < 1 || k > 32 || m < 1 || m > k || 2 * k - m > MAX_BASES) return bl_set_error(BL_ERR_INVALID, "need 1 <= m <= k <= 32 and 2k - m <= 59 (bases per packed record)");
     if (n_groups == 0) return BL_OK;
-    SK_HIP(hipSetDevice(bl_ctx_device(ctx)));
+    BLH_TRY(hipSetDevice(bl_ctx_device(ctx)));
     hipStream_t s = bl_ctx_stream(ctx);
     hipLaunchKernelGGL(pack_kernel, dim3((unsigned)((n_groups + 255) / 256)), dim3(256), 0, s, static_cast<const unsigned char*>(bl_batch_device_bases(batch)),
                        (unsigned long long)bl_batch_n_bases(batch), reinterpret_cast<const unsigned long long*>(d_first_pos), d_sizes, d_mm_pos,
                        (unsigned long long)n_groups, (int)k, reinterpret_cast<ulonglong2*>(d_records), (unsigned long long)bl_batch_origin(batch));
-    SK_HIP(hipGetLastError());
+    BLH_TRY(hipGetLastError());
     return BL_OK;
 }
 
@@ -638,7 +628,7 @@ int bl_partition_records(bl_ctx* ctx, const uint64_t* d_hashes, const uint64_t* 
 {
     if (!ctx || !counts || parts == 0 || parts > MAX_PARTS || (n && (!d_hashes || !d_records || !d_out)))
         return bl_set_error(BL_ERR_INVALID, "bad argument (1 <= parts <= 64)");
-    SK_HIP(hipSetDevice(bl_ctx_device(ctx)));
+    BLH_TRY(hipSetDevice(bl_ctx_device(ctx)));
     unsigned long long host[MAX_PARTS];
     const hipError_t e = blpart::partition(reinterpret_cast<const ulonglong2*>(d_records), (unsigned long long)n, parts,
                                            HashArrayOwner{reinterpret_cast<const unsigned long long*>(d_hashes)}, reinterpret_cast<ulonglong2*>(d_out), host,
@@ -655,7 +645,7 @@ int bl_expand_super_kmers(bl_ctx* ctx, const uint64_t* d_records, uint64_t n_gro
     if (k < 1 || k > 32) return bl_set_error(BL_ERR_INVALID, "need 1 <= k <= 32");
     *n_kmers = 0;
     if (n_groups == 0) return BL_OK;
-    SK_HIP(hipSetDevice(bl_ctx_device(ctx)));
+    BLH_TRY(hipSetDevice(bl_ctx_device(ctx)));
     hipStream_t s = bl_ctx_stream(ctx);
     unsigned long long *sizes = nullptr, *offsets = nullptr;
     void* tmp = nullptr;
@@ -702,7 +692,7 @@ int bl_count_super_kmers(bl_ctx* ctx, const uint64_t* d_records, uint64_t n_grou
     if (k == 32 && !canonical) return bl_set_error(BL_ERR_INVALID, "k = 32 needs the canonical flag here (the all-T 32-mer is the table's empty mark); use bl_expand_super_kmers + bl_sort_u64");
     *n_distinct = 0;
     if (n_groups == 0) return BL_OK;
-    SK_HIP(hipSetDevice(bl_ctx_device(ctx)));
+    BLH_TRY(hipSetDevice(bl_ctx_device(ctx)));
     hipStream_t s = bl_ctx_stream(ctx);
     const uint32_t n = (uint32_t)n_groups;
     // buckets of ~36 records (about 300 k-mers at k = 31, m = 15), one wave each; at most 2^26 of them

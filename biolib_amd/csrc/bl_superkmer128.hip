@@ -28,14 +28,9 @@
 #include <vector>
 
 #include "../../include/biolib_amd.h"
+#include "bl_host.hpp"
 #include "bl_partition.hpp"
 #include "bl_superkmer128_core.hpp"
-
-extern int bl_set_error(int code, const char* msg);  // bl_capi.hip
-extern hipStream_t bl_ctx_stream(bl_ctx* ctx);
-extern int bl_ctx_device(bl_ctx* ctx);
-extern void* bl_ctx_scratch(bl_ctx* ctx, int slot, size_t bytes);
-extern int bl_ctx_count128_tables(bl_ctx* ctx);  // the "count128_tables" option
 
 namespace {
 
@@ -49,12 +44,6 @@ using bl::WaveTable128;
 
 constexpr int MAX_PARTS = 64;
 constexpr const char* LIMITS = "need 1 <= m <= 32, m <= k <= 64, k - m + 1 <= 64 and 2k - m <= 122 (bases per 32-byte record)";
-
-#define SK_HIP(call)                                                                                                             \
-    do {                                                                                                                         \
-        hipError_t e_ = (call);                                                                                                  \
-        if (e_ != hipSuccess) return bl_set_error(e_ == hipErrorOutOfMemory ? BL_ERR_OOM : BL_ERR_HIP, hipGetErrorString(e_));    \
-    } while (0)
 
 bool shape_ok(uint32_t k, uint32_t m) { return m >= 1 && m <= 32 && k >= m && k <= 64 && k - m + 1 <= 64 && 2 * k - m <= (uint32_t)bl::SK128_MAX_BASES; }
 
@@ -340,7 +329,7 @@ hipError_t count_by_sort128(bl_ctx* ctx, const Rec32* recs, unsigned long long n
     return e;
 }
 
-int hip_rc(hipError_t e) { return bl_set_error(e == hipErrorOutOfMemory ? BL_ERR_OOM : BL_ERR_HIP, hipGetErrorString(e)); }
+using blh::hip_rc;
 
 }  // namespace
 
@@ -354,12 +343,12 @@ int bl_pack_super_kmers128(bl_ctx* ctx, const bl_batch* batch, const uint64_t* d
     if (!shape_ok(k, m)) return bl_set_error(BL_ERR_INVALID, LIMITS);
     if ((uintptr_t)d_records & 31u) return bl_set_error(BL_ERR_INVALID, "d_records must be 32-byte aligned");
     if (n_groups == 0) return BL_OK;
-    SK_HIP(hipSetDevice(bl_ctx_device(ctx)));
+    BLH_TRY(hipSetDevice(bl_ctx_device(ctx)));
     hipStream_t s = bl_ctx_stream(ctx);
     hipLaunchKernelGGL(pack128_kernel, dim3((unsigned)((n_groups + 255) / 256)), dim3(256), 0, s, static_cast<const unsigned char*>(bl_batch_device_bases(batch)),
                        (unsigned long long)bl_batch_n_bases(batch), reinterpret_cast<const unsigned long long*>(d_first_pos), d_sizes, d_mm_pos,
                        (unsigned long long)n_groups, (int)k, reinterpret_cast<Rec32*>(d_records), (unsigned long long)bl_batch_origin(batch));
-    SK_HIP(hipGetLastError());
+    BLH_TRY(hipGetLastError());
     return BL_OK;
 }
 
@@ -368,7 +357,7 @@ int bl_partition_records128(bl_ctx* ctx, const uint64_t* d_hashes, const uint64_
     if (!ctx || !counts || parts == 0 || parts > MAX_PARTS || (n && (!d_hashes || !d_records || !d_out)))
         return bl_set_error(BL_ERR_INVALID, "bad argument (1 <= parts <= 64)");
     if (((uintptr_t)d_records | (uintptr_t)d_out) & 31u) return bl_set_error(BL_ERR_INVALID, "d_records and d_out must be 32-byte aligned");
-    SK_HIP(hipSetDevice(bl_ctx_device(ctx)));
+    BLH_TRY(hipSetDevice(bl_ctx_device(ctx)));
     unsigned long long host[MAX_PARTS];
     const hipError_t e = blpart::partition(reinterpret_cast<const Rec32*>(d_records), (unsigned long long)n, parts,
                                            HashArrayOwner{reinterpret_cast<const unsigned long long*>(d_hashes)}, reinterpret_cast<Rec32*>(d_out), host, bl_ctx_stream(ctx));
@@ -386,7 +375,7 @@ int bl_expand_super_kmers128(bl_ctx* ctx, const uint64_t* d_records, uint64_t n_
     if ((uintptr_t)d_kmers & 15u) return bl_set_error(BL_ERR_INVALID, "d_kmers must be 16-byte aligned");
     *n_kmers = 0;
     if (n_groups == 0) return BL_OK;
-    SK_HIP(hipSetDevice(bl_ctx_device(ctx)));
+    BLH_TRY(hipSetDevice(bl_ctx_device(ctx)));
     unsigned long long need = 0;
     const hipError_t e = expand128(ctx, reinterpret_cast<const Rec32*>(d_records), n_groups, (int)k, (flags & BL_FLAG_CANONICAL) ? 1 : 0,
                                    reinterpret_cast<unsigned long long*>(d_kmers), capacity, &need, bl_ctx_stream(ctx));
@@ -407,7 +396,7 @@ int bl_count_super_kmers128(bl_ctx* ctx, const uint64_t* d_records, uint64_t n_g
     const int canonical = (flags & BL_FLAG_CANONICAL) ? 1 : 0;
     *n_distinct = 0;
     if (n_groups == 0) return BL_OK;
-    SK_HIP(hipSetDevice(bl_ctx_device(ctx)));
+    BLH_TRY(hipSetDevice(bl_ctx_device(ctx)));
     hipStream_t s = bl_ctx_stream(ctx);
     const uint32_t n = (uint32_t)n_groups;
     const Rec32* recs = reinterpret_cast<const Rec32*>(d_records);
@@ -426,8 +415,8 @@ int bl_count_super_kmers128(bl_ctx* ctx, const uint64_t* d_records, uint64_t n_g
         if (runs > capacity || (!write && runs)) return bl_set_error(BL_ERR_CAPACITY, short_msg);
         if (runs) {
             hipLaunchKernelGGL(append_counted128_kernel, dim3((unsigned)((runs + 255) / 256)), dim3(256), 0, s, uniq, cnts, runs, out_keys, d_counts, 0ull);
-            SK_HIP(hipGetLastError());
-            SK_HIP(hipStreamSynchronize(s));
+            BLH_TRY(hipGetLastError());
+            BLH_TRY(hipStreamSynchronize(s));
         }
         return BL_OK;
     }

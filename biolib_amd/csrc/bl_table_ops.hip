@@ -12,18 +12,10 @@
 // bllk::finish_table (bl_lookup.hip): the prefix index is the build's.
 #include <hip/hip_runtime.h>
 
-#include <rocprim/device/device_scan.hpp>
-
-#include <new>
-
 #include "../../include/biolib_amd.h"
+#include "bl_host.hpp"
 #include "bl_lookup_launch.hpp"
 #include "bl_table_ops_core.hpp"
-
-extern int bl_set_error(int code, const char* msg);  // bl_capi.hip
-extern hipStream_t bl_ctx_stream(bl_ctx* ctx);
-extern int bl_ctx_device(bl_ctx* ctx);
-extern void* bl_ctx_scratch(bl_ctx* ctx, int slot, size_t bytes);  // slots 4-6 are the set operations': 4 data, 5 library workspace, 6 counters
 
 namespace {
 
@@ -134,7 +126,7 @@ __global__ __launch_bounds__(TPB) void table_write_kernel(const Tables in, const
     if (lane == 0 && wrote) atomicAdd(&counters[WRITTEN], (ull)wrote);
 }
 
-int hip_rc(hipError_t e) { return bl_set_error(e == hipErrorOutOfMemory ? BL_ERR_OOM : BL_ERR_HIP, hipGetErrorString(e)); }
+using blh::hip_rc;
 
 template <typename K>
 int combine(bl_ctx* ctx, const bl_table* ta, const bl_table* tb, const Rule& rule, bl_table** out, bl_table_stats* stats)
@@ -189,37 +181,16 @@ int combine(bl_ctx* ctx, const bl_table* ta, const bl_table* tb, const Rule& rul
     if (!out) return BL_OK;
     if (!fits_table(n_out, MAX_OUT)) return bl_set_error(BL_ERR_CAPACITY, "the result has 2^32 entries or more: a count table takes fewer");
 
-    bl_table* t = new (std::nothrow) bl_table{};
-    if (!t) return bl_set_error(BL_ERR_OOM, "out of host memory");
-    t->ctx = ctx;
-    t->device = bl_ctx_device(ctx);
-    t->view.key_words = ta->view.key_words;
-    t->view.key_bits = ta->view.key_bits;
-    t->view.n = (uint32_t)n_out;
+    bl_table* t = nullptr;
+    int rc = bllk::new_table(ctx, ta->view.key_words, ta->view.key_bits, n_out, &t);
+    if (rc != BL_OK) return rc;
     if (n_out) {
-        size_t scan_bytes = 0;
-        e = rocprim::exclusive_scan(nullptr, scan_bytes, totals, bases, 0ull, (size_t)n_tiles, rocprim::plus<ull>(), s);
-        void* ws = nullptr;
-        if (e == hipSuccess) {
-            ws = bl_ctx_scratch(ctx, 5, scan_bytes ? scan_bytes : 16);
-            if (!ws) e = hipErrorOutOfMemory;
-        }
-        void* keys = nullptr;
-        void* counts = nullptr;
-        if (e == hipSuccess) e = hipMalloc(&keys, (size_t)n_out * sizeof(K));
-        if (e == hipSuccess) {
-            t->view.keys = static_cast<uint64_t*>(keys);
-            e = hipMalloc(&counts, (size_t)n_out * sizeof(uint32_t));
-        }
-        if (e == hipSuccess) {
-            t->view.counts = static_cast<uint32_t*>(counts);
-            e = rocprim::exclusive_scan(ws, scan_bytes, totals, bases, 0ull, (size_t)n_tiles, rocprim::plus<ull>(), s);
-        }
-        if (e == hipSuccess) {
-            hipLaunchKernelGGL(table_write_kernel<K>, dim3((unsigned)n_tiles), dim3(TPB), 0, s, in, rule, splits, bases, n_out, static_cast<K*>(keys),
-                               static_cast<uint32_t*>(counts), d_counters);
-            e = hipGetLastError();
-        }
+        static_assert(sizeof(ull) == sizeof(uint64_t), "the tile totals are 8-byte words");
+        rc = blh::exclusive_sum(ctx, reinterpret_cast<const uint64_t*>(totals), reinterpret_cast<uint64_t*>(bases), (size_t)n_tiles, s);
+        if (rc != BL_OK) { bllk::free_table(t); return rc; }
+        hipLaunchKernelGGL(table_write_kernel<K>, dim3((unsigned)n_tiles), dim3(TPB), 0, s, in, rule, splits, bases, n_out,
+                           reinterpret_cast<K*>(const_cast<uint64_t*>(t->view.keys)), const_cast<uint32_t*>(t->view.counts), d_counters);
+        e = hipGetLastError();
         if (e == hipSuccess) e = hipMemcpyAsync(&host[WRITTEN], d_counters + WRITTEN, sizeof(ull), hipMemcpyDeviceToHost, s);
         if (e == hipSuccess) e = hipStreamSynchronize(s);
         if (e != hipSuccess) { bllk::free_table(t); return hip_rc(e); }
