@@ -203,7 +203,6 @@ def lib():
     L.bl_scan_minimizers.argtypes = [vp, vp, u64, u64, u32, u32, u64, u32, vp, vp, vp, u64, C.POINTER(Result)]
     L.bl_scan_hash_sample.argtypes = [vp, vp, u64, u64, u32, u64, u64, u32, vp, vp, vp, u64, C.POINTER(Result)]
     L.bl_sort_unique_u64.argtypes = [vp, vp, u64, C.POINTER(u64)]
-    L.bl_jaccard_sorted_u64.argtypes = [vp, vp, u64, vp, u64, C.POINTER(u64), C.POINTER(u64)]
     L.bl_pack_super_kmers.argtypes = [vp, vp, vp, vp, vp, u64, u32, u32, vp]
     L.bl_count_super_kmers.argtypes = [vp, vp, u64, u32, u32, u64, u32, vp, vp, u64, C.POINTER(u64)]
     L.bl_partition_records.argtypes = [vp, vp, vp, u64, u32, vp, vp]
@@ -212,9 +211,18 @@ def lib():
     L.bl_probe_hbm.argtypes = [vp, u64, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double)]
     L.bl_clock_probe_start.argtypes = [vp, u32, C.POINTER(vp)]
     L.bl_clock_probe_finish.argtypes = [vp, C.POINTER(C.c_double)]
-    L.bl_partition_u64.argtypes = [vp, vp, u64, u32, u64, vp, vp]
     L.bl_sort_u64.argtypes = [vp, vp, u64]
-    L.bl_count_sorted_u64.argtypes = [vp, vp, u64, vp, vp, C.POINTER(u64)]
+    for suffix in ("u64", "u128"):  # the key-list calls whose signature does not depend on the key's width
+        for name, argtypes in (("jaccard_sorted", [vp, vp, u64, vp, u64, C.POINTER(u64), C.POINTER(u64)]),
+                               ("partition", [vp, vp, u64, u32, u64, vp, vp]),
+                               ("count_sorted", [vp, vp, u64, vp, vp, C.POINTER(u64)]),
+                               ("write_run", [vp, vp, u64, C.c_char_p]),
+                               ("write_vector", [vp, vp, u64, C.c_char_p]),
+                               ("file_count", [C.c_char_p, C.c_int, C.POINTER(u64)]),
+                               ("read_file", [vp, C.c_char_p, C.c_int, vp, u64, C.POINTER(u64)]),
+                               ("merge_runs", [vp, C.POINTER(C.c_char_p), u32, vp, u64, C.POINTER(u64)])):
+            getattr(L, f"bl_{name}_{suffix}").argtypes = argtypes
+        getattr(L, f"bl_read_file_{suffix}_host").argtypes = [C.c_char_p, C.c_int, vp, u64, C.POINTER(u64)]
     L.bl_scan_super_kmers.argtypes = [vp, vp, u64, u64, u32, u32, u64, u32, vp, vp, vp, vp, vp, u64, C.POINTER(Result)]
     L.bl_scan_super_kmer_records.argtypes = [vp, vp, u64, u64, u32, u32, u64, u32, vp, vp, u64, C.POINTER(Result)]
     L.bl_scan_syncmers.argtypes = [vp, vp, u64, u64, u32, u32, u32, u32, u64, u32, vp, u64, C.POINTER(Result)]
@@ -236,10 +244,6 @@ def lib():
     L.bl_reader_kind.argtypes = [vp]
     L.bl_reader_next_text.argtypes = [vp, u64, C.POINTER(vp), C.POINTER(u64)]
     L.bl_reader_next_batch_device.argtypes = [vp, vp, u64, C.POINTER(vp), C.POINTER(u64), C.POINTER(u64)]
-    L.bl_file_count_u64.argtypes = [C.c_char_p, C.c_int, C.POINTER(u64)]
-    L.bl_read_file_u64_host.argtypes = [C.c_char_p, C.c_int, vp, u64, C.POINTER(u64)]
-    L.bl_read_file_u64.argtypes = [vp, C.c_char_p, C.c_int, vp, u64, C.POINTER(u64)]
-    L.bl_merge_runs_u64.argtypes = [vp, C.POINTER(C.c_char_p), u32, vp, u64, C.POINTER(u64)]
     L.bl_count_allreduce.argtypes = [C.POINTER(vp), C.c_int, C.POINTER(u64), C.c_int]
     L.bl_reader_next_record.argtypes = [vp, C.POINTER(C.c_char_p), C.POINTER(vp), C.POINTER(u64)]
     L.bl_reader_next_batch.argtypes = [vp, vp, u64, C.POINTER(vp), C.POINTER(u64), C.POINTER(u64)]
@@ -248,8 +252,6 @@ def lib():
     L.bl_reader_last_name.argtypes = [vp, u64]
     L.bl_batch_from_text.argtypes = [vp, vp, u64, C.POINTER(vp), C.POINTER(u64), C.POINTER(u64)]
     L.bl_run_file_name.argtypes = [C.c_char_p, C.c_char_p, u64, C.c_char_p, u64]
-    L.bl_write_run_u64.argtypes = [vp, vp, u64, C.c_char_p]
-    L.bl_write_vector_u64.argtypes = [vp, vp, u64, C.c_char_p]
     L.bl_device_alloc.argtypes = [vp, u64, C.POINTER(vp)]
     L.bl_device_free.argtypes = [vp, vp]
     L.bl_copy_to_host.argtypes = [vp, vp, vp, u64]
@@ -274,15 +276,6 @@ def lib():
     L.bl_count_super_kmers128.argtypes = [vp, vp, u64, u32, u32, u64, u32, vp, vp, u64, C.POINTER(u64)]
     L.bl_sort_u128.argtypes = [vp, vp, u64, u32]
     L.bl_sort_unique_u128.argtypes = [vp, vp, u64, u32, C.POINTER(u64)]
-    L.bl_count_sorted_u128.argtypes = [vp, vp, u64, vp, vp, C.POINTER(u64)]
-    L.bl_jaccard_sorted_u128.argtypes = [vp, vp, u64, vp, u64, C.POINTER(u64), C.POINTER(u64)]
-    L.bl_partition_u128.argtypes = [vp, vp, u64, u32, u64, vp, vp]
-    L.bl_write_run_u128.argtypes = [vp, vp, u64, C.c_char_p]
-    L.bl_write_vector_u128.argtypes = [vp, vp, u64, C.c_char_p]
-    L.bl_file_count_u128.argtypes = [C.c_char_p, C.c_int, C.POINTER(u64)]
-    L.bl_read_file_u128_host.argtypes = [C.c_char_p, C.c_int, vp, u64, C.POINTER(u64)]
-    L.bl_read_file_u128.argtypes = [vp, C.c_char_p, C.c_int, vp, u64, C.POINTER(u64)]
-    L.bl_merge_runs_u128.argtypes = [vp, C.POINTER(C.c_char_p), u32, vp, u64, C.POINTER(u64)]
     L.bl_hash64_u128.restype = u64
     L.bl_hash64_u128.argtypes = [u64, u64, u64]
     if "BIOLIB_AMD_LIB" not in os.environ or hasattr(L, "bl_table_build_u64"):  # (an A/B build of an older revision lacks them)

@@ -10,12 +10,9 @@ namespace blh {
 
 int exclusive_sum(bl_ctx* ctx, const uint64_t* in, uint64_t* out, size_t n, hipStream_t s)
 {
-    size_t bytes = 0;
-    BLH_TRY(rocprim::exclusive_scan(nullptr, bytes, in, out, (uint64_t)0, n, rocprim::plus<uint64_t>(), s));
-    void* tmp = bl_ctx_scratch(ctx, 5, bytes ? bytes : 16);
-    if (!tmp) return bl_set_error(BL_ERR_OOM, "scratch allocation failed");
-    BLH_TRY(rocprim::exclusive_scan(tmp, bytes, in, out, (uint64_t)0, n, rocprim::plus<uint64_t>(), s));
-    return BL_OK;
+    const hipError_t e = with_workspace(ctx, 5, [&](void* ws, size_t& bytes) { return rocprim::exclusive_scan(ws, bytes, in, out, (uint64_t)0, n, rocprim::plus<uint64_t>(), s); });
+    if (e == hipErrorOutOfMemory) return bl_set_error(BL_ERR_OOM, "scratch allocation failed");
+    return e == hipSuccess ? BL_OK : hip_rc(e);
 }
 
 }  // namespace blh

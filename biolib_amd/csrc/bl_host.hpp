@@ -24,9 +24,10 @@ int bl_ctx_table_prefix_bits(bl_ctx* ctx);  // the "table_prefix_bits" option
 //   0      candidates                                  bl_correct
 //   0-3    arenas, library workspace, keys, counts,    the k-mer counters (bl_superkmer*.hip; the 128-bit one keeps its run count in 7) and
 //          the text (3)                                the text parser, which call the set operations while they hold them
-//   4      data                                        the set operations, the table build and algebra, the quantiles, select, format,
-//   5      library workspace (rocPRIM):                the corrector, the graph (about 133 bytes per key in slot 4), links and clean:
-//          blh::exclusive_sum takes it                 none of them calls another while it holds 4-6
+//   4      data; blpart::partition's histogram,        the set operations (bl_keylist.hpp), the owner splits, the table build and algebra, the
+//          offsets and bucket starts                   quantiles, select, format, the corrector, the graph (about 133 bytes per key in slot 4),
+//   5      library workspace (rocPRIM):                links and clean: none of them calls another while it holds 4-6
+//          blh::exclusive_sum takes it
 //   6      counters, flags, statistics
 void* bl_ctx_scratch(bl_ctx* ctx, int slot, size_t bytes);
 
@@ -85,6 +86,19 @@ private:
     bl_ctx* ctx_ = nullptr;
     T* p_ = nullptr;
 };
+
+// The two calls of a rocPRIM device primitive: call(nullptr, bytes) asks for the size; the workspace is scratch `slot`; call(ws, bytes)
+// runs.  hipErrorOutOfMemory if the slot cannot grow.  Two primitives of one entry point may take the same slot one after the other
+// without a wait in between: a slot only grows, and bl_ctx_scratch synchronises the device before it replaces the block.
+template <typename F>
+hipError_t with_workspace(bl_ctx* ctx, int slot, F&& call)
+{
+    size_t bytes = 0;
+    const hipError_t e = call(static_cast<void*>(nullptr), bytes);
+    if (e != hipSuccess) return e;
+    void* ws = bl_ctx_scratch(ctx, slot, bytes ? bytes : 16);
+    return ws ? call(ws, bytes) : hipErrorOutOfMemory;
+}
 
 // Exclusive sum of n 8-byte words on `stream` (rocPRIM; its workspace is scratch slot 5, which a second sum on the same stream may take
 // again at once).  Defined in bl_host.hip: the library's one instantiation of that scan.

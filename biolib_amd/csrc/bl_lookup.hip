@@ -212,21 +212,15 @@ int build(bl_ctx* ctx, const uint64_t* d_keys, const uint32_t* d_counts, uint64_
         merged_c = reinterpret_cast<uint32_t*>(data + 2 * kb + cb);
         const KeyT* in = reinterpret_cast<const KeyT*>(d_keys);
         const rocprim::constant_iterator<uint32_t> ones(1u);
-        size_t sort_bytes = 0, reduce_bytes = 0;
-        if (d_counts) e = rocprim::radix_sort_pairs(nullptr, sort_bytes, in, sorted, d_counts, sorted_c, (size_t)n, 0u, key_bits, s);
-        else e = rocprim::radix_sort_pairs(nullptr, sort_bytes, in, sorted, ones, sorted_c, (size_t)n, 0u, key_bits, s);
-        if (e == hipSuccess) e = rocprim::reduce_by_key(nullptr, reduce_bytes, sorted, sorted_c, (size_t)n, merged, merged_c, d_words + 2, SatAdd(), rocprim::equal_to<KeyT>(), s);
-        void* ws = nullptr;
-        if (e == hipSuccess) {
-            const size_t need = sort_bytes > reduce_bytes ? sort_bytes : reduce_bytes;
-            ws = bl_ctx_scratch(ctx, 5, need ? need : 16);  // one block for both: the stream orders them
-            if (!ws) e = hipErrorOutOfMemory;
-        }
-        if (e == hipSuccess) {
-            if (d_counts) e = rocprim::radix_sort_pairs(ws, sort_bytes, in, sorted, d_counts, sorted_c, (size_t)n, 0u, key_bits, s);
-            else e = rocprim::radix_sort_pairs(ws, sort_bytes, in, sorted, ones, sorted_c, (size_t)n, 0u, key_bits, s);
-        }
-        if (e == hipSuccess) e = rocprim::reduce_by_key(ws, reduce_bytes, sorted, sorted_c, (size_t)n, merged, merged_c, d_words + 2, SatAdd(), rocprim::equal_to<KeyT>(), s);
+        // slot 5 for both, one after the other: the stream orders them
+        e = blh::with_workspace(ctx, 5, [&](void* ws, size_t& bytes) {
+            if (d_counts) return rocprim::radix_sort_pairs(ws, bytes, in, sorted, d_counts, sorted_c, (size_t)n, 0u, key_bits, s);
+            return rocprim::radix_sort_pairs(ws, bytes, in, sorted, ones, sorted_c, (size_t)n, 0u, key_bits, s);
+        });
+        if (e == hipSuccess)
+            e = blh::with_workspace(ctx, 5, [&](void* ws, size_t& bytes) {
+                return rocprim::reduce_by_key(ws, bytes, sorted, sorted_c, (size_t)n, merged, merged_c, d_words + 2, SatAdd(), rocprim::equal_to<KeyT>(), s);
+            });
         if (e == hipSuccess) e = hipMemcpyAsync(&distinct, d_words + 2, sizeof(ull), hipMemcpyDeviceToHost, s);
         if (e == hipSuccess) e = hipStreamSynchronize(s);
         if (e != hipSuccess) return hip_rc(e);

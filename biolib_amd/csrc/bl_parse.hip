@@ -178,7 +178,6 @@ int bl_parse_device_text_lines(bl_ctx* ctx, const uint8_t* d_text_in, uint64_t n
     const uint8_t* d_text = nullptr;
     unsigned long long *d_blk = nullptr, *d_line_end = nullptr, *d_len = nullptr, *d_hdr = nullptr, *d_rec = nullptr, *d_dst = nullptr;
     unsigned int* d_err = nullptr;
-    void* d_tmp = nullptr;
     blh::Pooled<uint8_t> d_bases;  // the outputs go on every exit path unless adopted ...
     blh::Pooled<unsigned long long> d_offsets;
     Drain drain{s};  // ... behind the wait for the stream (declared last: it goes first)
@@ -198,14 +197,15 @@ int bl_parse_device_text_lines(bl_ctx* ctx, const uint8_t* d_text_in, uint64_t n
     BLH_TRY(hipMemsetAsync(d_err, 0, sizeof(unsigned int), s));
     hipLaunchKernelGGL(count_newlines_kernel, dim3(n_blocks), dim3(PB), 0, s, d_text, n, d_blk);
 
-    // scans: one scratch buffer sized for the largest of them (n_lines <= n)
-    size_t tmp_bytes = 0, need = 0;
-    BLH_TRY(rocprim::exclusive_scan(nullptr, need, d_blk, d_blk_base, 0ull, (size_t)n_blocks + 1, rocprim::plus<unsigned long long>(), s));
-    tmp_bytes = need;
-    // the other two scans run over n_lines <= n_blocks * BYTES_PER_BLOCK items; their workspace is asked for again below
-    d_tmp = bl_ctx_scratch(ctx, 2, tmp_bytes ? tmp_bytes : 16);
-    if (!d_tmp) return bl_set_error(BL_ERR_OOM, "device allocation failed (scan scratch)");
-    BLH_TRY(rocprim::exclusive_scan(d_tmp, tmp_bytes, d_blk, d_blk_base, 0ull, (size_t)n_blocks + 1, rocprim::plus<unsigned long long>(), s));
+    // the three scans: each takes its workspace from slot 2 (which grows with the largest of them)
+    auto scan = [&](auto&& call) {
+        const hipError_t e = blh::with_workspace(ctx, 2, call);
+        if (e == hipErrorOutOfMemory) return bl_set_error(BL_ERR_OOM, "device allocation failed (scan scratch)");
+        return e == hipSuccess ? (int)BL_OK : blh::hip_rc(e);
+    };
+    const rocprim::plus<unsigned long long> plus;
+    int rc = scan([&](void* ws, size_t& bytes) { return rocprim::exclusive_scan(ws, bytes, d_blk, d_blk_base, 0ull, (size_t)n_blocks + 1, plus, s); });
+    if (rc != BL_OK) return rc;
     unsigned long long n_newlines = 0;
     BLH_TRY(hipMemcpyAsync(&n_newlines, d_blk_base + n_blocks, sizeof(n_newlines), hipMemcpyDeviceToHost, s));
     BLH_TRY(hipStreamSynchronize(s));
@@ -238,23 +238,11 @@ int bl_parse_device_text_lines(bl_ctx* ctx, const uint8_t* d_text_in, uint64_t n
     const unsigned lb = (unsigned)((n_lines + 255) / 256);
     hipLaunchKernelGGL(classify_lines_kernel, dim3(lb), dim3(256), 0, s, d_text, d_line_end, n_lines, fastq ? 1 : 0, d_len, d_hdr, d_err);
 
-    BLH_TRY(rocprim::inclusive_scan(nullptr, need, d_hdr, d_rec, (size_t)n_lines, rocprim::plus<unsigned long long>(), s));
-    if (need > tmp_bytes) {
-        BLH_TRY(hipStreamSynchronize(s));
-        tmp_bytes = need;
-        d_tmp = bl_ctx_scratch(ctx, 2, tmp_bytes);
-        if (!d_tmp) return bl_set_error(BL_ERR_OOM, "device allocation failed (scan scratch)");
-    }
-    BLH_TRY(rocprim::inclusive_scan(d_tmp, need, d_hdr, d_rec, (size_t)n_lines, rocprim::plus<unsigned long long>(), s));
+    rc = scan([&](void* ws, size_t& bytes) { return rocprim::inclusive_scan(ws, bytes, d_hdr, d_rec, (size_t)n_lines, plus, s); });
+    if (rc != BL_OK) return rc;
     if (!fastq) hipLaunchKernelGGL(mask_leading_lines_kernel, dim3(lb), dim3(256), 0, s, d_rec, d_len, n_lines);
-    BLH_TRY(rocprim::exclusive_scan(nullptr, need, d_len, d_dst, 0ull, (size_t)n_lines + 1, rocprim::plus<unsigned long long>(), s));
-    if (need > tmp_bytes) {
-        BLH_TRY(hipStreamSynchronize(s));
-        tmp_bytes = need;
-        d_tmp = bl_ctx_scratch(ctx, 2, tmp_bytes);
-        if (!d_tmp) return bl_set_error(BL_ERR_OOM, "device allocation failed (scan scratch)");
-    }
-    BLH_TRY(rocprim::exclusive_scan(d_tmp, need, d_len, d_dst, 0ull, (size_t)n_lines + 1, rocprim::plus<unsigned long long>(), s));
+    rc = scan([&](void* ws, size_t& bytes) { return rocprim::exclusive_scan(ws, bytes, d_len, d_dst, 0ull, (size_t)n_lines + 1, plus, s); });
+    if (rc != BL_OK) return rc;
 
     unsigned long long total = 0, n_records = 0;
     unsigned int err = 0;
@@ -293,7 +281,7 @@ int bl_parse_device_text_lines(bl_ctx* ctx, const uint8_t* d_text_in, uint64_t n
     if (ragged) fixed_len = 0;
     drain.now();
     if (lines) *lines = bl_parse::LineIndex{d_line_end, d_hdr, d_rec, d_dst, n_lines, n_records, total, fastq ? 1 : 0};
-    int rc = bl_batch_adopt_device(ctx, d_bases.release(), total, reinterpret_cast<uint64_t*>(d_offsets.release()), n_records, fixed_len, out);  // takes ownership of both
+    rc = bl_batch_adopt_device(ctx, d_bases.release(), total, reinterpret_cast<uint64_t*>(d_offsets.release()), n_records, fixed_len, out);  // takes ownership of both
     if (rc != BL_OK) return rc;
     if (n_seqs) *n_seqs = n_records;
     if (n_bases) *n_bases = total;

@@ -7,7 +7,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
-#include <rocprim/device/device_scan.hpp>
+#include "bl_host.hpp"
 
 namespace blpart {
 
@@ -65,38 +65,29 @@ static __global__ void starts_kernel(const unsigned long long* offset, unsigned 
     if (b == parts) starts[b] = n;
 }
 
-// counts: host array of `parts` entries.  Returns a hipError_t.
+// counts: host array of `parts` entries.  Scratch slot 4 holds the histogram, the offsets and the bucket starts, slot 5 the workspace of
+// the scan (blh::exclusive_sum): the caller holds neither.  Returns a BL_* code.
 template <typename T, typename Owner>
-hipError_t partition(const T* d_src, unsigned long long n, uint32_t parts, Owner owner, T* d_dst, unsigned long long* counts, hipStream_t s)
+int partition(bl_ctx* ctx, const T* d_src, unsigned long long n, uint32_t parts, Owner owner, T* d_dst, uint64_t* counts, hipStream_t s)
 {
     for (uint32_t b = 0; b < parts; ++b) counts[b] = 0;
-    if (n == 0) return hipSuccess;
+    if (n == 0) return BL_OK;
     const unsigned long long n_blocks = (n + CHUNK - 1) / CHUNK;
     const size_t cells = (size_t)parts * n_blocks;
-    unsigned long long *d_hist = nullptr, *d_off = nullptr, *d_starts = nullptr;
-    void* d_tmp = nullptr;
-    size_t tmp_bytes = 0;
-    hipError_t e = hipMalloc(&d_hist, (2 * cells + MAX_PARTS + 1) * sizeof(unsigned long long));
-    if (e != hipSuccess) return e;
-    d_off = d_hist + cells;
-    d_starts = d_off + cells;
+    unsigned long long* d_hist = static_cast<unsigned long long*>(bl_ctx_scratch(ctx, 4, (2 * cells + MAX_PARTS + 1) * sizeof(unsigned long long)));
+    if (!d_hist) return blh::hip_rc(hipErrorOutOfMemory);
+    unsigned long long *d_off = d_hist + cells, *d_starts = d_off + cells;
     hipLaunchKernelGGL((hist_kernel<Owner>), dim3((unsigned)n_blocks), dim3(PT), 0, s, owner, n, parts, n_blocks, d_hist);
-    e = rocprim::exclusive_scan(nullptr, tmp_bytes, d_hist, d_off, 0ull, cells, rocprim::plus<unsigned long long>(), s);
-    if (e == hipSuccess) e = hipMalloc(&d_tmp, tmp_bytes ? tmp_bytes : 16);
-    if (e == hipSuccess) e = rocprim::exclusive_scan(d_tmp, tmp_bytes, d_hist, d_off, 0ull, cells, rocprim::plus<unsigned long long>(), s);
-    if (e == hipSuccess) {
-        hipLaunchKernelGGL((scatter_kernel<T, Owner>), dim3((unsigned)n_blocks), dim3(PT), 0, s, d_src, owner, n, parts, n_blocks, d_off, d_dst);
-        hipLaunchKernelGGL(starts_kernel, dim3(1), dim3(MAX_PARTS + 1), 0, s, d_off, n_blocks, parts, n, d_starts);
-        e = hipGetLastError();
-    }
+    const int rc = blh::exclusive_sum(ctx, reinterpret_cast<const uint64_t*>(d_hist), reinterpret_cast<uint64_t*>(d_off), cells, s);
+    if (rc != BL_OK) return rc;
+    hipLaunchKernelGGL((scatter_kernel<T, Owner>), dim3((unsigned)n_blocks), dim3(PT), 0, s, d_src, owner, n, parts, n_blocks, d_off, d_dst);
+    hipLaunchKernelGGL(starts_kernel, dim3(1), dim3(MAX_PARTS + 1), 0, s, d_off, n_blocks, parts, n, d_starts);
+    BLH_TRY(hipGetLastError());
     unsigned long long starts[MAX_PARTS + 1] = {0};
-    if (e == hipSuccess) e = hipMemcpyAsync(starts, d_starts, (parts + 1) * sizeof(unsigned long long), hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess) e = hipStreamSynchronize(s);
-    (void)hipFree(d_hist);
-    if (d_tmp) (void)hipFree(d_tmp);
-    if (e != hipSuccess) return e;
+    BLH_TRY(hipMemcpyAsync(starts, d_starts, (parts + 1) * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
+    BLH_TRY(hipStreamSynchronize(s));
     for (uint32_t b = 0; b < parts; ++b) counts[b] = starts[b + 1] - starts[b];
-    return hipSuccess;
+    return BL_OK;
 }
 
 }  // namespace blpart

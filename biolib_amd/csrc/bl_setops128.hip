@@ -1,8 +1,8 @@
 // bl_setops128.hip — the consumer side of the pipeline for 16-byte keys (k-mers of 33 <= k <= 64, kmer_view<__uint128_t>): sort,
 // unique, run-length count, owner split, the device half of the run-file calls, and the sizes of intersection / union of two sorted
-// unique sets.  As in bl_setops.hip the sort, the unique, the run-length count and the pairwise merge of runs are rocPRIM device
-// primitives on __uint128_t (library plumbing), the owner split is blpart::partition with a 16-byte element.  Hand-written: the two
-// intersection kernels, whose per-thread bodies live in bl_setops128_core.hpp —
+// unique sets.  As in bl_setops.hip the host bodies are bl_keylist.hpp's, instantiated here for __uint128_t (rocPRIM device
+// primitives: library plumbing); the owner split is blpart::partition with a 16-byte element.  Hand-written: the two intersection
+// kernels, whose per-thread bodies live in bl_setops128_core.hpp —
 //   merge kernel    merge path: one thread per tile boundary finds the tile's split in global memory (merge_partition_kernel); one
 //                   workgroup per tile of 2048 merged elements stages its A range and its B range plus ONE more B element in LDS with
 //                   16-byte accesses, every thread merges 8 elements from its own diagonal and counts the equal pairs
@@ -12,17 +12,9 @@
 // The context option "jaccard128_path" forces one of them (1 merge, 2 search); 0 chooses by the size ratio (bl128s::choose_merge).
 #include <hip/hip_runtime.h>
 
-#include <rocprim/device/device_merge.hpp>
-#include <rocprim/device/device_radix_sort.hpp>
-#include <rocprim/device/device_run_length_encode.hpp>
-#include <rocprim/device/device_select.hpp>
-
-#include <vector>
-
 #include "../../include/biolib_amd.h"
-#include "bl_host.hpp"
+#include "bl_keylist.hpp"
 #include "bl_kmers128_core.hpp"
-#include "bl_partition.hpp"
 #include "bl_setops128_core.hpp"
 
 namespace {
@@ -87,19 +79,12 @@ struct Key128HashOwner {
 };
 
 using blh::hip_rc;
-bool misaligned(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) != 0; }
-int bad_alignment() { return bl_set_error(BL_ERR_INVALID, "arrays of 16-byte keys must be 16-byte aligned"); }
+using blkeys::bad_alignment;
+using blkeys::misaligned;
 
-// keys[0 .. n) -> sorted[0 .. n) over the bits [0, key_bits).  Scratch slot 5.
-hipError_t sort128(bl_ctx* ctx, __uint128_t* keys, __uint128_t* sorted, ull n, uint32_t key_bits, hipStream_t s)
-{
-    size_t bytes = 0;
-    hipError_t e = rocprim::radix_sort_keys(nullptr, bytes, keys, sorted, (size_t)n, 0u, key_bits, s);
-    if (e != hipSuccess) return e;
-    void* tmp = bl_ctx_scratch(ctx, 5, bytes ? bytes : 16);
-    if (!tmp) return hipErrorOutOfMemory;
-    return rocprim::radix_sort_keys(tmp, bytes, keys, sorted, (size_t)n, 0u, key_bits, s);
-}
+int bad_key_bits() { return bl_set_error(BL_ERR_INVALID, "bad argument (1 <= key_bits <= 128)"); }
+__uint128_t* as_keys(uint64_t* p) { return reinterpret_cast<__uint128_t*>(p); }
+const __uint128_t* as_keys(const uint64_t* p) { return reinterpret_cast<const __uint128_t*>(p); }
 
 }  // namespace
 
@@ -107,49 +92,19 @@ extern "C" {
 
 int bl_sort_u128(bl_ctx* ctx, uint64_t* d_keys, uint64_t n, uint32_t key_bits)
 {
-    if (!ctx || (n && !d_keys) || key_bits < 1 || key_bits > 128) return bl_set_error(BL_ERR_INVALID, "bad argument (1 <= key_bits <= 128)");
+    if (!ctx || (n && !d_keys) || key_bits < 1 || key_bits > 128) return bad_key_bits();
     if (n == 0) return BL_OK;
     if (misaligned(d_keys)) return bad_alignment();
-    hipError_t e = hipSetDevice(bl_ctx_device(ctx));
-    if (e != hipSuccess) return hip_rc(e);
-    hipStream_t s = bl_ctx_stream(ctx);
-    __uint128_t* keys = reinterpret_cast<__uint128_t*>(d_keys);
-    __uint128_t* tmp = static_cast<__uint128_t*>(bl_ctx_scratch(ctx, 4, n * sizeof(__uint128_t)));
-    if (!tmp) return bl_set_error(BL_ERR_OOM, "scratch allocation failed");
-    e = sort128(ctx, keys, tmp, n, key_bits, s);
-    if (e == hipSuccess) e = hipMemcpyAsync(keys, tmp, n * sizeof(__uint128_t), hipMemcpyDeviceToDevice, s);
-    if (e == hipSuccess) e = hipStreamSynchronize(s);
-    return e == hipSuccess ? BL_OK : hip_rc(e);
+    return blkeys::sort_keys(ctx, as_keys(d_keys), n, key_bits);
 }
 
 int bl_sort_unique_u128(bl_ctx* ctx, uint64_t* d_keys, uint64_t n, uint32_t key_bits, uint64_t* n_unique)
 {
-    if (!ctx || !n_unique || (n && !d_keys) || key_bits < 1 || key_bits > 128) return bl_set_error(BL_ERR_INVALID, "bad argument (1 <= key_bits <= 128)");
+    if (!ctx || !n_unique || (n && !d_keys) || key_bits < 1 || key_bits > 128) return bad_key_bits();
     *n_unique = 0;
     if (n == 0) return BL_OK;
     if (misaligned(d_keys)) return bad_alignment();
-    hipError_t e = hipSetDevice(bl_ctx_device(ctx));
-    if (e != hipSuccess) return hip_rc(e);
-    hipStream_t s = bl_ctx_stream(ctx);
-    __uint128_t* keys = reinterpret_cast<__uint128_t*>(d_keys);
-    __uint128_t* tmp = static_cast<__uint128_t*>(bl_ctx_scratch(ctx, 4, n * sizeof(__uint128_t)));
-    ull* d_count = static_cast<ull*>(bl_ctx_scratch(ctx, 6, 64));
-    if (!tmp || !d_count) return bl_set_error(BL_ERR_OOM, "scratch allocation failed");
-    e = sort128(ctx, keys, tmp, n, key_bits, s);  // keys -> tmp (sorted)
-    size_t bytes = 0;
-    if (e == hipSuccess) e = rocprim::unique(nullptr, bytes, tmp, keys, d_count, (size_t)n, rocprim::equal_to<__uint128_t>(), s);
-    void* ws = nullptr;
-    if (e == hipSuccess) {
-        ws = bl_ctx_scratch(ctx, 5, bytes ? bytes : 16);  // (the sort's use of the slot is ordered in front of this one by the stream)
-        if (!ws) e = hipErrorOutOfMemory;
-    }
-    if (e == hipSuccess) e = rocprim::unique(ws, bytes, tmp, keys, d_count, (size_t)n, rocprim::equal_to<__uint128_t>(), s);  // tmp -> keys
-    ull cnt = 0;
-    if (e == hipSuccess) e = hipMemcpyAsync(&cnt, d_count, sizeof(cnt), hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess) e = hipStreamSynchronize(s);
-    if (e != hipSuccess) return hip_rc(e);
-    *n_unique = cnt;
-    return BL_OK;
+    return blkeys::sort_unique(ctx, as_keys(d_keys), n, key_bits, n_unique);
 }
 
 int bl_count_sorted_u128(bl_ctx* ctx, const uint64_t* d_sorted, uint64_t n, uint64_t* d_unique, uint32_t* d_counts, uint64_t* n_unique)
@@ -158,28 +113,7 @@ int bl_count_sorted_u128(bl_ctx* ctx, const uint64_t* d_sorted, uint64_t n, uint
     *n_unique = 0;
     if (n == 0) return BL_OK;
     if (misaligned(d_sorted) || misaligned(d_unique)) return bad_alignment();
-    if (n >= (1ull << 32)) return bl_set_error(BL_ERR_INVALID, "bl_count_sorted_u128 takes fewer than 2^32 keys");  // (run_length_encode's size is 32 bits)
-    hipError_t e = hipSetDevice(bl_ctx_device(ctx));
-    if (e != hipSuccess) return hip_rc(e);
-    hipStream_t s = bl_ctx_stream(ctx);
-    const __uint128_t* sorted = reinterpret_cast<const __uint128_t*>(d_sorted);
-    __uint128_t* uniq = reinterpret_cast<__uint128_t*>(d_unique);
-    ull* d_runs = static_cast<ull*>(bl_ctx_scratch(ctx, 6, 64));
-    if (!d_runs) return bl_set_error(BL_ERR_OOM, "scratch allocation failed");
-    size_t bytes = 0;
-    void* tmp = nullptr;
-    e = rocprim::run_length_encode(nullptr, bytes, sorted, (unsigned int)n, uniq, d_counts, d_runs, s);
-    if (e == hipSuccess) {
-        tmp = bl_ctx_scratch(ctx, 5, bytes ? bytes : 16);
-        if (!tmp) e = hipErrorOutOfMemory;
-    }
-    if (e == hipSuccess) e = rocprim::run_length_encode(tmp, bytes, sorted, (unsigned int)n, uniq, d_counts, d_runs, s);
-    ull runs = 0;
-    if (e == hipSuccess) e = hipMemcpyAsync(&runs, d_runs, sizeof(runs), hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess) e = hipStreamSynchronize(s);
-    if (e != hipSuccess) return hip_rc(e);
-    *n_unique = runs;
-    return BL_OK;
+    return blkeys::count_sorted(ctx, as_keys(d_sorted), n, as_keys(d_unique), d_counts, n_unique);
 }
 
 int bl_jaccard_sorted_u128(bl_ctx* ctx, const uint64_t* d_a, uint64_t na, const uint64_t* d_b, uint64_t nb, uint64_t* intersection, uint64_t* union_size)
@@ -220,8 +154,7 @@ int bl_jaccard_sorted_u128(bl_ctx* ctx, const uint64_t* d_a, uint64_t na, const 
         e = hipGetLastError();
     }
     ull inter = 0;
-    if (e == hipSuccess) e = hipMemcpyAsync(&inter, d_out, sizeof(inter), hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess) e = hipStreamSynchronize(s);
+    if (e == hipSuccess) e = blkeys::read_counter(d_out, s, &inter);
     if (e != hipSuccess) return hip_rc(e);
     *intersection = inter;
     *union_size = na + nb - inter;
@@ -232,96 +165,20 @@ int bl_partition_u128(bl_ctx* ctx, const uint64_t* d_keys, uint64_t n, uint32_t 
 {
     if (!ctx || !counts || parts == 0 || parts > blpart::MAX_PARTS || (n && (!d_keys || !d_out))) return bl_set_error(BL_ERR_INVALID, "bad argument (1 <= parts <= 64)");
     if (n && (misaligned(d_keys) || misaligned(d_out))) return bad_alignment();
-    hipError_t e = hipSetDevice(bl_ctx_device(ctx));
-    if (e != hipSuccess) return hip_rc(e);
     const Key* keys = reinterpret_cast<const Key*>(d_keys);
-    ull host[blpart::MAX_PARTS];
-    e = blpart::partition(keys, (ull)n, parts, Key128HashOwner{keys, (uint32_t)seed}, reinterpret_cast<Key*>(d_out), host, bl_ctx_stream(ctx));
-    if (e != hipSuccess) return hip_rc(e);
-    for (uint32_t b = 0; b < parts; ++b) counts[b] = host[b];
-    return BL_OK;
+    return blkeys::partition_keys(ctx, keys, n, parts, Key128HashOwner{keys, (uint32_t)seed}, reinterpret_cast<Key*>(d_out), counts);
 }
 
 int bl_read_file_u128(bl_ctx* ctx, const char* path, int with_count, uint64_t* d_out, uint64_t capacity, uint64_t* n)
 {
     if (!ctx || !path) return bl_set_error(BL_ERR_INVALID, "NULL argument");
-    uint64_t cnt = 0;
-    int rc = bl_file_count_u128(path, with_count, &cnt);
-    if (rc != BL_OK) return rc;
-    if (n) *n = cnt;
-    if (cnt > capacity) return bl_set_error(BL_ERR_CAPACITY, "device array too small for the file");
-    if (cnt == 0) return BL_OK;
-    if (!d_out) return bl_set_error(BL_ERR_INVALID, "NULL argument");
-    if (misaligned(d_out)) return bad_alignment();
-    std::vector<uint64_t> host(2 * cnt);
-    rc = bl_read_file_u128_host(path, with_count, host.data(), cnt, nullptr);
-    if (rc != BL_OK) return rc;
-    hipError_t e = hipSetDevice(bl_ctx_device(ctx));
-    hipStream_t s = bl_ctx_stream(ctx);
-    if (e == hipSuccess) e = hipMemcpyAsync(d_out, host.data(), cnt * 16, hipMemcpyHostToDevice, s);
-    if (e == hipSuccess) e = hipStreamSynchronize(s);  // `host` goes away
-    return e == hipSuccess ? BL_OK : hip_rc(e);
+    return blkeys::read_file(ctx, path, with_count, as_keys(d_out), capacity, n);
 }
 
 int bl_merge_runs_u128(bl_ctx* ctx, const char* const* paths, uint32_t n_paths, uint64_t* d_out, uint64_t capacity, uint64_t* n_total)
 {
     if (!ctx || (n_paths && !paths) || !n_total) return bl_set_error(BL_ERR_INVALID, "NULL argument");
-    std::vector<uint64_t> len(n_paths), off(n_paths + 1, 0);
-    for (uint32_t i = 0; i < n_paths; ++i) {
-        int rc = bl_file_count_u128(paths[i], 0, &len[i]);
-        if (rc != BL_OK) return rc;
-        off[i + 1] = off[i] + len[i];
-    }
-    const uint64_t total = off[n_paths];
-    *n_total = total;
-    if (total > capacity) return bl_set_error(BL_ERR_CAPACITY, "device array too small for the merged runs");
-    if (total == 0) return BL_OK;
-    if (!d_out) return bl_set_error(BL_ERR_INVALID, "NULL argument");
-    if (misaligned(d_out)) return bad_alignment();
-    for (uint32_t i = 0; i < n_paths; ++i) {
-        int rc = bl_read_file_u128(ctx, paths[i], 0, d_out + 2 * off[i], len[i], nullptr);
-        if (rc != BL_OK) return rc;
-    }
-    hipError_t e = hipSetDevice(bl_ctx_device(ctx));
-    if (e != hipSuccess) return hip_rc(e);
-    hipStream_t s = bl_ctx_stream(ctx);
-    // runs = [cur[i], cur[i+1]); merge neighbours pairwise, ping-ponging between d_out and the scratch array
-    __uint128_t* a = reinterpret_cast<__uint128_t*>(d_out);
-    __uint128_t* b = nullptr;
-    std::vector<uint64_t> cur(off);
-    bool in_a = true;
-    while (cur.size() > 2 && e == hipSuccess) {
-        if (!b) {
-            b = static_cast<__uint128_t*>(bl_ctx_scratch(ctx, 4, total * sizeof(__uint128_t)));
-            if (!b) return bl_set_error(BL_ERR_OOM, "scratch allocation failed");
-        }
-        __uint128_t* src = in_a ? a : b;
-        __uint128_t* dst = in_a ? b : a;
-        std::vector<uint64_t> next(1, 0);
-        for (size_t i = 0; i + 1 < cur.size() && e == hipSuccess; i += 2) {
-            const uint64_t lo = cur[i], mid = cur[i + 1], hi = i + 2 < cur.size() ? cur[i + 2] : cur[i + 1];
-            if (hi == mid) {  // odd run out: copied through
-                if (mid > lo) e = hipMemcpyAsync(dst + lo, src + lo, (mid - lo) * sizeof(__uint128_t), hipMemcpyDeviceToDevice, s);
-            } else {
-                size_t need = 0;
-                e = rocprim::merge(nullptr, need, src + lo, src + mid, dst + lo, mid - lo, hi - mid, rocprim::less<__uint128_t>(), s);
-                void* tmp = nullptr;
-                if (e == hipSuccess) {
-                    // the slot only grows, and growing it synchronises the device first: the merges in flight are done with the old block
-                    tmp = bl_ctx_scratch(ctx, 5, need ? need : 16);
-                    if (!tmp) e = hipErrorOutOfMemory;
-                }
-                if (e == hipSuccess) e = rocprim::merge(tmp, need, src + lo, src + mid, dst + lo, mid - lo, hi - mid, rocprim::less<__uint128_t>(), s);
-            }
-            next.push_back(hi);
-        }
-        cur.swap(next);
-        in_a = !in_a;
-    }
-    if (e == hipSuccess && !in_a) e = hipMemcpyAsync(a, b, total * sizeof(__uint128_t), hipMemcpyDeviceToDevice, s);
-    const hipError_t se = hipStreamSynchronize(s);
-    if (e == hipSuccess) e = se;
-    return e == hipSuccess ? BL_OK : hip_rc(e);
+    return blkeys::merge_runs(ctx, paths, n_paths, as_keys(d_out), capacity, n_total);
 }
 
 }  // extern "C"

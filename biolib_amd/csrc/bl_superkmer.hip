@@ -629,13 +629,8 @@ int bl_partition_records(bl_ctx* ctx, const uint64_t* d_hashes, const uint64_t* 
     if (!ctx || !counts || parts == 0 || parts > MAX_PARTS || (n && (!d_hashes || !d_records || !d_out)))
         return bl_set_error(BL_ERR_INVALID, "bad argument (1 <= parts <= 64)");
     BLH_TRY(hipSetDevice(bl_ctx_device(ctx)));
-    unsigned long long host[MAX_PARTS];
-    const hipError_t e = blpart::partition(reinterpret_cast<const ulonglong2*>(d_records), (unsigned long long)n, parts,
-                                           HashArrayOwner{reinterpret_cast<const unsigned long long*>(d_hashes)}, reinterpret_cast<ulonglong2*>(d_out), host,
-                                           bl_ctx_stream(ctx));
-    if (e != hipSuccess) return bl_set_error(e == hipErrorOutOfMemory ? BL_ERR_OOM : BL_ERR_HIP, hipGetErrorString(e));
-    for (uint32_t b = 0; b < parts; ++b) counts[b] = host[b];
-    return BL_OK;
+    return blpart::partition(ctx, reinterpret_cast<const ulonglong2*>(d_records), (unsigned long long)n, parts, HashArrayOwner{reinterpret_cast<const unsigned long long*>(d_hashes)},
+                             reinterpret_cast<ulonglong2*>(d_out), counts, bl_ctx_stream(ctx));
 }
 
 int bl_expand_super_kmers(bl_ctx* ctx, const uint64_t* d_records, uint64_t n_groups, uint32_t k, uint32_t flags, uint64_t* d_kmers, uint64_t capacity,
@@ -648,20 +643,13 @@ int bl_expand_super_kmers(bl_ctx* ctx, const uint64_t* d_records, uint64_t n_gro
     BLH_TRY(hipSetDevice(bl_ctx_device(ctx)));
     hipStream_t s = bl_ctx_stream(ctx);
     unsigned long long *sizes = nullptr, *offsets = nullptr;
-    void* tmp = nullptr;
-    size_t bytes = 0;
     const unsigned blocks = (unsigned)((n_groups + 255) / 256);
     sizes = static_cast<unsigned long long*>(bl_ctx_scratch(ctx, 4, 2 * n_groups * sizeof(unsigned long long)));  // (slots 4-6: the set operations')
     if (!sizes) return bl_set_error(BL_ERR_OOM, "scratch allocation failed");
     hipError_t e = hipSuccess;
     offsets = sizes + n_groups;
     hipLaunchKernelGGL(sizes_kernel, dim3(blocks), dim3(256), 0, s, reinterpret_cast<const ulonglong2*>(d_records), (unsigned long long)n_groups, sizes);
-    e = rocprim::exclusive_scan(nullptr, bytes, sizes, offsets, 0ull, n_groups, rocprim::plus<unsigned long long>(), s);
-    if (e == hipSuccess) {
-        tmp = bl_ctx_scratch(ctx, 5, bytes ? bytes : 16);
-        if (!tmp) e = hipErrorOutOfMemory;
-    }
-    if (e == hipSuccess) e = rocprim::exclusive_scan(tmp, bytes, sizes, offsets, 0ull, n_groups, rocprim::plus<unsigned long long>(), s);
+    e = blh::with_workspace(ctx, 5, [&](void* ws, size_t& bytes) { return rocprim::exclusive_scan(ws, bytes, sizes, offsets, 0ull, n_groups, rocprim::plus<unsigned long long>(), s); });
     unsigned long long last[2] = {0, 0};
     if (e == hipSuccess) e = hipMemcpyAsync(&last[0], offsets + n_groups - 1, 8, hipMemcpyDeviceToHost, s);
     if (e == hipSuccess) e = hipMemcpyAsync(&last[1], sizes + n_groups - 1, 8, hipMemcpyDeviceToHost, s);
@@ -678,7 +666,7 @@ int bl_expand_super_kmers(bl_ctx* ctx, const uint64_t* d_records, uint64_t n_gro
             if (e == hipSuccess) e = hipStreamSynchronize(s);
         }
     }
-    if (e != hipSuccess) return bl_set_error(e == hipErrorOutOfMemory ? BL_ERR_OOM : BL_ERR_HIP, hipGetErrorString(e));
+    if (e != hipSuccess) return blh::hip_rc(e);
     return rc;
 }
 
@@ -724,14 +712,7 @@ int bl_count_super_kmers(bl_ctx* ctx, const uint64_t* d_records, uint64_t n_grou
         e = hipGetLastError();
     }
     if (e == hipSuccess && bits > 0) {
-        size_t tmp_bytes = 0;
-        e = rocprim::radix_sort_pairs(nullptr, tmp_bytes, ids, ids_sorted, recs, recs_sorted, (size_t)n, 0, (unsigned)bits, s);
-        void* tmp = nullptr;
-        if (e == hipSuccess) {
-            tmp = bl_ctx_scratch(ctx, 1, tmp_bytes ? tmp_bytes : 16);
-            if (!tmp) e = hipErrorOutOfMemory;
-        }
-        if (e == hipSuccess) e = rocprim::radix_sort_pairs(tmp, tmp_bytes, ids, ids_sorted, recs, recs_sorted, (size_t)n, 0, (unsigned)bits, s);
+        e = blh::with_workspace(ctx, 1, [&](void* ws, size_t& bytes) { return rocprim::radix_sort_pairs(ws, bytes, ids, ids_sorted, recs, recs_sorted, (size_t)n, 0, (unsigned)bits, s); });
     } else if (e == hipSuccess) {
         ids_sorted = ids;
         recs_sorted = const_cast<ulonglong2*>(recs);
@@ -752,14 +733,8 @@ int bl_count_super_kmers(bl_ctx* ctx, const uint64_t* d_records, uint64_t n_grou
                            cursor, overflow, max_overflow);
         e = hipGetLastError();
         if (e == hipSuccess) e = hipMemsetAsync(distinct + n_buckets, 0, sizeof(unsigned int), s);
-        size_t scan_bytes = 0;
-        if (e == hipSuccess) e = rocprim::exclusive_scan(nullptr, scan_bytes, distinct, offsets, 0ull, (size_t)n_buckets + 1, rocprim::plus<unsigned long long>(), s);
-        void* scan_tmp = nullptr;
-        if (e == hipSuccess) {
-            scan_tmp = bl_ctx_scratch(ctx, 2, scan_bytes ? scan_bytes : 16);
-            if (!scan_tmp) e = hipErrorOutOfMemory;
-        }
-        if (e == hipSuccess) e = rocprim::exclusive_scan(scan_tmp, scan_bytes, distinct, offsets, 0ull, (size_t)n_buckets + 1, rocprim::plus<unsigned long long>(), s);
+        if (e == hipSuccess)
+            e = blh::with_workspace(ctx, 2, [&](void* ws, size_t& bytes) { return rocprim::exclusive_scan(ws, bytes, distinct, offsets, 0ull, (size_t)n_buckets + 1, rocprim::plus<unsigned long long>(), s); });
         if (e == hipSuccess) e = hipMemcpyAsync(&cur[0], offsets + n_buckets, sizeof(unsigned long long), hipMemcpyDeviceToHost, s);
         if (e == hipSuccess) e = hipMemcpyAsync(&cur[1], cursor + 1, sizeof(unsigned long long), hipMemcpyDeviceToHost, s);
         if (e == hipSuccess) e = hipStreamSynchronize(s);
@@ -893,7 +868,7 @@ int bl_count_super_kmers(bl_ctx* ctx, const uint64_t* d_records, uint64_t n_grou
             }
         }
     }
-    if (e != hipSuccess) return bl_set_error(e == hipErrorOutOfMemory ? BL_ERR_OOM : BL_ERR_HIP, hipGetErrorString(e));
+    if (e != hipSuccess) return blh::hip_rc(e);
     if (rc != BL_OK) return rc;
     *n_distinct = total;
     if (total > capacity || ((!d_kmers || !d_counts) && total)) return bl_set_error(BL_ERR_CAPACITY, "distinct k-mers exceed the capacity of the output arrays (n_distinct holds the need)");

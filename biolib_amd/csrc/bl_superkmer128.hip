@@ -258,12 +258,7 @@ __global__ void append_counted128_kernel(const __uint128_t* keys, const unsigned
 
 hipError_t excl_scan(bl_ctx* ctx, int tmp_slot, const unsigned long long* in, unsigned long long* out, size_t n, hipStream_t s)
 {
-    size_t bytes = 0;
-    hipError_t e = rocprim::exclusive_scan(nullptr, bytes, in, out, 0ull, n, rocprim::plus<unsigned long long>(), s);
-    if (e != hipSuccess) return e;
-    void* tmp = bl_ctx_scratch(ctx, tmp_slot, bytes ? bytes : 16);
-    if (!tmp) return hipErrorOutOfMemory;
-    return rocprim::exclusive_scan(tmp, bytes, in, out, 0ull, n, rocprim::plus<unsigned long long>(), s);
+    return blh::with_workspace(ctx, tmp_slot, [&](void* ws, size_t& bytes) { return rocprim::exclusive_scan(ws, bytes, in, out, 0ull, n, rocprim::plus<unsigned long long>(), s); });
 }
 
 // the k-mers of recs[0 .. n), group after group, to d_kmers when they fit `capacity` (nothing is written otherwise); *need = their number.
@@ -308,20 +303,10 @@ hipError_t count_by_sort128(bl_ctx* ctx, const Rec32* recs, unsigned long long n
     __uint128_t *sorted = keys + n_kmers, *distinct = keys + 2 * n_kmers;
     e = expand128(ctx, recs, n, k, canonical, reinterpret_cast<unsigned long long*>(keys), n_kmers, &n_kmers, s);
     if (e != hipSuccess) return e;
-    size_t bytes = 0;
-    e = rocprim::radix_sort_keys(nullptr, bytes, keys, sorted, (size_t)n_kmers, 0u, (unsigned)(2 * k), s);
-    if (e != hipSuccess) return e;
-    void* tmp = bl_ctx_scratch(ctx, 6, bytes ? bytes : 16);
-    if (!tmp) return hipErrorOutOfMemory;
-    e = rocprim::radix_sort_keys(tmp, bytes, keys, sorted, (size_t)n_kmers, 0u, (unsigned)(2 * k), s);
+    e = blh::with_workspace(ctx, 6, [&](void* ws, size_t& bytes) { return rocprim::radix_sort_keys(ws, bytes, keys, sorted, (size_t)n_kmers, 0u, (unsigned)(2 * k), s); });
     if (e != hipSuccess) return e;
     if (n_kmers >= (1ull << 32)) return hipErrorInvalidValue;  // (run_length_encode takes a 32-bit size; 2^32 k-mers are 64 GiB of keys)
-    bytes = 0;
-    e = rocprim::run_length_encode(nullptr, bytes, sorted, (unsigned int)n_kmers, distinct, counts, d_runs, s);
-    if (e != hipSuccess) return e;
-    tmp = bl_ctx_scratch(ctx, 6, bytes ? bytes : 16);
-    if (!tmp) return hipErrorOutOfMemory;
-    e = rocprim::run_length_encode(tmp, bytes, sorted, (unsigned int)n_kmers, distinct, counts, d_runs, s);
+    e = blh::with_workspace(ctx, 6, [&](void* ws, size_t& bytes) { return rocprim::run_length_encode(ws, bytes, sorted, (unsigned int)n_kmers, distinct, counts, d_runs, s); });
     if (e == hipSuccess) e = hipMemcpyAsync(runs, d_runs, sizeof(unsigned long long), hipMemcpyDeviceToHost, s);
     if (e == hipSuccess) e = hipStreamSynchronize(s);
     *uniq = distinct;
@@ -358,12 +343,8 @@ int bl_partition_records128(bl_ctx* ctx, const uint64_t* d_hashes, const uint64_
         return bl_set_error(BL_ERR_INVALID, "bad argument (1 <= parts <= 64)");
     if (((uintptr_t)d_records | (uintptr_t)d_out) & 31u) return bl_set_error(BL_ERR_INVALID, "d_records and d_out must be 32-byte aligned");
     BLH_TRY(hipSetDevice(bl_ctx_device(ctx)));
-    unsigned long long host[MAX_PARTS];
-    const hipError_t e = blpart::partition(reinterpret_cast<const Rec32*>(d_records), (unsigned long long)n, parts,
-                                           HashArrayOwner{reinterpret_cast<const unsigned long long*>(d_hashes)}, reinterpret_cast<Rec32*>(d_out), host, bl_ctx_stream(ctx));
-    if (e != hipSuccess) return hip_rc(e);
-    for (uint32_t b = 0; b < parts; ++b) counts[b] = host[b];
-    return BL_OK;
+    return blpart::partition(ctx, reinterpret_cast<const Rec32*>(d_records), (unsigned long long)n, parts, HashArrayOwner{reinterpret_cast<const unsigned long long*>(d_hashes)},
+                             reinterpret_cast<Rec32*>(d_out), counts, bl_ctx_stream(ctx));
 }
 
 int bl_expand_super_kmers128(bl_ctx* ctx, const uint64_t* d_records, uint64_t n_groups, uint32_t k, uint32_t flags, uint64_t* d_kmers, uint64_t capacity,
@@ -447,14 +428,7 @@ int bl_count_super_kmers128(bl_ctx* ctx, const uint64_t* d_records, uint64_t n_g
         e = hipGetLastError();
     }
     if (e == hipSuccess && bits > 0) {
-        size_t tmp_bytes = 0;
-        e = rocprim::radix_sort_pairs(nullptr, tmp_bytes, ids, ids_sorted, index, perm, (size_t)n, 0, (unsigned)bits, s);
-        void* tmp = nullptr;
-        if (e == hipSuccess) {
-            tmp = bl_ctx_scratch(ctx, 1, tmp_bytes ? tmp_bytes : 16);
-            if (!tmp) e = hipErrorOutOfMemory;
-        }
-        if (e == hipSuccess) e = rocprim::radix_sort_pairs(tmp, tmp_bytes, ids, ids_sorted, index, perm, (size_t)n, 0, (unsigned)bits, s);
+        e = blh::with_workspace(ctx, 1, [&](void* ws, size_t& bytes) { return rocprim::radix_sort_pairs(ws, bytes, ids, ids_sorted, index, perm, (size_t)n, 0, (unsigned)bits, s); });
     } else if (e == hipSuccess) {  // one bucket: the input order
         ids_sorted = ids;
         perm = index;
@@ -468,16 +442,8 @@ int bl_count_super_kmers128(bl_ctx* ctx, const uint64_t* d_records, uint64_t n_g
         e = hipGetLastError();
     }
     if (e == hipSuccess) e = hipMemsetAsync(distinct + n_buckets, 0, sizeof(unsigned int), s);
-    if (e == hipSuccess) {
-        size_t scan_bytes = 0;
-        e = rocprim::exclusive_scan(nullptr, scan_bytes, distinct, offsets, 0ull, (size_t)n_buckets + 1, rocprim::plus<unsigned long long>(), s);
-        void* scan_tmp = nullptr;
-        if (e == hipSuccess) {
-            scan_tmp = bl_ctx_scratch(ctx, 1, scan_bytes ? scan_bytes : 16);  // (the sort is done with slot 1: same stream)
-            if (!scan_tmp) e = hipErrorOutOfMemory;
-        }
-        if (e == hipSuccess) e = rocprim::exclusive_scan(scan_tmp, scan_bytes, distinct, offsets, 0ull, (size_t)n_buckets + 1, rocprim::plus<unsigned long long>(), s);
-    }
+    if (e == hipSuccess)  // (the sort is done with slot 1: same stream)
+        e = blh::with_workspace(ctx, 1, [&](void* ws, size_t& bytes) { return rocprim::exclusive_scan(ws, bytes, distinct, offsets, 0ull, (size_t)n_buckets + 1, rocprim::plus<unsigned long long>(), s); });
     unsigned long long n_over = 0;
     if (e == hipSuccess) e = hipMemcpyAsync(&table_total, offsets + n_buckets, sizeof(unsigned long long), hipMemcpyDeviceToHost, s);
     if (e == hipSuccess) e = hipMemcpyAsync(&n_over, cursor, sizeof(unsigned long long), hipMemcpyDeviceToHost, s);

@@ -202,139 +202,9 @@ class Context:
         b._keep = t
         return b
 
-    # ---- set operations on device k-mer lists (int64 CUDA tensors holding uint64 keys)
-    def sort_unique(self, keys, n=None):
-        """in-place sort + unique of keys[:n]; returns the number of distinct keys now at the front"""
-        n = keys.numel() if n is None else int(n)
-        self._inputs_ready()
-        out = C.c_uint64()
-        check(self._lib.bl_sort_unique_u64(self._h, C.c_void_p(keys.data_ptr()), n, C.byref(out)))
-        return int(out.value)
-
-    def jaccard(self, a, na, b, nb):
-        """(|A n B|, |A u B|) of two sorted duplicate-free key arrays"""
-        self._inputs_ready()
-        i, u = C.c_uint64(), C.c_uint64()
-        check(self._lib.bl_jaccard_sorted_u64(self._h, C.c_void_p(a.data_ptr()), int(na), C.c_void_p(b.data_ptr()), int(nb), C.byref(i), C.byref(u)))
-        return int(i.value), int(u.value)
-
-    def partition(self, keys, parts, seed=0, n=None):
-        """(bucketed copy of keys[:n], sizes[parts]): bucket b = keys with hash64(key, seed) % parts == b, contiguous, in bucket order"""
-        n = keys.numel() if n is None else int(n)
-        self._inputs_ready()
-        out = self.empty_u64(n)
-        counts = (C.c_uint64 * int(parts))()
-        check(self._lib.bl_partition_u64(self._h, C.c_void_p(keys.data_ptr()), n, int(parts), int(seed), C.c_void_p(out.data_ptr()), counts))
-        return out[:n], [int(c) for c in counts]
-
-    def sort_count(self, keys, n=None):
-        """(distinct keys ascending, multiplicities) of keys[:n]; keys is sorted in place"""
-        import torch
-
-        n = keys.numel() if n is None else int(n)
-        self._inputs_ready()
-        check(self._lib.bl_sort_u64(self._h, C.c_void_p(keys.data_ptr()), n))
-        uniq = self.empty_u64(n)
-        mult = torch.empty(max(n, 1), dtype=torch.int32, device=self.torch_device)
-        runs = C.c_uint64()
-        check(self._lib.bl_count_sorted_u64(self._h, C.c_void_p(keys.data_ptr()), n, C.c_void_p(uniq.data_ptr()), C.c_void_p(mult.data_ptr()), C.byref(runs)))
-        return uniq[: runs.value], mult[: runs.value]
-
-    def partition_records(self, hashes, records, parts, n=None):
-        """(bucketed copy of the 16-byte records[:n], sizes[parts]): bucket b = records with hashes[i] % parts == b"""
-        import torch
-
-        n = records.shape[0] if n is None else int(n)
-        self._inputs_ready()
-        out = torch.empty((max(n, 1), 2), dtype=torch.int64, device=self.torch_device)
-        counts = (C.c_uint64 * int(parts))()
-        check(self._lib.bl_partition_records(self._h, C.c_void_p(hashes.data_ptr()), C.c_void_p(records.data_ptr()), n, int(parts), C.c_void_p(out.data_ptr()), counts))
-        return out[:n], [int(c) for c in counts]
-
-    def expand_super_kmers(self, records, k, canonical=True, n=None):
-        """the k-mers (device tensor) the packed super-k-mer records stand for, group after group"""
-        n = records.shape[0] if n is None else int(n)
-        self._inputs_ready()
-        need = C.c_uint64()
-        flags = FLAG_CANONICAL if canonical else 0
-        rc = self._lib.bl_expand_super_kmers(self._h, C.c_void_p(records.data_ptr()), n, int(k), flags, None, 0, C.byref(need))
-        if rc not in (0, capi.BL_ERR_CAPACITY):
-            check(rc)
-        out = self.empty_u64(need.value)
-        if need.value:
-            check(self._lib.bl_expand_super_kmers(self._h, C.c_void_p(records.data_ptr()), n, int(k), flags, C.c_void_p(out.data_ptr()), need.value, C.byref(need)))
-        return out[: need.value]
-
-    def partition_records128(self, hashes, records, parts, n=None):
-        """(bucketed copy of the 32-byte records[:n] — int64[n, 4] —, sizes[parts]): bucket b = records with hashes[i] % parts == b"""
-        import torch
-
-        n = records.shape[0] if n is None else int(n)
-        self._inputs_ready()
-        out = torch.empty((max(n, 1), 4), dtype=torch.int64, device=self.torch_device)
-        counts = (C.c_uint64 * int(parts))()
-        check(self._lib.bl_partition_records128(self._h, C.c_void_p(hashes.data_ptr()), C.c_void_p(records.data_ptr()), n, int(parts), C.c_void_p(out.data_ptr()), counts))
-        return out[:n], [int(c) for c in counts]
-
-    def expand_super_kmers128(self, records, k, canonical=True, n=None):
-        """the 128-bit k-mers (device tensor int64[n_kmers, 2]: low, high) the 32-byte super-k-mer records stand for, group after group"""
-        import torch
-
-        n = records.shape[0] if n is None else int(n)
-        self._inputs_ready()
-        need = C.c_uint64()
-        flags = FLAG_CANONICAL if canonical else 0
-        rc = self._lib.bl_expand_super_kmers128(self._h, C.c_void_p(records.data_ptr()), n, int(k), flags, None, 0, C.byref(need))
-        if rc not in (0, capi.BL_ERR_CAPACITY):
-            check(rc)
-        out = torch.empty((max(need.value, 1), 2), dtype=torch.int64, device=self.torch_device)
-        if need.value:
-            check(self._lib.bl_expand_super_kmers128(self._h, C.c_void_p(records.data_ptr()), n, int(k), flags, C.c_void_p(out.data_ptr()), need.value, C.byref(need)))
-        return out[: need.value]
-
-    def count_super_kmers128(self, records, k, m, seed=0, canonical=True, n=None):
-        """(distinct 128-bit k-mers int64[d, 2] — low, high —, multiplicities int32[d]) of the 32-byte super-k-mer records, in no particular
-        order (bl_count_super_kmers128)"""
-        import torch
-
-        n = records.shape[0] if n is None else int(n)
-        self._inputs_ready()
-        flags = FLAG_CANONICAL if canonical else 0
-        need = C.c_uint64()
-        cap = int(n * (k - m + 1) * 0.62) + 4096  # groups average ~ (w+1)/2 k-mers; retried with the exact need if short
-        while True:
-            keys = torch.empty((cap, 2), dtype=torch.int64, device=self.torch_device)
-            cnts = torch.empty(cap, dtype=torch.int32, device=self.torch_device)
-            rc = self._lib.bl_count_super_kmers128(self._h, C.c_void_p(records.data_ptr()), n, int(k), int(m), int(seed), flags, C.c_void_p(keys.data_ptr()),
-                                                   C.c_void_p(cnts.data_ptr()), cap, C.byref(need))
-            if rc == capi.BL_ERR_CAPACITY:
-                cap = int(need.value) + 64
-                continue
-            check(rc)
-            return keys[: need.value], cnts[: need.value]
-
-    def read_file_u64(self, path, with_count=False):
-        """a run file (raw sorted u64) or, with_count, an io::basic_store'd vector<uint64_t> of biolib -> device tensor"""
-        n = C.c_uint64()
-        check(self._lib.bl_file_count_u64(str(path).encode(), 1 if with_count else 0, C.byref(n)))
-        out = self.empty_u64(n.value)
-        check(self._lib.bl_read_file_u64(self._h, str(path).encode(), 1 if with_count else 0, C.c_void_p(out.data_ptr()), n.value, C.byref(n)))
-        return out[: n.value]
-
-    def merge_runs(self, paths):
-        """the sorted union (duplicates kept) of biolib run files, on the device: what iterating the reference's
-        external_memory_vector yields"""
-        arr = (C.c_char_p * len(paths))(*[str(p).encode() for p in paths])
-        total = C.c_uint64()
-        rc = self._lib.bl_merge_runs_u64(self._h, arr, len(paths), None, 0, C.byref(total))
-        if rc not in (0, capi.BL_ERR_CAPACITY):
-            check(rc)
-        out = self.empty_u64(total.value)
-        if total.value:
-            check(self._lib.bl_merge_runs_u64(self._h, arr, len(paths), C.c_void_p(out.data_ptr()), total.value, C.byref(total)))
-        return out[: total.value]
-
-    # ---- the same set operations on 16-byte keys: int64[n, 2] CUDA tensors (low, high), as kmers128 / expand_super_kmers128 return
+    # ---- set operations on device k-mer lists, run files and super-k-mer records: one implementation per operation, keyed by the 8-byte
+    # words of an element.  Keys: 1 word (int64[n] CUDA tensors holding uint64 keys) or 2 (int64[n, 2]: low, high, as kmers128 /
+    # expand_super_kmers128 return).  Records: 2 words (16 bytes, whose k-mers are one-word keys) or 4 (32 bytes: two-word keys).
     def _keys128(self, keys, n):
         if keys.dim() != 2 or keys.shape[1] != 2 or keys.element_size() != 8 or not keys.is_contiguous():
             raise ValueError("128-bit keys are a contiguous int64[n, 2] tensor (low, high)")
@@ -344,11 +214,162 @@ class Context:
         self._inputs_ready()
         return n
 
-    def empty_u128(self, n):
+    def _n_keys(self, words, keys, n):
+        if words == 2:
+            return self._keys128(keys, n)
+        n = keys.numel() if n is None else int(n)
+        self._inputs_ready()
+        return n
+
+    def _n_records(self, records, n):
+        n = records.shape[0] if n is None else int(n)
+        self._inputs_ready()
+        return n
+
+    def _key_call(self, name, words):
+        return getattr(self._lib, f"bl_{name}_u{64 * words}")
+
+    def _record_call(self, name, words):
+        return getattr(self._lib, f"bl_{name}{'128' if words == 4 else ''}")
+
+    def _empty_words(self, n, words):
         import torch
 
-        return torch.empty((max(int(n), 1), 2), dtype=torch.int64, device=self.torch_device)
+        n = max(int(n), 1)
+        return torch.empty(n if words == 1 else (n, words), dtype=torch.int64, device=self.torch_device)
 
+    def _sort_unique(self, words, keys, n, *key_bits):
+        n = self._n_keys(words, keys, n)
+        out = C.c_uint64()
+        check(self._key_call("sort_unique", words)(self._h, C.c_void_p(keys.data_ptr()), n, *key_bits, C.byref(out)))
+        return int(out.value)
+
+    def _jaccard(self, words, a, na, b, nb):
+        na, nb = self._n_keys(words, a, na), self._n_keys(words, b, nb)
+        i, u = C.c_uint64(), C.c_uint64()
+        check(self._key_call("jaccard_sorted", words)(self._h, C.c_void_p(a.data_ptr()), na, C.c_void_p(b.data_ptr()), nb, C.byref(i), C.byref(u)))
+        return int(i.value), int(u.value)
+
+    def _partition(self, words, keys, parts, seed, n):
+        n = self._n_keys(words, keys, n)
+        out = self._empty_words(n, words)
+        counts = (C.c_uint64 * max(int(parts), 1))()
+        check(self._key_call("partition", words)(self._h, C.c_void_p(keys.data_ptr()), n, int(parts), int(seed), C.c_void_p(out.data_ptr()), counts))
+        return out[:n], [int(c) for c in counts]
+
+    def _sort_count(self, words, keys, n, *key_bits):
+        import torch
+
+        n = self._n_keys(words, keys, n)
+        check(self._key_call("sort", words)(self._h, C.c_void_p(keys.data_ptr()), n, *key_bits))
+        uniq = self._empty_words(n, words)
+        mult = torch.empty(max(n, 1), dtype=torch.int32, device=self.torch_device)
+        runs = C.c_uint64()
+        check(self._key_call("count_sorted", words)(self._h, C.c_void_p(keys.data_ptr()), n, C.c_void_p(uniq.data_ptr()), C.c_void_p(mult.data_ptr()), C.byref(runs)))
+        return uniq[: runs.value], mult[: runs.value]
+
+    def _read_file(self, words, path, with_count):
+        n = C.c_uint64()
+        check(self._key_call("file_count", words)(str(path).encode(), 1 if with_count else 0, C.byref(n)))
+        out = self._empty_words(n.value, words)
+        check(self._key_call("read_file", words)(self._h, str(path).encode(), 1 if with_count else 0, C.c_void_p(out.data_ptr()), n.value, C.byref(n)))
+        return out[: n.value]
+
+    def _merge_runs(self, words, paths):
+        merge = self._key_call("merge_runs", words)
+        arr = (C.c_char_p * len(paths))(*[str(p).encode() for p in paths])
+        total = C.c_uint64()
+        rc = merge(self._h, arr, len(paths), None, 0, C.byref(total))
+        if rc not in (0, capi.BL_ERR_CAPACITY):
+            check(rc)
+        out = self._empty_words(total.value, words)
+        if total.value:
+            check(merge(self._h, arr, len(paths), C.c_void_p(out.data_ptr()), total.value, C.byref(total)))
+        return out[: total.value]
+
+    def _partition_records(self, words, hashes, records, parts, n):
+        n = self._n_records(records, n)
+        out = self._empty_words(n, words)
+        counts = (C.c_uint64 * int(parts))()
+        check(self._record_call("partition_records", words)(self._h, C.c_void_p(hashes.data_ptr()), C.c_void_p(records.data_ptr()), n, int(parts),
+                                                            C.c_void_p(out.data_ptr()), counts))
+        return out[:n], [int(c) for c in counts]
+
+    def _expand_super_kmers(self, words, records, k, canonical, n):
+        expand = self._record_call("expand_super_kmers", words)
+        n = self._n_records(records, n)
+        need = C.c_uint64()
+        flags = FLAG_CANONICAL if canonical else 0
+        rc = expand(self._h, C.c_void_p(records.data_ptr()), n, int(k), flags, None, 0, C.byref(need))
+        if rc not in (0, capi.BL_ERR_CAPACITY):
+            check(rc)
+        out = self._empty_words(need.value, words // 2)
+        if need.value:
+            check(expand(self._h, C.c_void_p(records.data_ptr()), n, int(k), flags, C.c_void_p(out.data_ptr()), need.value, C.byref(need)))
+        return out[: need.value]
+
+    def _count_super_kmers(self, words, records, k, m, seed, canonical, n, out=None):
+        import torch
+
+        n = self._n_records(records, n)
+        flags = FLAG_CANONICAL if canonical else 0
+        need = C.c_uint64()
+        cap = int(n * (k - m + 1) * 0.62) + 4096  # groups average ~ (w+1)/2 k-mers; retried with the exact need if short
+        while True:
+            if out is not None:  # caller-owned (keys int64, counts int32) tensors: no allocation on this path
+                keys, cnts = out
+                cap = min(keys.shape[0], cnts.numel())
+                out = None
+            else:
+                keys = self._empty_words(cap, words // 2)
+                cnts = torch.empty(max(cap, 1), dtype=torch.int32, device=self.torch_device)
+            rc = self._record_call("count_super_kmers", words)(self._h, C.c_void_p(records.data_ptr()), n, int(k), int(m), int(seed), flags,
+                                                               C.c_void_p(keys.data_ptr()), C.c_void_p(cnts.data_ptr()), cap, C.byref(need))
+            if rc == capi.BL_ERR_CAPACITY:
+                cap = int(need.value) + 64
+                continue
+            check(rc)
+            return keys[: need.value], cnts[: need.value]
+
+    def sort_unique(self, keys, n=None):
+        """in-place sort + unique of keys[:n]; returns the number of distinct keys now at the front"""
+        return self._sort_unique(1, keys, n)
+
+    def jaccard(self, a, na, b, nb):
+        """(|A n B|, |A u B|) of two sorted duplicate-free key arrays"""
+        return self._jaccard(1, a, na, b, nb)
+
+    def partition(self, keys, parts, seed=0, n=None):
+        """(bucketed copy of keys[:n], sizes[parts]): bucket b = keys with hash64(key, seed) % parts == b, contiguous, in bucket order"""
+        return self._partition(1, keys, parts, seed, n)
+
+    def sort_count(self, keys, n=None):
+        """(distinct keys ascending, multiplicities) of keys[:n]; keys is sorted in place"""
+        return self._sort_count(1, keys, n)
+
+    def partition_records(self, hashes, records, parts, n=None):
+        """(bucketed copy of the 16-byte records[:n], sizes[parts]): bucket b = records with hashes[i] % parts == b"""
+        return self._partition_records(2, hashes, records, parts, n)
+
+    def expand_super_kmers(self, records, k, canonical=True, n=None):
+        """the k-mers (device tensor) the packed super-k-mer records stand for, group after group"""
+        return self._expand_super_kmers(2, records, k, canonical, n)
+
+    def count_super_kmers(self, records, k, m, seed=0, canonical=True, n=None, out=None):
+        """(distinct k-mers, multiplicities) of the packed super-k-mer records, in no particular order: buckets by minimizer
+        hash counted in LDS hash tables (bl_count_super_kmers), no global sort"""
+        return self._count_super_kmers(2, records, k, m, seed, canonical, n, out)
+
+    def read_file_u64(self, path, with_count=False):
+        """a run file (raw sorted u64) or, with_count, an io::basic_store'd vector<uint64_t> of biolib -> device tensor"""
+        return self._read_file(1, path, with_count)
+
+    def merge_runs(self, paths):
+        """the sorted union (duplicates kept) of biolib run files, on the device: what iterating the reference's
+        external_memory_vector yields"""
+        return self._merge_runs(1, paths)
+
+    # ---- the same on 16-byte keys and 32-byte records
     def sort128(self, keys, key_bits=128, n=None):
         """in-place ascending sort of keys[:n] as 128-bit integers; key_bits = number of low bits that can be non-zero (2k for k-mers)"""
         n = self._keys128(keys, n)
@@ -356,37 +377,41 @@ class Context:
 
     def sort_unique128(self, keys, key_bits=128, n=None):
         """in-place sort + unique of keys[:n]; returns the number of distinct keys now at the front"""
-        n = self._keys128(keys, n)
-        out = C.c_uint64()
-        check(self._lib.bl_sort_unique_u128(self._h, C.c_void_p(keys.data_ptr()), n, int(key_bits), C.byref(out)))
-        return int(out.value)
+        return self._sort_unique(2, keys, n, int(key_bits))
 
     def jaccard128(self, a, na, b, nb):
         """(|A n B|, |A u B|) of two sorted duplicate-free arrays of 128-bit keys"""
-        na, nb = self._keys128(a, na), self._keys128(b, nb)
-        i, u = C.c_uint64(), C.c_uint64()
-        check(self._lib.bl_jaccard_sorted_u128(self._h, C.c_void_p(a.data_ptr()), na, C.c_void_p(b.data_ptr()), nb, C.byref(i), C.byref(u)))
-        return int(i.value), int(u.value)
+        return self._jaccard(2, a, na, b, nb)
 
     def partition128(self, keys, parts, seed=0, n=None):
         """(bucketed copy of keys[:n], sizes[parts]): bucket b = keys with hash64_u128(lo, hi, seed) % parts == b, contiguous, in bucket order"""
-        n = self._keys128(keys, n)
-        out = self.empty_u128(n)
-        counts = (C.c_uint64 * max(int(parts), 1))()
-        check(self._lib.bl_partition_u128(self._h, C.c_void_p(keys.data_ptr()), n, int(parts), int(seed), C.c_void_p(out.data_ptr()), counts))
-        return out[:n], [int(c) for c in counts]
+        return self._partition(2, keys, parts, seed, n)
 
     def sort_count128(self, keys, key_bits=128, n=None):
         """(distinct keys ascending int64[d, 2], multiplicities int32[d]) of keys[:n]; keys is sorted in place"""
-        import torch
+        return self._sort_count(2, keys, n, int(key_bits))
 
-        n = self._keys128(keys, n)
-        check(self._lib.bl_sort_u128(self._h, C.c_void_p(keys.data_ptr()), n, int(key_bits)))
-        uniq = self.empty_u128(n)
-        mult = torch.empty(max(n, 1), dtype=torch.int32, device=self.torch_device)
-        runs = C.c_uint64()
-        check(self._lib.bl_count_sorted_u128(self._h, C.c_void_p(keys.data_ptr()), n, C.c_void_p(uniq.data_ptr()), C.c_void_p(mult.data_ptr()), C.byref(runs)))
-        return uniq[: runs.value], mult[: runs.value]
+    def partition_records128(self, hashes, records, parts, n=None):
+        """(bucketed copy of the 32-byte records[:n] — int64[n, 4] —, sizes[parts]): bucket b = records with hashes[i] % parts == b"""
+        return self._partition_records(4, hashes, records, parts, n)
+
+    def expand_super_kmers128(self, records, k, canonical=True, n=None):
+        """the 128-bit k-mers (device tensor int64[n_kmers, 2]: low, high) the 32-byte super-k-mer records stand for, group after group"""
+        return self._expand_super_kmers(4, records, k, canonical, n)
+
+    def count_super_kmers128(self, records, k, m, seed=0, canonical=True, n=None):
+        """(distinct 128-bit k-mers int64[d, 2] — low, high —, multiplicities int32[d]) of the 32-byte super-k-mer records, in no particular
+        order (bl_count_super_kmers128)"""
+        return self._count_super_kmers(4, records, k, m, seed, canonical, n)
+
+    def read_file_u128(self, path, with_count=False):
+        """a run file (raw sorted 16-byte keys) or, with_count, an io::basic_store'd vector<__uint128_t> of biolib -> int64[n, 2] device tensor"""
+        return self._read_file(2, path, with_count)
+
+    def merge_runs128(self, paths):
+        """the sorted union (duplicates kept) of run files of 16-byte keys, on the device: what iterating the reference's
+        external_memory_vector<__uint128_t> yields"""
+        return self._merge_runs(2, paths)
 
     # ---- the count table: what takes the (keys, counts) pairs of the counters on
     def count_table(self, keys, counts=None, key_bits=None, n=None):
@@ -412,53 +437,6 @@ class Context:
         build = self._lib.bl_table_build_u128 if key_words == 2 else self._lib.bl_table_build_u64
         check(build(self._h, C.c_void_p(keys.data_ptr()), _ptr(counts), n, key_bits, C.byref(h)))
         return CountTable(self, h)
-
-    def read_file_u128(self, path, with_count=False):
-        """a run file (raw sorted 16-byte keys) or, with_count, an io::basic_store'd vector<__uint128_t> of biolib -> int64[n, 2] device tensor"""
-        n = C.c_uint64()
-        check(self._lib.bl_file_count_u128(str(path).encode(), 1 if with_count else 0, C.byref(n)))
-        out = self.empty_u128(n.value)
-        check(self._lib.bl_read_file_u128(self._h, str(path).encode(), 1 if with_count else 0, C.c_void_p(out.data_ptr()), n.value, C.byref(n)))
-        return out[: n.value]
-
-    def merge_runs128(self, paths):
-        """the sorted union (duplicates kept) of run files of 16-byte keys, on the device: what iterating the reference's
-        external_memory_vector<__uint128_t> yields"""
-        arr = (C.c_char_p * len(paths))(*[str(p).encode() for p in paths])
-        total = C.c_uint64()
-        rc = self._lib.bl_merge_runs_u128(self._h, arr, len(paths), None, 0, C.byref(total))
-        if rc not in (0, capi.BL_ERR_CAPACITY):
-            check(rc)
-        out = self.empty_u128(total.value)
-        if total.value:
-            check(self._lib.bl_merge_runs_u128(self._h, arr, len(paths), C.c_void_p(out.data_ptr()), total.value, C.byref(total)))
-        return out[: total.value]
-
-    def count_super_kmers(self, records, k, m, seed=0, canonical=True, n=None, out=None):
-        """(distinct k-mers, multiplicities) of the packed super-k-mer records, in no particular order: buckets by minimizer
-        hash counted in LDS hash tables (bl_count_super_kmers), no global sort"""
-        import torch
-
-        n = records.shape[0] if n is None else int(n)
-        self._inputs_ready()
-        flags = FLAG_CANONICAL if canonical else 0
-        need = C.c_uint64()
-        cap = int(n * (k - m + 1) * 0.62) + 4096  # groups average ~ (w+1)/2 k-mers; retried with the exact need if short
-        while True:
-            if out is not None:  # caller-owned (keys int64, counts int32) tensors: no allocation on this path
-                keys, cnts = out
-                cap = min(keys.numel(), cnts.numel())
-                out = None
-            else:
-                keys = self.empty_u64(cap)
-                cnts = torch.empty(max(cap, 1), dtype=torch.int32, device=self.torch_device)
-            rc = self._lib.bl_count_super_kmers(self._h, C.c_void_p(records.data_ptr()), n, int(k), int(m), int(seed), flags, C.c_void_p(keys.data_ptr()),
-                                                C.c_void_p(cnts.data_ptr()), cap, C.byref(need))
-            if rc == capi.BL_ERR_CAPACITY:
-                cap = int(need.value) + 64
-                continue
-            check(rc)
-            return keys[: need.value], cnts[: need.value]
 
     def probe_hbm(self, n_bytes=8 << 30, iters=5):
         """(read GB/s, copy GB/s) sustained by this device: read-only stream kernel and DtoD copy"""
@@ -513,9 +491,10 @@ class Context:
 
     # ---- device arrays (torch plumbing)
     def empty_u64(self, n):
-        import torch
+        return self._empty_words(n, 1)
 
-        return torch.empty(max(int(n), 1), dtype=torch.int64, device=self.torch_device)
+    def empty_u128(self, n):
+        return self._empty_words(n, 2)
 
     def empty_u8(self, n):
         import torch

@@ -141,6 +141,30 @@ def test_sort_count_vs_numpy(ctx):
     assert e[0].numel() == 0 and e[1].numel() == 0
 
 
+def test_count_sorted_u64_refuses_2_to_the_32_keys(ctx):
+    """rocPRIM's run_length_encode takes a 32-bit size: from 2^32 keys on the call is an error before any device work, as
+    bl_count_sorted_u128 is, not a count of n mod 2^32 keys.  (n = 2^32 - 1 is not called: it would read that many keys.)"""
+    import ctypes as C
+
+    import torch
+
+    from biolib_amd import capi
+
+    L = capi.lib()
+    keys = torch.tensor([1, 1, 2, 3], dtype=torch.int64, device="cuda")
+    uniq = torch.full((4,), -7, dtype=torch.int64, device="cuda")
+    mult = torch.full((4,), -7, dtype=torch.int32, device="cuda")
+    args = [C.c_void_p(t.data_ptr()) for t in (keys, uniq, mult)]
+    n = C.c_uint64(99)
+    assert L.bl_count_sorted_u64(ctx._h, args[0], 1 << 32, args[1], args[2], C.byref(n)) == capi.BL_ERR_INVALID
+    assert n.value == 0 and L.bl_last_error() == b"bl_count_sorted_u64 takes fewer than 2^32 keys"
+    ctx.sync()
+    assert keys.tolist() == [1, 1, 2, 3] and uniq.tolist() == [-7] * 4 and mult.tolist() == [-7] * 4
+    # the same arrays with their own length
+    capi.check(L.bl_count_sorted_u64(ctx._h, args[0], 4, args[1], args[2], C.byref(n)))
+    assert n.value == 3 and uniq.tolist()[:3] == [1, 2, 3] and mult.tolist()[:3] == [2, 1, 1]
+
+
 def test_exchange_and_count_single_rank_rccl(ctx):
     """the whole distributed counter on one GPU: scan -> partition -> all-to-all (RCCL, world 1) -> sort -> count"""
     import torch

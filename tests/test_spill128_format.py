@@ -51,3 +51,25 @@ def test_read_side_host(tmp_path):
     capi.check(L.bl_file_count_u128(str(empty).encode(), 0, C.byref(n)))
     assert n.value == 0
     capi.check(L.bl_read_file_u128_host(str(empty).encode(), 0, None, 0, C.byref(n)))
+
+
+def test_count_word_whose_product_wraps_is_refused(tmp_path):
+    """stored vectors whose count word times the element size wraps around 2^64 to the body's length: 2^61 + 1 over an 8-byte body (the
+    case that passes a product check of 8-byte elements) and 2^60 + 1 over a 16-byte body (the same for 16-byte elements)"""
+    from biolib_amd import capi
+
+    L = capi.lib()
+    n = C.c_uint64(5)
+    out = np.zeros((4, 2), np.uint64)
+    for name, words in (("wrap8.bin", [(1 << 61) + 1, 7]), ("wrap16.bin", [(1 << 60) + 1, 7, 9])):
+        bad = tmp_path / name
+        bad.write_bytes(np.array(words, np.uint64).tobytes())
+        assert L.bl_file_count_u128(str(bad).encode(), 1, C.byref(n)) == capi.BL_ERR_INVALID and n.value == 0
+        assert b"16-byte elements (count word and file size disagree)" in L.bl_last_error()
+        assert L.bl_read_file_u128_host(str(bad).encode(), 1, out.ctypes.data_as(C.c_void_p), 4, C.byref(n)) == capi.BL_ERR_INVALID
+        assert not out.any()
+    # a sound vector of one element next to them
+    good = tmp_path / "one.bin"
+    good.write_bytes(np.array([1, 7, 9], np.uint64).tobytes())
+    capi.check(L.bl_read_file_u128_host(str(good).encode(), 1, out.ctypes.data_as(C.c_void_p), 4, C.byref(n)))
+    assert n.value == 1 and out[0].tolist() == [7, 9]

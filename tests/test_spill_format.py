@@ -100,3 +100,25 @@ def test_merge_runs_on_device(tmp_path):
     v = ctx.read_file_u64(os.path.join(SP, "vector.bin"), with_count=True).cpu().numpy().view(np.uint64)
     assert np.array_equal(v, np.sort(ref_keys))
     ctx.close()
+
+
+def test_count_word_whose_product_wraps_is_refused(tmp_path):
+    """a stored vector whose count word is 2^61 + 1 over ONE 8-byte element: 8 + 8 * (2^61 + 1) wraps to the file's 16 bytes, so the
+    check has to divide the body's length, not multiply the count"""
+    from biolib_amd import capi
+
+    L = capi.lib()
+    bad = tmp_path / "wrap.bin"
+    bad.write_bytes(np.array([(1 << 61) + 1, 7], np.uint64).tobytes())
+    n = C.c_uint64(5)
+    assert L.bl_file_count_u64(str(bad).encode(), 1, C.byref(n)) == capi.BL_ERR_INVALID and n.value == 0
+    assert b"8-byte elements (count word and file size disagree)" in L.bl_last_error()
+    out = np.zeros(4, np.uint64)
+    assert L.bl_read_file_u64_host(str(bad).encode(), 1, out.ctypes.data_as(C.c_void_p), 4, C.byref(n)) == capi.BL_ERR_INVALID
+    assert not out.any()
+    # the same bytes are a sound run file of two elements, and a sound vector once the count word says 1
+    capi.check(L.bl_file_count_u64(str(bad).encode(), 0, C.byref(n)))
+    assert n.value == 2
+    bad.write_bytes(np.array([1, 7], np.uint64).tobytes())
+    capi.check(L.bl_read_file_u64_host(str(bad).encode(), 1, out.ctypes.data_as(C.c_void_p), 4, C.byref(n)))
+    assert n.value == 1 and out[0] == 7
