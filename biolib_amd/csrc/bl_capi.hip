@@ -106,7 +106,8 @@ struct bl_ctx {
     bool exact_windows = false;  // bl_ctx_set_exact_windows
     bool position_tiled = false; // bl_ctx_set_option("position_tiled"): never the read-tiled layout
     bool packed_codes = true;    // bl_ctx_set_option("packed_codes"): 0 = new batches get no packed copy and scans ignore the one a batch has
-    int jaccard128_path = 0;     // bl_ctx_set_option("jaccard128_path"): 0 = bl_jaccard_sorted_u128 chooses, 1 = merge kernel, 2 = search kernel
+    bool direct_codes = true;    // bl_ctx_set_option("direct_codes"): 0 = the read-tiled pass 1 stages every tile in LDS, clean ones too
+    int jaccard128_path = 0;    // bl_ctx_set_option("jaccard128_path"): 0 = bl_jaccard_sorted_u128 chooses, 1 = merge kernel, 2 = search kernel
     bool count128_tables = true; // bl_ctx_set_option("count128_tables"): 0 = bl_count_super_kmers128 counts every bucket by sort + run-length
     int table_prefix_bits = -1;  // bl_ctx_set_option("table_prefix_bits"): -1 = bl_table_build_* chooses the width of the prefix index, 0 .. 24 forces it
     bool ktiming = false;
@@ -626,6 +627,10 @@ int bl_ctx_set_option(bl_ctx* c, const char* name, int64_t value)
     }
     if (n == "packed_codes" && (value == 0 || value == 1)) {
         c->packed_codes = value != 0;
+        return BL_OK;
+    }
+    if (n == "direct_codes" && (value == 0 || value == 1)) {
+        c->direct_codes = value != 0;
         return BL_OK;
     }
     if (n == "count128_tables" && (value == 0 || value == 1)) {
@@ -1240,6 +1245,7 @@ static int scan_windows(int mode, bl_ctx* c, const bl_batch* b, uint64_t first, 
     if (c->packed_codes && b->codes && bl::packed_covers(p) && (p.frl || bl::packed_scan_shape(mode, (int)w))) {  // pass 1 stages from the batch's packed copy and hands no codes to pass 2
         p.codes_packed = b->codes;
         p.chunk_bad = b->chunk_bad;
+        p.direct_codes = c->direct_codes ? 1 : 0;
     }
     p.unit = (int32_t)unit;
     p.w = (int32_t)w;

@@ -233,19 +233,26 @@ template <int MODE, int W, int NS, int LIM_LAST, bool GENERIC, bool APPROX = fal
 __device__ __forceinline__ void count_tile_frl(const ScanParams& p, TileShared<MODE, W>& sh, uint32_t tile, int tid)
 {
     const int64_t q0 = tile_q0(p, tile);
-    phase_load_frl<MODE, W, PACKED>(p, sh, tid, q0);
-    if (APPROX && tid == 0) sh.redo = 0;
-    if (!PACKED) {  // hand the packed codes to pass 2 (a batch with a packed copy: pass 2 reads that)
-        uint32_t* sc = p.slots_c + (size_t)tile * p.slot_chunks;
-        for (int c = tid; c < p.slot_chunks; c += TPB) sc[c] = sh.codes[c];  // own LDS entries: no barrier needed
+    // a tile of the packed copy without a bad chunk (nearly every tile of real reads) is not staged: no codes, flags or wave_bad in LDS and
+    // no barrier; its lanes take their dwords from the copy (phase_hash_frl).  One answer for the workgroup, from scalar loads.
+    const bool clean = PACKED && p.direct_codes && frl_tile_clean(p, q0);
+    if (!clean) {
+        phase_load_frl<MODE, W, PACKED>(p, sh, tid, q0);
+        if (!PACKED) {  // hand the packed codes to pass 2 (a batch with a packed copy: pass 2 reads that)
+            uint32_t* sc = p.slots_c + (size_t)tile * p.slot_chunks;
+            for (int c = tid; c < p.slot_chunks; c += TPB) sc[c] = sh.codes[c];  // own LDS entries: no barrier needed
+        }
+        __syncthreads();  // (clean is uniform for the workgroup)
     }
-    __syncthreads();
 
     ThreadState st;
     bool tie = false;
-    phase_hash_frl<MODE, W, NS, GENERIC, APPROX, U>(p, sh, tid, q0, tile, st);
-    phase_window_frl_a<MODE, W, NS, LIM_LAST, APPROX>(p, sh, tid, st, nullptr, &tie);
-    if (APPROX && BL_COLD(wave_any(tie)) && (tid & 63) == 0) sh.redo = 1;
+    phase_hash_frl<MODE, W, NS, GENERIC, APPROX, U>(p, sh, tid, q0, tile, st, clean ? p.codes_packed + (q0 >> 4) : nullptr);
+    phase_window_frl_a<MODE, W, NS, LIM_LAST, APPROX>(p, sh, tid, st, nullptr, &tie, clean);
+    if (APPROX) {  // one flag per wave, written whatever it holds: nothing to reset, so no barrier between a reset and these stores
+        const bool any = wave_any(tie);
+        if ((tid & 63) == 0) sh.wave_redo[wave_index(tid)] = any ? 1u : 0u;
+    }
     const uint32_t packed = phase_window_frl_b<MODE, W, NS>(p, tid, st, nullptr);
 
     uint32_t total;
@@ -254,7 +261,7 @@ __device__ __forceinline__ void count_tile_frl(const ScanParams& p, TileShared<M
     phase_list_frl<MODE, W, NS>(sh, st, excl & 0xffffu, excl >> 16);
     if (tid == 0) p.tile_counts[tile] = (unsigned long long)n_s | ((unsigned long long)n_e << 32);
     __syncthreads();  // lists complete
-    if (APPROX && tid == 0 && BL_COLD(sh.redo != 0)) p.redo_list[atomicAdd(p.redo_count, 1ull)] = tile;
+    if (APPROX && tid == 0 && BL_COLD((sh.wave_redo[0] | sh.wave_redo[1] | sh.wave_redo[2] | sh.wave_redo[3]) != 0)) p.redo_list[atomicAdd(p.redo_count, 1ull)] = tile;
     const size_t slot = (size_t)tile * p.stride;  // stride is a multiple of 4 entries: dword aligned
     spill_list(p.slots_a + slot, sh.list_a, n_s, tid);
     if (MODE == MODE_SUPERKMER) {

@@ -121,6 +121,9 @@ struct ScanParams {
     // reads them here.
     const uint32_t* codes_packed;
     const uint32_t* chunk_bad;
+    // read-tiled pass 1 with a packed copy: a tile without a bad chunk is not staged, its lanes read their dwords from codes_packed
+    // (frl_tile_clean, bl_scan_frl.hpp).  bl_ctx_set_option("direct_codes", 0) clears it: every tile is staged (checks and A/B runs)
+    int32_t direct_codes;
 };
 
 // The packed copy's guard chunks: a position-tiled scan starts up to 16 bases before the batch (plan_scan), and a tile that starts inside

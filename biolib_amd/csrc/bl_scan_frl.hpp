@@ -69,6 +69,36 @@ BL_DEV void phase_load_frl(const ScanParams& p, TileShared<MODE, W>& sh, int tid
 #endif
 }
 
+// A tile of a PACKED scan whose staged chunks [q0 >> 4, (q0 >> 4) + slot_chunks) are all good ones needs no staging: what phase_load_frl
+// would put into sh.codes is, bit for bit, codes_packed from q0 >> 4 on, and nobody looks at sh.flags.  The test ORs whole words of
+// chunk_bad, those that hold a bit of a staged chunk and no others (packed_covers promises the staged chunks, guards included, not their
+// neighbours' words): a bad chunk of a neighbouring tile in one of them costs a staging that was not needed, nothing else.  q0, and so
+// every address, is the same for the whole workgroup: scalar loads on the device, nmin or nmin + 1 of them (10 or 11 for 150-bp reads).
+BL_DEV bool frl_tile_clean(const ScanParams& p, int64_t q0)
+{
+    const int64_t c0 = q0 >> 4;  // q0 >= 0 (tile_q0)
+    const uint32_t* wp = p.chunk_bad + (c0 >> 5);
+    const int nmin = (p.slot_chunks + 31) >> 5, nw = (int)(((c0 & 31) + p.slot_chunks + 31) >> 5);  // nw - nmin is 0 or 1
+    uint32_t any = 0;
+    for (int i = 0; i < nmin; ++i) any |= wp[i];
+    if (nw > nmin) any |= wp[nmin];
+    return any == 0;
+}
+
+// four consecutive dwords of the packed copy, at any dword (one global_load_dwordx4)
+#if defined(__HIP_DEVICE_COMPILE__) && !defined(BL_CPU_EMU)
+typedef uint32_t PackedQuad __attribute__((ext_vector_type(4), aligned(4)));
+#endif
+BL_DEV void load_packed4(const uint32_t* q, uint32_t& c0, uint32_t& c1, uint32_t& c2, uint32_t& c3)
+{
+#if defined(__HIP_DEVICE_COMPILE__) && !defined(BL_CPU_EMU)
+    const PackedQuad v = *reinterpret_cast<const PackedQuad*>(q);
+    c0 = v.x; c1 = v.y; c2 = v.z; c3 = v.w;
+#else
+    c0 = q[0]; c1 = q[1]; c2 = q[2]; c3 = q[3];
+#endif
+}
+
 // ------------------------------------------------------------------------------------------------
 // Phase 2: which read and which units this lane owns; roll and hash them.
 // GENERIC: run-time unit length (see phase_hash: those kernels hash with the compiler's own multiply)
@@ -101,8 +131,9 @@ BL_DEV void units_direct(uint32_t a0, uint32_t a1, uint32_t a2, uint32_t r0, uin
 
 // U: the unit length where the kernel fixes it (0: from p.unit).  31 (the C3 shape) with NS <= 17 takes the units by direct
 // extraction (units_direct); every other length keeps the rolling registers.  In the CPU emulation U is 0 and p.unit decides.
+// tile_codes: where the tile's chunk 0 lies in the packed copy, for a tile that was not staged (frl_tile_clean); nullptr: sh.codes holds it
 template <int MODE, int W, int NS, bool GENERIC = false, bool APPROX = false, int U = 0>
-BL_DEV void phase_hash_frl(const ScanParams& p, TileShared<MODE, W>& sh, int tid, int64_t q0, uint32_t tile, ThreadState& st)
+BL_DEV void phase_hash_frl(const ScanParams& p, TileShared<MODE, W>& sh, int tid, int64_t q0, uint32_t tile, ThreadState& st, const uint32_t* tile_codes = nullptr)
 {
     const int wv = wave_index(tid), lane = tid & 63;
     const int r = (int)(((uint32_t)lane * p.lpr_inv) >> 16);  // read of this wave the lane works on
@@ -113,9 +144,15 @@ BL_DEV void phase_hash_frl(const ScanParams& p, TileShared<MODE, W>& sh, int tid
     const int base = active ? off0 + (wv * p.rpw + r) * p.read_len + j * NS : off0;
     st.lane_base = base;
     st.jlane = active ? j : -1;
-    // the lane's 48 bases from `base` on: four staged dwords funnel-shifted to the lane's own alignment
-    const uint32_t* cp = sh.codes + (base >> 4);
-    const uint32_t c0 = cp[0], c1 = cp[1], c2 = cp[2], c3 = cp[3];
+    // the lane's 48 bases from `base` on: four dwords, staged ones or the packed copy's own, funnel-shifted to the lane's own alignment
+    // (two loads in two branches: one load through a pointer chosen between LDS and HBM would be a flat load)
+    uint32_t c0, c1, c2, c3;
+    if (tile_codes) {
+        load_packed4(tile_codes + (base >> 4), c0, c1, c2, c3);
+    } else {
+        const uint32_t* cp = sh.codes + (base >> 4);
+        c0 = cp[0]; c1 = cp[1]; c2 = cp[2]; c3 = cp[3];
+    }
     const int sh2 = 2 * (base & 15);
     const uint32_t a0 = (uint32_t)(((((uint64_t)c0 << 32) | c1) << sh2) >> 32);
     const uint32_t a1 = (uint32_t)(((((uint64_t)c1 << 32) | c2) << sh2) >> 32);
@@ -286,8 +323,9 @@ constexpr bool frl_occ_form() { return MODE == MODE_MINIMIZER && W > 1 && W - 1 
 // Phase 3a: window argmins of the lane's NS windows and which of them exist.
 // LIM_LAST != 0 (the compile-time geometry of scan_count_frl_kernel): every lane of a read owns NS windows but the last,
 // which owns LIM_LAST (1..NS); 0: any geometry.
+// clean: the tile was not staged (frl_tile_clean: no break in it, and sh.wave_bad and sh.flags hold nothing of this tile)
 template <int MODE, int W, int NS, int LIM_LAST = 0, bool APPROX = false>
-BL_DEV void phase_window_frl_a(const ScanParams& p, TileShared<MODE, W>& sh, int tid, ThreadState& st, const ThreadState* all, bool* tie = nullptr)
+BL_DEV void phase_window_frl_a(const ScanParams& p, TileShared<MODE, W>& sh, int tid, ThreadState& st, const ThreadState* all, bool* tie = nullptr, bool clean = false)
 {
     uint32_t a[S];
     lane_window_argmin_frl<NS, (W > 1 ? W : 2), APPROX>(all, tid, st, st.jlane >= 0, a, tie);
@@ -298,7 +336,7 @@ BL_DEV void phase_window_frl_a(const ScanParams& p, TileShared<MODE, W>& sh, int
         lim = lim < 0 ? 0 : (lim > NS ? NS : lim);
         vmask = (1u << lim) - 1u;
     }
-    const uint32_t tile_bad = sh.wave_bad[0] | sh.wave_bad[1] | sh.wave_bad[2] | sh.wave_bad[3];
+    const uint32_t tile_bad = clean ? 0u : sh.wave_bad[0] | sh.wave_bad[1] | sh.wave_bad[2] | sh.wave_bad[3];
     if (BL_COLD(tile_bad)) vmask &= frl_good_mask<NS>(p, sh.flags, st.lane_base, p.unit + (W > 0 ? W : p.w) - 1);
     st.vmask = vmask;
     if (frl_occ_form<MODE, W, NS>()) {

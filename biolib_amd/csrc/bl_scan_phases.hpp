@@ -43,6 +43,7 @@ struct TileShared {
     uint32_t wave_tot[NWAVE];
     uint32_t redo;                  // closed-syncmer scans: some wave of the tile could not decide (equal high dwords)
     uint32_t wave_bad[NWAVE];       // read-tiled scans: wave wv staged at least one base that is not ACGTUacgtu
+    uint32_t wave_redo[NWAVE];      // read-tiled scans on murmur64_top: wave wv could not decide; every wave writes its own, so no barrier orders a reset before them
     unsigned long long dig[4];
 };
 

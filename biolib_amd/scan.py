@@ -108,7 +108,7 @@ class Context:
         check(self._lib.bl_ctx_set_exact_windows(self._h, 1 if on else 0))
 
     def set_option(self, name, value):
-        """tuning / test switches by name (bl_ctx_set_option: "exact_windows", "lanes", "position_tiled", "packed_codes", "emit_lds_bytes",
+        """tuning / test switches by name (bl_ctx_set_option: "exact_windows", "lanes", "position_tiled", "packed_codes", "direct_codes", "emit_lds_bytes",
         "count128_tables", "jaccard128_path", "table_prefix_bits")"""
         check(self._lib.bl_ctx_set_option(self._h, name.encode(), int(value)))
 

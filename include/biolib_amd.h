@@ -280,6 +280,8 @@ int bl_ctx_set_exact_windows(bl_ctx* ctx, int on);
  *                                 and the window scans stage their tiles from it.  0: batches made LATER get none, and scans ignore the copy
  *                                 of a batch that has one.  bl_batch_from_device batches, whose memory is the caller's,
  *                                 never get one
+ *   "direct_codes"    0 / 1       1 (default): the read-tiled pass 1 of a batch with a packed copy does not stage a tile that holds no bad
+ *                                 chunk; its lanes read their codes from the copy.  0: every tile is staged in LDS
  *   "emit_lds_bytes"  0 or bytes  two-lane contexts: LDS footprint the record pass's workgroups are padded to, which caps how many of
  *                                 them a CU holds beside the next scan's hashing pass (0: the built-in default per scan kind)
  *   "count128_tables" 0 / 1       0: bl_count_super_kmers128 counts every bucket by expand + sort + run-length instead of the LDS tables
