@@ -30,7 +30,7 @@ SYMBOLS = [
     "bl_select_read_counts", "bl_batch_select", "bl_read_spans", "bl_scan_read_edits", "bl_batch_apply_edits",
     "bl_table_adjacency", "bl_table_unitigs", "bl_unitig_links", "bl_unitigs_format_gfa", "bl_unitigs_mark", "bl_table_remove_unitigs",
     "bl_text_index_build", "bl_text_index_info", "bl_text_index_offsets", "bl_text_index_destroy", "bl_reader_next_batch_device_indexed", "bl_batch_format",
-    "bl_text_write",
+    "bl_text_write", "bl_bgzf_bound", "bl_bgzf_deflate", "bl_text_write_bgzf",
 ]
 
 
@@ -57,6 +57,7 @@ class ReadCountsRecord(C.Structure):
 
 READ_COUNTS_INIT, READ_COUNTS_ACCUMULATE = 0, 1
 SELECT_KEEP_EMPTY = 1
+BGZF_NO_EOF = 1
 TRIM_NONE, TRIM_PREFIX, TRIM_SUFFIX, TRIM_LONGER = 0, 1, 2, 3
 
 
@@ -319,6 +320,11 @@ def lib():
         L.bl_reader_next_batch_device_indexed.argtypes = [vp, vp, u64, C.POINTER(vp), C.POINTER(vp), C.POINTER(u64), C.POINTER(u64)]
         L.bl_batch_format.argtypes = [vp, vp, vp, vp, vp, vp, vp, C.POINTER(FormatRule), vp, u64, C.POINTER(u64), C.POINTER(u64)]
         L.bl_text_write.argtypes = [vp, vp, u64, C.c_char_p, C.c_int]
+    if "BIOLIB_AMD_LIB" not in os.environ or hasattr(L, "bl_bgzf_deflate"):
+        L.bl_bgzf_bound.argtypes = [u64, C.c_uint32]
+        L.bl_bgzf_bound.restype = u64
+        L.bl_bgzf_deflate.argtypes = [vp, vp, u64, C.c_uint32, vp, u64, C.POINTER(u64), vp, C.POINTER(u64)]
+        L.bl_text_write_bgzf.argtypes = [vp, vp, u64, C.c_char_p, C.c_int, C.c_uint32]
     _lib = L
     return L
 

@@ -26,8 +26,8 @@ int bl_ctx_table_prefix_bits(bl_ctx* ctx);  // the "table_prefix_bits" option
 //          the text (3)                                the text parser, which call the set operations while they hold them
 //   4      data; blpart::partition's histogram,        the set operations (bl_keylist.hpp), the owner splits, the table build and algebra, the
 //          offsets and bucket starts                   quantiles, select, format, the corrector, the graph (about 133 bytes per key in slot 4),
-//   5      library workspace (rocPRIM):                links and clean: none of them calls another while it holds 4-6
-//          blh::exclusive_sum takes it
+//   5      library workspace (rocPRIM):                links, clean and the BGZF writer (slots, token areas and sizes of the members in flight):
+//          blh::exclusive_sum takes it                 none of them calls another while it holds 4-6
 //   6      counters, flags, statistics
 void* bl_ctx_scratch(bl_ctx* ctx, int slot, size_t bytes);
 

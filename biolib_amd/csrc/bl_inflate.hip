@@ -10,6 +10,7 @@
 #include <cstring>
 
 #include "../../include/biolib_amd.h"
+#include "bl_crc_wave.hpp"
 #include "bl_host.hpp"
 #include "bl_inflate_core.hpp"
 int bl_bgzf_inflate_on(hipStream_t s, const void* d_packed, uint64_t packed_bytes, const bl_bgzf_member* d_members, uint64_t n_members, void* d_text,
@@ -17,34 +18,7 @@ int bl_bgzf_inflate_on(hipStream_t s, const void* d_packed, uint64_t packed_byte
 
 namespace {
 
-constexpr uint32_t CRC_POLY = 0xedb88320u;  // CRC-32 of gzip, bit-reflected: bit 31 of a word is x^0
-constexpr uint32_t STATUS_CRC = 10;         // after the decoder's own codes (bl_inflate::Status)
-
-// a(x) * b(x) mod P(x) in the reflected representation
-__host__ __device__ constexpr uint32_t mulmod(uint32_t a, uint32_t b)
-{
-    uint32_t p = 0;
-    for (int i = 0; i < 32; ++i) {
-        if (a & (0x80000000u >> i)) p ^= b;
-        b = (b >> 1) ^ ((b & 1u) ? CRC_POLY : 0u);
-    }
-    return p;
-}
-
-struct PowerTable {
-    uint32_t x2n[32];  // x^(2^k) mod P
-};
-constexpr PowerTable make_powers()
-{
-    PowerTable t{};
-    uint32_t p = 0x40000000u;  // x^1
-    for (int k = 0; k < 32; ++k) {
-        t.x2n[k] = p;
-        p = mulmod(p, p);
-    }
-    return t;
-}
-__constant__ PowerTable g_powers = make_powers();
+constexpr uint32_t STATUS_CRC = 10;  // after the decoder's own codes (bl_inflate::Status)
 
 __global__ __launch_bounds__(64) void inflate_members_kernel(const uint8_t* packed, uint64_t packed_bytes, const bl_bgzf_member* members, uint32_t n_members,
                                                              uint8_t* text, uint64_t text_bytes, uint32_t* status)
@@ -66,33 +40,16 @@ __global__ __launch_bounds__(64) void inflate_members_kernel(const uint8_t* pack
     if ((threadIdx.x & 63u) == 0) status[mi] = st;
 }
 
-// CRC-32 of each member's text: the lanes take 64 consecutive slices, each its slice's own CRC; the CRC of a concatenation is
-// crc(A || B) = crc(A) * x^(8 |B|) + crc(B)  (mod P), so lane i's value is carried over the bytes behind its slice and the 64
-// results are added (xor).
+// CRC-32 of each member's text (slices and their combination: bl_crc_wave.hpp)
 __global__ __launch_bounds__(64) void crc_members_kernel(const uint8_t* text, const bl_bgzf_member* members, uint32_t n_members, uint32_t* status)
 {
     __shared__ uint32_t table[256];
     const uint32_t lane = threadIdx.x & 63u, mi = blockIdx.x;
-    for (uint32_t e = lane; e < 256; e += 64) {
-        uint32_t c = e;
-        for (int k = 0; k < 8; ++k) c = (c >> 1) ^ ((c & 1u) ? CRC_POLY : 0u);
-        table[e] = c;
-    }
+    blcrcw::fill_table(table, lane);
     __syncthreads();
     if (mi >= n_members || status[mi] != bl_inflate::OK) return;
     const bl_bgzf_member m = members[mi];
-    const uint32_t slice = (m.isize + 63u) / 64u;
-    const uint32_t a = lane * slice < m.isize ? lane * slice : m.isize;
-    const uint32_t b = a + slice < m.isize ? a + slice : m.isize;
-    const uint8_t* p = text + m.dst_off;
-    uint32_t c = 0xffffffffu;
-    for (uint32_t i = a; i < b; ++i) c = table[(c ^ p[i]) & 0xffu] ^ (c >> 8);
-    c = a < b ? ~c : 0u;
-    uint32_t power = 0x80000000u;  // x^0, then x^(8 * bytes behind the slice)
-    uint32_t behind = m.isize - b;
-    for (int k = 3; behind; ++k, behind >>= 1)
-        if (behind & 1u) power = mulmod(g_powers.x2n[k & 31], power);
-    uint32_t v = mulmod(power, c);
+    uint32_t v = blcrcw::lane_share(table, text + m.dst_off, m.isize, lane);
     for (int d = 32; d >= 1; d >>= 1) v ^= (uint32_t)__shfl_xor((int)v, d, 64);
     if (lane == 0 && v != m.crc) status[mi] = STATUS_CRC;
 }

@@ -478,6 +478,46 @@ class Context:
             for p in ptrs:
                 self._lib.bl_device_free(self._h, p)
 
+    def bgzf_deflate_raw(self, text_ptr, n_bytes, flags, out, capacity, members=None):
+        """bl_bgzf_deflate: `text_ptr` a device address (or None), `out` a uint8 device tensor (or None) of `capacity` bytes, `members` an
+        int64 device tensor of 4 words per member (or None).  Returns (n_out_bytes, n_members); the library checks every argument."""
+        nb, nm = C.c_uint64(), C.c_uint64()
+        check(self._lib.bl_bgzf_deflate(self._h, text_ptr, int(n_bytes), int(flags), _ptr(out), int(capacity), C.byref(nb), _ptr(members), C.byref(nm)))
+        return int(nb.value), int(nm.value)
+
+    def bgzf_deflate(self, text, eof=True, members=False):
+        """`text` (bytes or a uint8 device tensor) as BGZF made on the device (bl_bgzf_deflate): a uint8 device tensor holding members of at
+        most 65,280 bytes of text each, one deflate block a member, and the EOF marker unless eof=False.  members=True: also the member
+        table, an int64 device tensor [n_members, 4] (the 32-byte rows of bl_bgzf_member: what bl_bgzf_inflate takes)."""
+        import torch
+
+        if not isinstance(text, torch.Tensor):
+            data = bytes(text)
+            text = torch.from_numpy(np.frombuffer(data, np.uint8).copy()).to(self.torch_device) if data else torch.empty(0, dtype=torch.uint8, device=self.torch_device)
+        if not (text.is_cuda and text.dtype == torch.uint8 and text.is_contiguous()):
+            raise ValueError("text: bytes or a contiguous uint8 device tensor")
+        n, flags = int(text.numel()), 0 if eof else capi.BGZF_NO_EOF
+        bound = int(self._lib.bl_bgzf_bound(n, flags))
+        out = torch.empty(max(bound, 16), dtype=torch.uint8, device=self.torch_device)
+        table = torch.zeros((max((n + 65279) // 65280, 1), 4), dtype=torch.int64, device=self.torch_device) if members else None
+        self._inputs_ready()
+        n_out, n_members = self.bgzf_deflate_raw(_ptr(text) if n else None, n, flags, out, bound, table)
+        return (out[:n_out], table[:n_members]) if members else out[:n_out]
+
+    def _write_text(self, text, path, append, compress, eof):
+        """a uint8 device tensor to a file: bl_text_write, or bl_text_write_bgzf.  Returns the bytes written: the text's, or with compress
+        the bytes the file grew by (the C call reports no count) — 0 for a target that is no regular file, such as /dev/null."""
+        import os
+
+        path = str(path)
+        p, n = (_ptr(text) if text.numel() else None), int(text.numel())
+        if not compress:
+            check(self._lib.bl_text_write(self._h, p, n, path.encode(), 1 if append else 0))
+            return n
+        before = os.path.getsize(path) if append and os.path.exists(path) else 0
+        check(self._lib.bl_text_write_bgzf(self._h, p, n, path.encode(), 1 if append else 0, 0 if eof else capi.BGZF_NO_EOF))
+        return os.path.getsize(path) - before
+
     def clock_probe_start(self, duration_ms):
         """start measuring the shader clock the chip holds over the next duration_ms (beside whatever else runs)"""
         h = C.c_void_p()
@@ -905,12 +945,14 @@ class Unitigs:
         self.mark_raw(rule, marks, st)
         return marks[:self.n_unitigs], st.as_dict()
 
-    def write_fasta(self, path, line_width=0):
+    def write_fasta(self, path, line_width=0, compress=False):
         """The unitigs as a FASTA file made on the device (Batch.write): names 0, 1, ... with " LN:i:<bases> KC:i:<count sum>" — BCALM's
-        header without its km and L fields (no floats; the links between unitigs leave through write_gfa).  Returns the bytes written."""
+        header without its km and L fields (no floats; the links between unitigs leave through write_gfa).  compress=True: as BGZF.
+        Returns the bytes written."""
         if self.batch is None:
             raise ValueError("unitigs(batch=False) holds no strings to write")
-        return self.batch.write(path, fmt="fasta", tags=self.count_sums if self.n_unitigs else None, tag_label="KC:i:", tag_length=True, line_width=line_width)
+        return self.batch.write(path, compress=compress, fmt="fasta", tags=self.count_sums if self.n_unitigs else None, tag_label="KC:i:", tag_length=True,
+                                line_width=line_width)
 
     def format_gfa_raw(self, rule, out=None, capacity=0):
         """bl_unitigs_format_gfa: `rule` a capi.GfaRule, `out` a uint8 device tensor (None: sizing only) of `capacity` bytes.  Synchronous.
@@ -943,11 +985,10 @@ class Unitigs:
         self.format_gfa_raw(rule, out, n_bytes)
         return out[:n_bytes]
 
-    def write_gfa(self, path, prefix="", first_number=0, header=True):
-        """format_gfa(...) written to `path` (bl_text_write, as Batch.write).  Returns the bytes written."""
-        text = self.format_gfa(prefix, first_number, header)
-        check(self._lib.bl_text_write(self._ctx._h, _ptr(text) if text.numel() else None, text.numel(), str(path).encode(), 0))
-        return int(text.numel())
+    def write_gfa(self, path, prefix="", first_number=0, header=True, compress=False):
+        """format_gfa(...) written to `path` (bl_text_write, as Batch.write; compress=True: as BGZF, bl_text_write_bgzf).  Returns the
+        bytes written."""
+        return self._ctx._write_text(self.format_gfa(prefix, first_number, header), path, False, compress, True)
 
 
 class ReadCounts:
@@ -1373,12 +1414,12 @@ class Batch:
         self.format_raw(rule, out, n_bytes, index, source_index, spans, tags, d_offsets)
         return out[:n_bytes]
 
-    def write(self, path, append=False, **how):
+    def write(self, path, append=False, compress=False, eof=True, **how):
         """format(**how) written to `path` (bl_text_write: the download in chunks through two pinned buffers, a chunk written while the
-        next copies; no compression).  Returns the bytes written."""
-        text = self.format(**how)
-        check(self._lib.bl_text_write(self.ctx._h, _ptr(text) if text.numel() else None, text.numel(), str(path).encode(), 1 if append else 0))
-        return int(text.numel())
+        next copies).  compress=True writes BGZF instead (bl_text_write_bgzf: the text is deflated on the device, chunk by chunk, and only
+        compressed bytes are downloaded); eof=False leaves the EOF marker out, for a file that further calls append to — the last call
+        writes it.  Returns the bytes written to the file (with compress: what the file grew by; 0 where `path` is no regular file)."""
+        return self.ctx._write_text(self.format(**how), path, append, compress, eof)
 
     def read_spans_raw(self, records, rule, spans, stat=None, offsets=None):
         """bl_read_spans: `records` are the whole-batch records of read_counts_raw, `rule` a capi.SpanRule, `spans` takes n_seqs pairs of

@@ -762,7 +762,8 @@ int bl_table_unitigs(bl_ctx* ctx, const bl_table* table, uint32_t k, bl_batch** 
  *   BL_ERR_INVALID with a message, nothing launched: NULL ctx, unitigs or rule; a batch of another context; unknown flags; rule->k even
  *   or outside 3 .. 63; name_prefix without a NUL inside its 16 bytes; reserved != 0; d_out not 16-byte aligned; d_unitig_offsets NULL
  *   with n_unitigs > 0; d_links NULL with n_links > 0.
- * NOT built: L: fields in BCALM FASTA headers, km:f:, GFA 2, paths and walks, compression.  (Tip, island and simple-bubble removal is
+ * NOT built: L: fields in BCALM FASTA headers, km:f:, GFA 2, paths and walks; of compression (bl_text_write_bgzf) a .gzi index, a
+ * run-length block header, matches across members, plain gzip output and compression levels.  (Tip, island and simple-bubble removal is
  * bl_unitigs_mark / bl_table_remove_unitigs below; superbubbles are not built.) */
 typedef struct bl_unitig_link { uint32_t from, to; /* (unitig << 1) | orientation */ } bl_unitig_link;
 typedef struct bl_link_stats { uint64_t n_ends, n_links, n_self_reverse, n_dead_ends, n_branch_ends, reserved[3]; } bl_link_stats;
@@ -878,7 +879,7 @@ int bl_table_remove_unitigs(bl_ctx* ctx, const bl_table* table, const bl_unitig_
  *
  * bl_text_write downloads d_text[0, n_bytes) in chunks through two pinned buffers and writes chunk c while chunk c + 1 copies, behind
  * the work on the context's stream.  append != 0 appends.  BL_ERR_IO where the file cannot be opened or a write comes back short.
- * No compression: BGZF deflate on the device is NOT built. */
+ * bl_text_write_bgzf (below, "BGZF written on the device") is the same pipeline with the compressor in front. */
 typedef struct bl_text_index bl_text_index;
 int bl_text_index_build(bl_ctx* ctx, const char* text, uint64_t n_bytes, bl_batch** out_batch, bl_text_index** out_index, uint64_t* n_seqs,
                         uint64_t* n_bases);
@@ -1016,6 +1017,42 @@ int bl_bgzf_walk(const void* bytes, uint64_t n_bytes, uint64_t src_base, uint64_
  * two buffers is refused, not followed, and nothing outside a member's own [dst_off, dst_off + isize) is ever written. */
 int bl_bgzf_inflate(bl_ctx* ctx, const void* d_packed, uint64_t packed_bytes, const bl_bgzf_member* d_members, uint64_t n_members, void* d_text,
                     uint64_t text_bytes, uint32_t* d_status);
+
+/* ---- BGZF written on the device (the chain's exit compressed) ----------------------------------------------------
+ * bl_bgzf_deflate turns the device text d_text[0, n_bytes) into a chain of BGZF members in d_out, one wavefront per member: the text is
+ * cut into members of 65,280 bytes (bgzip's 0xff00), the last one holds the rest.  A member is the 18-byte BGZF header (1f 8b 08 04,
+ * MTIME 0, XFL 0, OS ff, XLEN 6, 'B' 'C' 02 00, BSIZE - 1), ONE deflate block, CRC-32 and ISIZE.  The 28-byte EOF marker (the empty
+ * member with the fixed-code data 03 00) follows unless BL_BGZF_NO_EOF is set; n_bytes == 0 gives the marker alone, or nothing.
+ * Members are contiguous in d_out; no byte at or behind d_out[*n_out_bytes] is written.
+ *   the block     the smallest of three forms in bytes, stored / fixed codes / dynamic codes, ties in that order; the sizes are known
+ *                 exactly after the code build, before a bit is written.  Stored keeps every member at or below ISIZE + 31 bytes:
+ *                 bl_bgzf_bound = n_bytes + 31 * ceil(n_bytes / 65280) + 28 (without the 28 under BL_BGZF_NO_EOF) is the exact worst case.
+ *   the codes     Huffman lengths from the block's own histograms, ties by symbol number, limited to 15 bits by the count-per-length
+ *                 adjustment; an alphabet with fewer than two used symbols gets two 1-bit codes.  The dynamic header sends the code
+ *                 lengths one by one with 4 bits each (HCLEN 19, no repeat symbols): at most 57 + 4 * (HLIT + HDIST) bits, 0.25 % of a member.
+ *   the matches   LZ77 inside the member's own text, distances up to 32,768, lengths 3..258, a deterministic function of the member's
+ *                 bytes (bl_deflate_core.hpp; restated in tests/deflate_cases.py); greedy, no lazy evaluation.
+ * capacity < bl_bgzf_bound(n_bytes, flags): BL_ERR_CAPACITY, nothing launched, *n_out_bytes = the bound (there is no sizing run: it
+ * would compress twice).  d_members (nullable, device, one row per member with text; the EOF marker is not listed) receives exactly what
+ * bl_bgzf_inflate takes: src_off / src_len the deflate data inside d_out, dst_off its place in the text, isize and crc.  *n_members
+ * (nullable) = ceil(n_bytes / 65280).  Synchronous, behind the work on the context's stream; temporaries come from the context's scratch
+ * and are bounded by 1,024 members in flight (334 MB), not by n_bytes.  Reruns are bit-identical: no atomic decides a placement.  No byte at or
+ * behind d_text[n_bytes] is read, whatever the alignment of d_text.
+ * BL_ERR_INVALID with a message, nothing launched: a NULL ctx; NULL d_text with n_bytes > 0; NULL d_out or n_out_bytes; unknown flags;
+ * d_out not 16-byte aligned.
+ *
+ * bl_text_write_bgzf is bl_text_write with the compressor in front: the text goes in chunks of 1,024 members (66.8 MB: a wave a member,
+ * fewer would leave the device idle); a chunk's size is fetched into a pinned word and exactly that many bytes are copied; chunk c + 1
+ * is copied and chunk c + 2 compressed while chunk c is written, so only compressed bytes cross the link.  The EOF marker is written
+ * once at the end unless BL_BGZF_NO_EOF is set (a file appended to in several calls: set it on all but the last, or finish with a call of
+ * n_bytes == 0).  append and BL_ERR_IO as in bl_text_write.  Every call pins its two host buffers and takes its two device buffers anew,
+ * each sized by the smaller of the text and a chunk; they are not kept between calls.
+ * NOT built: a .gzi index, a run-length block header, matches across members, plain single-stream gzip output, compression levels. */
+enum { BL_BGZF_NO_EOF = 1u << 0 };
+uint64_t bl_bgzf_bound(uint64_t n_bytes, uint32_t flags);
+int bl_bgzf_deflate(bl_ctx* ctx, const uint8_t* d_text, uint64_t n_bytes, uint32_t flags, uint8_t* d_out, uint64_t capacity, uint64_t* n_out_bytes,
+                    bl_bgzf_member* d_members /* nullable */, uint64_t* n_members /* nullable */);
+int bl_text_write_bgzf(bl_ctx* ctx, const uint8_t* d_text, uint64_t n_bytes, const char* path, int append, uint32_t flags);
 
 /* Measurement helper: sustained HBM rates of THIS device — a read-only streaming kernel over n_bytes and a
  * device-to-device copy (read + write bytes counted), `iters` repetitions each; bench.py reports them next to the 8 TB/s spec. */
