@@ -31,6 +31,7 @@ SYMBOLS = [
     "bl_table_adjacency", "bl_table_unitigs", "bl_unitig_links", "bl_unitigs_format_gfa", "bl_unitigs_mark", "bl_table_remove_unitigs",
     "bl_text_index_build", "bl_text_index_info", "bl_text_index_offsets", "bl_text_index_destroy", "bl_reader_next_batch_device_indexed", "bl_batch_format",
     "bl_text_write", "bl_bgzf_bound", "bl_bgzf_deflate", "bl_text_write_bgzf",
+    "bl_scan_read_steps", "bl_link_support", "bl_steps_format_gaf",
 ]
 
 
@@ -135,6 +136,33 @@ class LinkStats(C.Structure):
 class GfaRule(C.Structure):
     """bl_gfa_rule (40 bytes)"""
     _fields_ = [("flags", C.c_uint32), ("k", C.c_uint32), ("name_prefix", C.c_char * 16), ("first_number", C.c_uint64), ("reserved", C.c_uint64)]
+
+
+STEP_LINKED, STEP_CONTINUED = 1, 2
+# bl_read_step as a numpy record (32 bytes)
+READ_STEP_DTYPE = [("pos", "<u8"), ("seq", "<u8"), ("end", "<u4"), ("offset", "<u4"), ("n_kmers", "<u4"), ("flags", "<u4")]
+
+
+class StepStats(C.Structure):
+    """bl_step_stats"""
+    _fields_ = [(name, C.c_uint64) for name in ("n_valid", "n_found", "n_steps", "n_chains", "n_linked", "longest_step")] + [("reserved", C.c_uint64 * 2)]
+
+    def as_dict(self):
+        return {name: int(getattr(self, name)) for name, _ in self._fields_ if name != "reserved"}
+
+
+class SupportStats(C.Structure):
+    """bl_support_stats"""
+    _fields_ = [("n_transitions", C.c_uint64), ("n_unmatched", C.c_uint64), ("reserved", C.c_uint64 * 2)]
+
+    def as_dict(self):
+        return {name: int(getattr(self, name)) for name, _ in self._fields_ if name != "reserved"}
+
+
+class GafRule(C.Structure):
+    """bl_gaf_rule (64 bytes)"""
+    _fields_ = [("flags", C.c_uint32), ("k", C.c_uint32), ("read_prefix", C.c_char * 16), ("segment_prefix", C.c_char * 16),
+                ("read_first_number", C.c_uint64), ("segment_first_number", C.c_uint64), ("reserved", C.c_uint64)]
 
 
 CLEAN_TIPS, CLEAN_ISOLATED, CLEAN_BUBBLES = 1, 2, 4
@@ -325,6 +353,10 @@ def lib():
         L.bl_bgzf_bound.restype = u64
         L.bl_bgzf_deflate.argtypes = [vp, vp, u64, C.c_uint32, vp, u64, C.POINTER(u64), vp, C.POINTER(u64)]
         L.bl_text_write_bgzf.argtypes = [vp, vp, u64, C.c_char_p, C.c_int, C.c_uint32]
+    if "BIOLIB_AMD_LIB" not in os.environ or hasattr(L, "bl_scan_read_steps"):
+        L.bl_scan_read_steps.argtypes = [vp, vp, u64, u64, u32, u32, vp, vp, vp, u64, vp, vp, u64, C.POINTER(StepStats)]
+        L.bl_link_support.argtypes = [vp, vp, u64, vp, vp, u64, u64, vp, C.POINTER(SupportStats)]
+        L.bl_steps_format_gaf.argtypes = [vp, vp, vp, vp, u64, vp, u64, C.POINTER(GafRule), vp, u64, C.POINTER(u64)]
     _lib = L
     return L
 

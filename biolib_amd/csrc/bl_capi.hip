@@ -371,6 +371,16 @@ int ensure_start_bits(bl_ctx* c, const bl_batch* cb)
 // the borrowed stream, or lane 0's.  With two lanes a scan may still be running on lane 1's stream, so lane 0's stream is
 // first made to wait for the end of the last scan issued on the other lane: callers may chain scan -> pack / sort / ...
 // without bl_ctx_sync, as the header promises.
+// kernel_event for a unit of its own that enqueues on bl_ctx_stream (bl_steps.hip: the node pass): the pair is recorded on `stream`
+int bl_ctx_kernel_event(bl_ctx* c, hipStream_t stream, int start)
+{
+    const hipStream_t keep = c->stream;
+    c->stream = stream;
+    const int rc = kernel_event(c, start != 0);
+    c->stream = keep;
+    return rc;
+}
+
 hipStream_t bl_ctx_stream(bl_ctx* c)
 {
     if (c->borrowed) return c->user_stream;

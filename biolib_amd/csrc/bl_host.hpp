@@ -14,6 +14,9 @@ int bl_set_error(int code, const char* msg);  // the thread's bl_last_error(); r
 // The stream every non-scan entry point enqueues on: the borrowed one or lane 0's, made to wait for a scan still running on lane 1.
 hipStream_t bl_ctx_stream(bl_ctx* ctx);
 int bl_ctx_device(bl_ctx* ctx);
+// With bl_ctx_kernel_timing on: an event pair on `stream` around what the caller enqueues between start = 1 and start = 0, added to
+// bl_ctx_kernel_time's sum as one launch.  Nothing otherwise.
+int bl_ctx_kernel_event(bl_ctx* ctx, hipStream_t stream, int start);
 int bl_ctx_count128_tables(bl_ctx* ctx);    // the "count128_tables" option
 int bl_ctx_jaccard128_path(bl_ctx* ctx);    // the "jaccard128_path" option
 int bl_ctx_table_prefix_bits(bl_ctx* ctx);  // the "table_prefix_bits" option
@@ -21,13 +24,14 @@ int bl_ctx_table_prefix_bits(bl_ctx* ctx);  // the "table_prefix_bits" option
 // Grow-only device scratch that lives with the context; NULL on failure.  The caller has synchronised the slot's previous use (the entry
 // points that use it are synchronous).
 //   slot   holds                                       used by
-//   0      candidates                                  bl_correct
+//   0      candidates; heads and tails of the steps    bl_correct; bl_steps
 //   0-3    arenas, library workspace, keys, counts,    the k-mer counters (bl_superkmer*.hip; the 128-bit one keeps its run count in 7) and
 //          the text (3)                                the text parser, which call the set operations while they hold them
 //   4      data; blpart::partition's histogram,        the set operations (bl_keylist.hpp), the owner splits, the table build and algebra, the
 //          offsets and bucket starts                   quantiles, select, format, the corrector, the graph (about 133 bytes per key in slot 4),
-//   5      library workspace (rocPRIM):                links, clean and the BGZF writer (slots, token areas and sizes of the members in flight):
-//          blh::exclusive_sum takes it                 none of them calls another while it holds 4-6
+//   5      library workspace (rocPRIM):                links, clean, the BGZF writer (slots, token areas and sizes of the members in flight)
+//          blh::exclusive_sum takes it                 and the steps (8 bytes per position; 88 per step for the GAF text): none of them calls
+//                                                      another while it holds 4-6
 //   6      counters, flags, statistics
 void* bl_ctx_scratch(bl_ctx* ctx, int slot, size_t bytes);
 

@@ -90,7 +90,9 @@ BL_DEV uint32_t index_entry(const TableView& t, uint32_t j)
 }
 
 // G searches in lockstep.  live bit g: search g takes part; the others answer 0 and read nothing.  out[g]: the stored count, 0 if absent.
-// Returns the mask of the keys found.
+// Returns the mask of the keys found.  SLOTS: out[g] is the slot of the found key instead (0 if absent: the mask tells), and no count is
+// read (bl_steps_core.hpp gathers the key's node from it).
+template <bool SLOTS = false>
 BL_DEV uint32_t search_group(const TableView& t, const uint64_t* lo, const uint64_t* hi, uint32_t live, uint32_t* out)
 {
     uint32_t b[G], e[G], e0[G];
@@ -134,7 +136,7 @@ BL_DEV uint32_t search_group(const TableView& t, const uint64_t* lo, const uint6
             uint64_t klo, khi;
             load_key(t, b[g], klo, khi);
             if (klo == lo[g] && khi == hi[g]) {
-                out[g] = t.counts[b[g]];
+                out[g] = SLOTS ? b[g] : t.counts[b[g]];
                 found |= 1u << g;
             }
         }

@@ -840,6 +840,9 @@ class CountTable:
             b._offsets_from_device = True
         u = Unitigs(b, d_out, sums[:n_unitigs], d_nodes[:n] if nodes else None, st.as_dict(), n_unitigs, n_bases)
         u.k, u._ctx, u._lib = int(k), self.ctx, self._lib
+        u._table = self  # read_steps looks the reads' k-mers up in the table the unitigs came from
+        if d_nodes is not None:
+            u._nodes = d_nodes[:n]
         if links:
             # the header's identity gives the record count before the call: one search pass, no sizing call
             bound = int(st.n_arcs) - int(st.n_linked_sides) + 2 * int(st.n_cycles)
@@ -913,7 +916,7 @@ class Unitigs:
         self.n_unitigs, self.n_bases = n_unitigs, n_bases
         self.link_offsets = self.links = self.link_stats = None
         self.k, self._ctx, self._lib = None, None, None
-        self._nodes, self._once = None, False
+        self._nodes, self._once, self._table = None, False, None
 
     def mark_raw(self, rule, marks, stats=None):
         """bl_unitigs_mark: `rule` a capi.CleanRule, `marks` a one-byte device tensor of n_unitigs elements, `stats` (or None) a
@@ -989,6 +992,77 @@ class Unitigs:
         """format_gfa(...) written to `path` (bl_text_write, as Batch.write; compress=True: as BGZF, bl_text_write_bgzf).  Returns the
         bytes written."""
         return self._ctx._write_text(self.format_gfa(prefix, first_number, header), path, False, compress, True)
+
+
+class ReadSteps:
+    """What Batch.read_steps returns: `steps`, an int64 device tensor [n_steps, 4] holding the 32-byte bl_read_step records in ascending
+    position (host() turns it into a numpy record array: pos, seq, end, offset, n_kmers, flags), and `stats` (n_valid, n_found, n_steps,
+    n_chains, n_linked, longest_step).  It keeps the batch and the unitigs the steps refer to."""
+
+    def __init__(self, batch, unitigs, steps, stats, d_offsets):
+        self.batch, self.unitigs, self.steps, self.stats = batch, unitigs, steps, stats
+        self.n_steps = int(steps.shape[0])
+        self._d_offsets = d_offsets
+        self._ctx, self._lib = batch.ctx, batch._lib
+
+    def host(self):
+        """a numpy record array of the steps (capi.READ_STEP_DTYPE)"""
+        return self.steps.cpu().numpy().view(np.uint8).reshape(-1, 32).copy().view(capi.READ_STEP_DTYPE).reshape(-1)
+
+    def link_support_raw(self, link_offsets, links, n_links, n_unitigs, support, stats=None):
+        """bl_link_support: `support` takes n_links uint32 words, `stats` (or None) is a capi.SupportStats.  Synchronous; the library checks
+        every argument."""
+        check(self._lib.bl_link_support(self._ctx._h, _ptr(self.steps) if self.n_steps else None, self.n_steps, _ptr(link_offsets), _ptr(links) if n_links else None,
+                                        int(n_links), int(n_unitigs), _ptr(support) if n_links else None, C.byref(stats) if stats is not None else None))
+
+    def link_support(self, unitigs=None):
+        """How many reads crossed every link record (bl_link_support): (support, stats).  support is an int32 device tensor [n_links]
+        holding uint32 counts, in the order of unitigs.links: a read's transition a -> b counts on the record a -> b and on its reverse
+        b^1 -> a^1 where the array holds them, a self-reverse record once.  stats: n_transitions, n_unmatched (transitions that found no
+        record).  `unitigs` (default: the ones the steps were made with) needs unitigs(k, links=True), with either value of once."""
+        import torch
+
+        u = unitigs if unitigs is not None else self.unitigs
+        if u.links is None:
+            raise ValueError("link_support needs unitigs(k, links=True)")
+        n_links = int(u.links.shape[0])
+        support = torch.empty(max(n_links, 1), dtype=torch.int32, device=self._ctx.torch_device)
+        st = capi.SupportStats()
+        self._ctx._inputs_ready()
+        self.link_support_raw(u.link_offsets, u.links, n_links, u.n_unitigs, support, st)
+        return support[:n_links], st.as_dict()
+
+    def format_gaf_raw(self, rule, out=None, capacity=0):
+        """bl_steps_format_gaf: `rule` a capi.GafRule, `out` a uint8 device tensor (None: sizing only) of `capacity` bytes.  Synchronous.
+        Returns n_bytes; the library checks every argument."""
+        nb = C.c_uint64()
+        u = self.unitigs
+        check(self._lib.bl_steps_format_gaf(self._ctx._h, self.batch._h, _ptr(self._d_offsets), _ptr(self.steps) if self.n_steps else None, self.n_steps,
+                                            _ptr(u.offsets), int(u.n_unitigs), C.byref(rule), _ptr(out), int(capacity), C.byref(nb)))
+        return int(nb.value)
+
+    def format_gaf(self, read_prefix="read", read_first_number=0, segment_prefix="", segment_first_number=0):
+        """The walks as GAF text made on the device (bl_steps_format_gaf): a uint8 device tensor, one line per chain of steps the read
+        made through link records.  Reads are named read_prefix + decimal(read_first_number + sequence index) (real read names are not
+        built), segments segment_prefix + decimal(segment_first_number + unitig): the names Unitigs.format_gfa prints for the same
+        prefix and first_number."""
+        import torch
+
+        rule = capi.GafRule()
+        rule.flags, rule.k = 0, self.unitigs.k
+        rule.read_prefix = read_prefix.encode("latin1") if isinstance(read_prefix, str) else bytes(read_prefix)
+        rule.segment_prefix = segment_prefix.encode("latin1") if isinstance(segment_prefix, str) else bytes(segment_prefix)
+        rule.read_first_number = int(read_first_number) & (2**64 - 1)
+        rule.segment_first_number = int(segment_first_number) & (2**64 - 1)
+        self._ctx._inputs_ready()
+        n_bytes = self.format_gaf_raw(rule)
+        out = torch.empty(max(n_bytes, 1), dtype=torch.uint8, device=self._ctx.torch_device)
+        self.format_gaf_raw(rule, out, n_bytes)
+        return out[:n_bytes]
+
+    def write_gaf(self, path, compress=False, **names):
+        """format_gaf(**names) written to `path` (bl_text_write; compress=True: as BGZF, bl_text_write_bgzf).  Returns the bytes written."""
+        return self._ctx._write_text(self.format_gaf(**names), path, False, compress, True)
 
 
 class ReadCounts:
@@ -1473,6 +1547,61 @@ class Batch:
         spans = self.read_spans(rc, k, trim, min_len, min_kmers, solid_min, solid_max, offsets=offsets)
         out, source_index = self.select(spans, keep_empty, offsets=offsets)
         return out, source_index, rc
+
+    # ---- threading: the reads' steps through the compacted graph
+    def read_steps_raw(self, table, k, flags, nodes, unitig_offsets, n_unitigs, steps, capacity, first=0, n=0, offsets=None, stats=None):
+        """bl_scan_read_steps: `nodes` / `unitig_offsets` are what CountTable.unitigs_raw filled for `table` and k, `steps` (or None with
+        capacity 0: the sizing call) takes `capacity` 32-byte records, `offsets` as read_counts_raw.  Synchronous; it waits for the scans
+        in flight itself.  Returns (rc, capi.StepStats): rc is BL_OK or BL_ERR_CAPACITY, any other error raises."""
+        stats = stats if stats is not None else capi.StepStats()
+        rc = self._lib.bl_scan_read_steps(self.ctx._h, self._h, int(first), int(n), int(k), int(flags), table._h, _ptr(nodes), _ptr(unitig_offsets),
+                                          int(n_unitigs), _ptr(offsets), _ptr(steps), int(capacity), C.byref(stats))
+        if rc != capi.BL_ERR_CAPACITY:
+            check(rc)
+        return rc, stats
+
+    # positions per call of read_steps: the library's own bound on a range
+    STEPS_CHUNK = 1 << 31
+
+    def read_steps(self, unitigs, offsets=None, chunk_positions=None):
+        """Every read threaded through the compacted graph (bl_scan_read_steps; the header states the rules): a ReadSteps.  `unitigs` is
+        what CountTable.unitigs(k, nodes=True) or unitigs(k, links=True) returned; the table it came from must still be open.  One
+        32-byte record per unitig visit: the k-mers at pos .. pos + n_kmers - 1 of sequence seq are the k-mers offset .. of unitig
+        end >> 1 read in orientation end & 1; flags has STEP_LINKED where the read came from the previous step over a link.  A sizing
+        call, then one allocation.  A batch of more than 2^31 positions (or chunk_positions) goes in chunks that end on sequence
+        boundaries, as read_quantiles cuts them, so that no step is cut.  offsets as read_counts."""
+        import torch
+
+        nodes = unitigs.nodes if unitigs.nodes is not None else unitigs._nodes
+        table = unitigs._table
+        if nodes is None or table is None or getattr(table, "_h", None) is None:
+            raise ValueError("read_steps needs unitigs(k, nodes=True) or unitigs(k, links=True) of a table that is still open")
+        if table.n_distinct == 0:
+            nodes = None
+        d_offsets = self._device_offsets(offsets)
+        limit = int(chunk_positions) if chunk_positions else self.STEPS_CHUNK
+        if self.n_bases <= limit:
+            chunks = [(0, self.n_bases)]
+        else:
+            host_offsets = offsets if offsets is not None else (self.offsets if self.offsets is not None and len(self.offsets) == self.n_seqs + 1 else None)
+            chunks = self._sequence_chunks(host_offsets, limit)
+        self.ctx._inputs_ready()
+        args = (table, unitigs.k, 0, nodes, unitigs.offsets if table.n_distinct else None, unitigs.n_unitigs)
+        sized = [self.read_steps_raw(*args, None, 0, b, e - b, d_offsets)[1].as_dict() if e > b else None for b, e in chunks]
+        total = sum(st["n_steps"] for st in sized if st)
+        steps = torch.empty((max(total, 1), 4), dtype=torch.int64, device=self.ctx.torch_device)  # (torch allocations are 16-byte aligned)
+        stats, at = dict(n_valid=0, n_found=0, n_steps=0, n_chains=0, n_linked=0, longest_step=0), 0
+        if not any(sized):  # no position at all: the library still checks the arguments
+            self.read_steps_raw(*args, None, 0, 0, 0, d_offsets)
+        for (b, e), st in zip(chunks, sized):
+            if not st:
+                continue
+            if st["n_steps"]:
+                self.read_steps_raw(*args, steps[at:], st["n_steps"], b, e - b, d_offsets)
+            at += st["n_steps"]
+            for name in stats:
+                stats[name] = max(stats[name], st[name]) if name == "longest_step" else stats[name] + st[name]
+        return ReadSteps(self, unitigs, steps[:total], stats, d_offsets)
 
     # ---- repair: single-substitution correction from a count table
     def read_edits_raw(self, table, k, flags, min_count, min_support, edits, capacity, first=0, n=0, stats=None):

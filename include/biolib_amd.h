@@ -310,7 +310,7 @@ int bl_ctx_last_scan_ms(bl_ctx* ctx, float* ms);
 /* Per-launch timing of the main scan kernel alone: after bl_ctx_kernel_timing(ctx, 1) every scan
  * brackets its tile kernel with a HIP event pair on the context's stream; bl_ctx_kernel_time
  * synchronises and returns the summed kernel time and the number of launches since timing was
- * switched on (switching it on or off resets both). */
+ * switched on (switching it on or off resets both).  bl_scan_read_steps brackets its node pass in the same way: one launch per call. */
 int bl_ctx_kernel_timing(bl_ctx* ctx, int enable);
 int bl_ctx_kernel_time(bl_ctx* ctx, double* total_ms, uint64_t* launches);
 /* Markers on the device's timeline that do not stop it.  bl_ctx_mark enqueues one behind everything issued so far on the
@@ -762,7 +762,8 @@ int bl_table_unitigs(bl_ctx* ctx, const bl_table* table, uint32_t k, bl_batch** 
  *   BL_ERR_INVALID with a message, nothing launched: NULL ctx, unitigs or rule; a batch of another context; unknown flags; rule->k even
  *   or outside 3 .. 63; name_prefix without a NUL inside its 16 bytes; reserved != 0; d_out not 16-byte aligned; d_unitig_offsets NULL
  *   with n_unitigs > 0; d_links NULL with n_links > 0.
- * NOT built: L: fields in BCALM FASTA headers, km:f:, GFA 2, paths and walks; of compression (bl_text_write_bgzf) a .gzi index, a
+ * NOT built: L: fields in BCALM FASTA headers, km:f:, GFA 2, P and W lines inside the GFA text (the reads' walks leave as GAF:
+ * bl_steps_format_gaf below); of compression (bl_text_write_bgzf) a .gzi index, a
  * run-length block header, matches across members, plain gzip output and compression levels.  (Tip, island and simple-bubble removal is
  * bl_unitigs_mark / bl_table_remove_unitigs below; superbubbles are not built.) */
 typedef struct bl_unitig_link { uint32_t from, to; /* (unitig << 1) | orientation */ } bl_unitig_link;
@@ -818,8 +819,9 @@ int bl_unitigs_format_gfa(bl_ctx* ctx, const bl_batch* unitigs, const uint64_t* 
  *   n_unitigs keeps its key).  The kept keys stay in order with their counts; all keys dropped gives a valid empty table.  *n_removed
  *   (nullable) = the input's n_distinct minus the output's.  No atomic decides a placement.  Synchronous.
  *   BL_ERR_INVALID: NULL ctx, table or out; a table of another context; d_nodes or d_marks NULL on a table that is not empty.
- * NOT built: complex bubbles (superbubbles), coverage-ratio rules such as relative-coverage tip clipping, read-threaded decisions, marking
- * and removal fused into bl_table_unitigs. */
+ * NOT built: complex bubbles (superbubbles), coverage-ratio rules such as relative-coverage tip clipping, read-threaded decisions (their
+ * evidence, the reads that crossed every link record, is bl_link_support below; no rule reads it yet), marking and removal fused into
+ * bl_table_unitigs. */
 enum { BL_CLEAN_TIPS = 1u << 0, BL_CLEAN_ISOLATED = 1u << 1, BL_CLEAN_BUBBLES = 1u << 2 };
 enum { BL_MARK_KEEP = 0, BL_MARK_TIP = 1, BL_MARK_ISOLATED = 2, BL_MARK_BUBBLE = 3 };
 typedef struct bl_clean_rule {
@@ -833,6 +835,95 @@ int bl_unitigs_mark(bl_ctx* ctx, const uint64_t* d_unitig_offsets /* n_unitigs +
                     const bl_clean_rule* rule, uint8_t* d_marks /* n_unitigs */, bl_clean_stats* stats /* nullable */);
 int bl_table_remove_unitigs(bl_ctx* ctx, const bl_table* table, const bl_unitig_node* d_nodes /* n_distinct */, const uint8_t* d_marks,
                             uint64_t n_unitigs, bl_table** out, uint64_t* n_removed /* nullable */);
+
+/* Back from the reads to the graph: where in the compacted graph every k-mer of a read lies, contracted to one record per unitig visit
+ * (what read-supported cleaning, path and walk output, pseudo-alignment, bubble phasing and threading long reads through a short-read
+ * graph start from).  Terms as above: L(u) = the keys of unitig u; oriented(u, 0) its string, oriented(u, 1) its reverse complement.
+ * NODE  let f be the forward k-mer at position p, valid by bl_scan_kmers128's rules, c = canon(f), s = (f != c).  If c is at slot i of
+ *   the table and d_nodes[i].unitig = u < n_unitigs, with rank r and flip fl, the position has the node (u, o, off): o = s XOR fl,
+ *   off = r where o = 0 and L(u) - 1 - r where o = 1.  Otherwise it has no node.  The k bases at p are oriented(u, o)[off : off + k].
+ * STEP  position p + 1 continues p iff both lie in the same sequence, both have nodes, the nodes have the same u and the same o, and
+ *   off(p + 1) = off(p) + 1.  A step is a maximal run of positions inside the range in which each continues its predecessor.  The test is
+ *   arithmetic only: once round a cyclic unitig (off L - 1 -> off 0) starts a new step, and so does a hairpin u+ -> u-.
+ * FLAGS  BL_STEP_LINKED iff position pos - 1 lies in the same sequence and has a node and pos does not continue it: on a table that is
+ *   the unitigs' own the read crossed the link record (previous step's end -> this end).  BL_STEP_CONTINUED only where pos = first and
+ *   `first` continues first - 1: the range cut a step.  The node at first - 1 is looked up for both flags although it lies in front of
+ *   the range.  A call over the whole batch never sets CONTINUED.  The records of consecutive ranges concatenated, every CONTINUED record
+ *   folded into its predecessor (n_kmers added, record dropped), are the records of one call over the union, wherever the cut falls.
+ *
+ * bl_scan_read_steps: the range rules are bl_scan_kmer_counts's (n = 0: to the end, at most 2^31 positions).  k odd, 3 .. 63.  The
+ *   canonical form is always used (the table holds canonical keys): BL_FLAG_CANONICAL may be set or not, BL_FLAG_SYNC is accepted,
+ *   BL_FLAG_DROP_LAST and unknown bits are refused.  d_nodes (n_distinct records), d_unitig_offsets (n_unitigs + 1 words) and n_unitigs
+ *   are what bl_table_unitigs wrote for this table and k.  d_offsets as bl_scan_read_counts: the device copy of the batch's n_seqs + 1
+ *   offsets, NULL for a single-sequence or a fixed-read-length batch; the sequence of a position is the last one whose offset is <= it.
+ *   Steps are written to d_steps (16-byte aligned) in strictly ascending pos; nothing is written at or beyond `capacity`; d_steps NULL
+ *   with capacity 0 is the sizing call; n_steps > capacity: BL_ERR_CAPACITY with complete stats and d_steps untouched.  stats (nullable,
+ *   host): n_valid, the valid k-mers of the range; n_found, its positions with a node; n_steps; n_chains, the steps with neither flag;
+ *   n_linked; longest_step (in k-mers).  Synchronous; it first waits for the context's scans in flight, like bl_scan_read_edits.
+ *   Temporaries come from the context's scratch: 8 bytes per position and 8 per step.  With bl_ctx_kernel_timing on, the node pass is
+ *   one launch of bl_ctx_kernel_time's sum.  An empty range, an empty batch and an empty table
+ *   succeed: nothing has a node, zero steps.  No atomic decides a placement: a rerun is bit-identical.  The arrays are trusted for
+ *   content, not for safety (select's policy): a node at or above n_unitigs is no node, offsets are only subtracted and compared, and no
+ *   byte outside the stated sizes is read or written.
+ *   BL_ERR_INVALID with a message, nothing launched: NULL ctx, batch or table; a batch or table of another context; k even or outside
+ *   3 .. 63; 2k above the table's key_bits; a table of one-word keys with k > 31; 2^31 keys or more; n_unitigs above n_distinct; d_nodes
+ *   or d_unitig_offsets NULL on a table that is not empty; d_offsets NULL on a batch that needs it; d_steps misaligned, or NULL with a
+ *   capacity; bad flags; a range that starts beyond the batch or holds more than 2^31 positions.
+ * bl_link_support: the reads that crossed every link record — the evidence of a read-threaded cleaning rule (no such rule is built).
+ *   d_link_offsets, d_links and n_links are bl_unitig_links's, with either value of BL_LINKS_ONCE.  d_support[n_links] is zeroed by the
+ *   call.  For every i with d_steps[i + 1].flags & BL_STEP_LINKED and d_steps[i].seq == d_steps[i + 1].seq, with a = d_steps[i].end and
+ *   b = d_steps[i + 1].end: 1 is added to every record present among (a -> b) and its reverse (b ^ 1 -> a ^ 1); a self-reverse record gets
+ *   the 1 once.  The records are looked for in out(a) and out(b ^ 1); only the first four records of an end are read.  A pair with an end
+ *   at or above 2 * n_unitigs is ignored, link offsets are clamped to n_links.  stats (nullable, host): n_transitions, the pairs
+ *   considered; n_unmatched, those that found no record.  Sums wrap mod 2^32; they are integer atomic adds, whose order does not show.
+ *   Synchronous.  BL_ERR_INVALID: NULL ctx; d_steps NULL with n_steps > 0 or misaligned; n_unitigs >= 2^31; d_link_offsets NULL with
+ *   n_unitigs > 0; d_links or d_support NULL with n_links > 0.
+ * bl_steps_format_gaf: the walks as GAF text made on the device.  A chain is a step without BL_STEP_LINKED and every following step that
+ *   has it (the first step of the array begins a chain whatever it carries).  One line per chain, every terminator LF:
+ *     <qname>\t<qlen>\t<qstart>\t<qend>\t+\t<path>\t<plen>\t<pstart>\t<pend>\t<m>\t<m>\t255\n
+ *   qname = read_prefix + decimal(read_first_number + seq); qlen = the sequence's length from d_offsets, the fixed read length or the
+ *   batch; qstart = the first step's pos relative to its sequence; K = the sum of n_kmers over the chain; qend = qstart + K + k - 1;
+ *   path = for every step '>' where o = 0 and '<' where o = 1, then segment_prefix + decimal(segment_first_number + u) — the names
+ *   bl_unitigs_format_gfa prints for the same prefix and number; plen = the sum of L(u) over the chain's steps, plus k - 1; pstart = the
+ *   first step's offset; pend = pstart + K + k - 1; m = K + k - 1.  Numbers wrap at 2^64 as in bl_batch_format.  On consistent inputs
+ *   the spelled path's bytes [pstart, pend) are the read's bytes [qstart, qend).  Per-chain aggregates are differences of prefix sums
+ *   over the steps.  A step with BL_STEP_CONTINUED is refused with a message: the caller folds first.  `batch` and d_offsets are those
+ *   of bl_scan_read_steps.  Sizing and refusals follow bl_unitigs_format_gfa: *n_bytes (nullable) always receives the size of the text;
+ *   d_out NULL: sizing only; capacity < *n_bytes: BL_ERR_CAPACITY, d_out untouched; no byte at or behind d_out[*n_bytes] is written.
+ *   Numbers are only printed: garbage steps print garbage and touch nothing else (a unitig at or above n_unitigs has L = 0, a sequence
+ *   at or above n_seqs length 0).  bl_text_write / bl_text_write_bgzf carry the text unchanged.  Synchronous; 88 bytes of scratch per step.
+ *   BL_ERR_INVALID with a message, nothing launched: NULL ctx, batch or rule; a batch of another context; flags != 0; rule->k even or
+ *   outside 3 .. 63; a prefix without a NUL inside its 16 bytes; reserved != 0; d_out or d_steps not 16-byte aligned; d_steps NULL with
+ *   n_steps > 0; d_unitig_offsets NULL with n_unitigs > 0; d_offsets NULL on a batch that needs it.
+ * NOT built: real read names from a bl_text_index (names are generated), the cs / cg tags, mapping qualities, a strand other than +. */
+enum { BL_STEP_LINKED = 1u << 0, BL_STEP_CONTINUED = 1u << 1 };
+typedef struct bl_read_step {   /* 32 bytes, 16-byte aligned arrays */
+    uint64_t pos;      /* batch-relative position of the step's first k-mer (origin not added) */
+    uint64_t seq;      /* index of the sequence */
+    uint32_t end;      /* (u << 1) | o: read like a link record's `to` */
+    uint32_t offset;   /* off of the first k-mer, counted along oriented(u, o) */
+    uint32_t n_kmers;  /* positions of the step */
+    uint32_t flags;    /* BL_STEP_LINKED | BL_STEP_CONTINUED */
+} bl_read_step;
+typedef struct bl_step_stats { uint64_t n_valid, n_found, n_steps, n_chains, n_linked, longest_step, reserved[2]; } bl_step_stats;
+typedef struct bl_support_stats { uint64_t n_transitions, n_unmatched, reserved[2]; } bl_support_stats;
+typedef struct bl_gaf_rule {
+    uint32_t flags, k;           /* flags: 0; k: odd, 3 .. 63, the k of the steps */
+    char     read_prefix[16];    /* qname: prefix + decimal(read_first_number + seq), NUL-terminated */
+    char     segment_prefix[16]; /* segment names as bl_gfa_rule's name_prefix / first_number */
+    uint64_t read_first_number, segment_first_number;
+    uint64_t reserved;           /* 0 */
+} bl_gaf_rule;
+int bl_scan_read_steps(bl_ctx* ctx, const bl_batch* batch, uint64_t first, uint64_t n, uint32_t k, uint32_t flags, const bl_table* table,
+                       const bl_unitig_node* d_nodes /* n_distinct */, const uint64_t* d_unitig_offsets /* n_unitigs + 1 */, uint64_t n_unitigs,
+                       const uint64_t* d_offsets /* nullable */, bl_read_step* d_steps /* nullable: sizing */, uint64_t capacity,
+                       bl_step_stats* stats /* nullable */);
+int bl_link_support(bl_ctx* ctx, const bl_read_step* d_steps, uint64_t n_steps, const uint64_t* d_link_offsets /* 2 n_unitigs + 1 */,
+                    const bl_unitig_link* d_links, uint64_t n_links, uint64_t n_unitigs, uint32_t* d_support /* n_links */,
+                    bl_support_stats* stats /* nullable */);
+int bl_steps_format_gaf(bl_ctx* ctx, const bl_batch* batch, const uint64_t* d_offsets /* nullable */, const bl_read_step* d_steps, uint64_t n_steps,
+                        const uint64_t* d_unitig_offsets /* n_unitigs + 1 */, uint64_t n_unitigs, const bl_gaf_rule* rule, uint8_t* d_out,
+                        uint64_t capacity, uint64_t* n_bytes);
 
 /* The chain's exit: reads and unitigs leave as FASTA / FASTQ text made on the device, names and qualities included.
  *
