@@ -298,14 +298,6 @@ int zero_result(bl_ctx* c, bl_result* user, uint32_t flags)
     return BL_OK;
 }
 
-int check_range(const bl_batch* b, uint64_t first, uint64_t n, uint64_t& end)
-{
-    if (first > b->n_bases) return fail(BL_ERR_INVALID, "range starts beyond the batch");
-    end = (n == 0 || n > b->n_bases - first) ? b->n_bases : first + n;  // first + n cannot wrap here
-    if (end - first > (1ull << 31)) return fail(BL_ERR_INVALID, "a scan range may hold at most 2^31 positions; split it");
-    return BL_OK;
-}
-
 int make_start_bits(bl_ctx* c, bl_batch* b, const uint64_t* offsets, uint64_t n_seqs, uint64_t read_len)
 {
     const uint64_t n_words = (b->n_bases + 31) / 32 + 4;
@@ -813,7 +805,7 @@ int bl_batch_from_device(bl_ctx* c, const void* d_bases, uint64_t n_bases, const
     bl_batch* b = nullptr;
     int rc = new_batch(c, n_bases, out, b);
     if (rc != BL_OK) return rc;
-    if ((n_bases && !d_bases) || (reinterpret_cast<uintptr_t>(d_bases) & 15)) {
+    if ((n_bases && !d_bases) || blh::misaligned16(d_bases)) {
         bl_batch_destroy(b);
         return fail(BL_ERR_INVALID, "d_bases must be a non-NULL, 16-byte aligned device pointer");
     }
@@ -958,13 +950,32 @@ int bl_batch_download(bl_batch* b, uint64_t first, uint64_t n, char* out)
 
 // ---------------------------------------------------------------------------------------- scans
 
+// One timed pass over the tiles and the fold of its digest: what the calls that write per position share (the two-pass calls have
+// scan_two_pass128 and scan_windows).  launch(): enqueues on c->stream; c->shards() is valid by then.  kernel: its name in the error
+// text, read after a launch has failed (bl_scan_read_counts names the one of its two kernels that did).
+extern "C++" {  // (a template cannot have the C linkage of the entry points around it)
+template <typename Launch>
+static int scan_one_pass(bl_ctx* c, Launch&& launch, const char* const& kernel, uint32_t add_mask, uint32_t flags, bl_result* result)
+{
+    int rc = begin_scan(c);
+    if (rc != BL_OK) return rc;
+    rc = kernel_event(c, true);
+    if (rc != BL_OK) return rc;
+    const hipError_t e = launch();
+    if (e != hipSuccess) return fail(BL_ERR_HIP, std::string(kernel) + ": " + hipGetErrorString(e));
+    rc = kernel_event(c, false);
+    if (rc != BL_OK) return rc;
+    return end_scan(c, add_mask, result, false, 0, flags);
+}
+}  // extern "C++"
+
 int bl_scan_kmers(bl_ctx* c, const bl_batch* b, uint64_t first, uint64_t n, uint32_t k, uint64_t seed, uint32_t flags,
                   uint64_t* d_values, uint64_t* d_hashes, uint8_t* d_valid, bl_result* result)
 {
     if (!c || !b || b->ctx != c) return fail(BL_ERR_INVALID, "ctx/batch is NULL or the batch belongs to another context");
     if (k < 1 || k > bl::MAX_UNIT) return fail(BL_ERR_INVALID, "k must be in [1, 32] (KmerType = uint64_t)");
     uint64_t end;
-    int rc = check_range(b, first, n, end);
+    int rc = blh::range_end(b->n_bases, first, n, "a scan range", end);
     if (rc != BL_OK) return rc;
     if (end <= first) return zero_result(c, result, flags);
     rc = ensure_start_bits(c, b);
@@ -984,19 +995,14 @@ int bl_scan_kmers(bl_ctx* c, const bl_batch* b, uint64_t first, uint64_t n, uint
     p.out_value = d_values;
     p.out_hash = d_hashes;
     p.out_valid = d_valid;
-    rc = begin_scan(c);
-    if (rc != BL_OK) return rc;
-    p.shards = c->shards();
     // 2,048 workgroups striding over the tiles (1.6 resident sets at five workgroups per CU).  One resident set exactly — 1,280 — measured
     // SLOWER on one lane (532 against 567 Gbp/s, A/B on one box) and the same on two (654): the 15 % a second lane gives this scan is not its tail.
     const int n_blocks = p.n_tiles < 256 * 8 ? p.n_tiles : 256 * 8;
-    rc = kernel_event(c, true);
-    if (rc != BL_OK) return rc;
-    hipError_t e = bl::launch_kmers(p, n_blocks, c->stream);
-    if (e != hipSuccess) return fail(BL_ERR_HIP, std::string("kmer_kernel: ") + hipGetErrorString(e));
-    rc = kernel_event(c, false);
-    if (rc != BL_OK) return rc;
-    return end_scan(c, /*add_mask: count, sum*/ (1u << 0) | (1u << 3), result, false, 0, flags);
+    const auto launch = [&] {
+        p.shards = c->shards();
+        return bl::launch_kmers(p, n_blocks, c->stream);
+    };
+    return scan_one_pass(c, launch, "kmer_kernel", /*add_mask: count, sum*/ (1u << 0) | (1u << 3), flags, result);
 }
 
 // ---- 128-bit k-mers (k <= 64): bl_kmers128.hip
@@ -1007,9 +1013,9 @@ static int prepare_kmers128(bl_ctx* c, const bl_batch* b, uint64_t first, uint64
     empty = false;
     if (!c || !b || b->ctx != c) return fail(BL_ERR_INVALID, "ctx/batch is NULL or the batch belongs to another context");
     if (k < 1 || k > bl::MAX_UNIT128) return fail(BL_ERR_INVALID, "k must be in [1, 64] (KmerType = __uint128_t)");
-    if (reinterpret_cast<uintptr_t>(d_values) % 16 != 0) return fail(BL_ERR_INVALID, "d_values must be 16-byte aligned (one __uint128_t per record)");
+    if (blh::misaligned16(d_values)) return fail(BL_ERR_INVALID, "d_values must be 16-byte aligned (one __uint128_t per record)");
     uint64_t end;
-    int rc = check_range(b, first, n, end);
+    int rc = blh::range_end(b->n_bases, first, n, "a scan range", end);
     if (rc != BL_OK) return rc;
     if (end <= first) {
         empty = true;
@@ -1089,44 +1095,39 @@ int bl_scan_kmers128(bl_ctx* c, const bl_batch* b, uint64_t first, uint64_t n, u
     p.out_value = d_values;
     p.out_hash = d_hashes;
     p.out_valid = d_valid;
-    rc = begin_scan(c);
-    if (rc != BL_OK) return rc;
-    p.shards = c->shards();
-    rc = kernel_event(c, true);
-    if (rc != BL_OK) return rc;
-    hipError_t e = bl::launch_kmers128(p, c->stream);
-    if (e != hipSuccess) return fail(BL_ERR_HIP, std::string("kmer128_kernel: ") + hipGetErrorString(e));
-    rc = kernel_event(c, false);
-    if (rc != BL_OK) return rc;
-    return end_scan(c, /*add_mask: count, sum*/ (1u << 0) | (1u << 3), result, false, 0, flags);
+    const auto launch = [&] {
+        p.shards = c->shards();
+        return bl::launch_kmers128(p, c->stream);
+    };
+    return scan_one_pass(c, launch, "kmer128_kernel", /*add_mask: count, sum*/ (1u << 0) | (1u << 3), flags, result);
+}
+
+// what the two scans that look k-mers up check of their table (a NULL context is left to prepare_kmers128, which refuses it)
+static int table_answers(bl_ctx* c, const bl_table* table, uint32_t k)
+{
+    if (!table) return fail(BL_ERR_INVALID, "table is NULL");
+    if (c) BLH_OK(blh::table_owner(table->ctx, c));
+    return blh::table_takes_k(table->view.key_words, table->view.key_bits, k);
 }
 
 // the k-mers of bl_scan_kmers128 looked up in a count table inside the scan: bl_lookup.hip
 int bl_scan_kmer_counts(bl_ctx* c, const bl_batch* b, uint64_t first, uint64_t n, uint32_t k, uint32_t flags, const bl_table* table, uint32_t* d_counts,
                         uint8_t* d_valid, bl_result* result)
 {
-    if (!table) return fail(BL_ERR_INVALID, "table is NULL");
-    if (c && table->ctx != c) return fail(BL_ERR_INVALID, "the table belongs to another context");
-    if (table->view.key_words == 1 && k > 32) return fail(BL_ERR_INVALID, "a table of one-word keys takes k <= 32");
-    if (k >= 1 && 2 * k > table->view.key_bits)
-        return fail(BL_ERR_INVALID, "2k = " + std::to_string(2 * k) + " exceeds the table's key_bits = " + std::to_string(table->view.key_bits));
+    int rc = table_answers(c, table, k);
+    if (rc != BL_OK) return rc;
     bllk::ScanCountParams p{};
     bool empty;
-    int rc = prepare_kmers128(c, b, first, n, k, 0, flags, nullptr, p.km, result, empty);
+    rc = prepare_kmers128(c, b, first, n, k, 0, flags, nullptr, p.km, result, empty);
     if (rc != BL_OK || empty) return rc;
     p.table = table->view;
     p.out_counts = d_counts;
     p.out_valid = d_valid;
-    rc = begin_scan(c);
-    if (rc != BL_OK) return rc;
-    p.km.shards = c->shards();
-    rc = kernel_event(c, true);
-    if (rc != BL_OK) return rc;
-    hipError_t e = bllk::launch_scan_counts(p, c->stream);
-    if (e != hipSuccess) return fail(BL_ERR_HIP, std::string("scan_counts_kernel: ") + hipGetErrorString(e));
-    rc = kernel_event(c, false);
-    if (rc != BL_OK) return rc;
-    return end_scan(c, /*add_mask: count, found, sum*/ (1u << 0) | (1u << 2) | (1u << 3), result, false, 0, flags);
+    const auto launch = [&] {
+        p.km.shards = c->shards();
+        return bllk::launch_scan_counts(p, c->stream);
+    };
+    return scan_one_pass(c, launch, "scan_counts_kernel", /*add_mask: count, found, sum*/ (1u << 0) | (1u << 2) | (1u << 3), flags, result);
 }
 
 // bl_scan_kmer_counts reduced per sequence inside the scan: bl_read_counts.hip
@@ -1134,20 +1135,16 @@ int bl_scan_read_counts(bl_ctx* c, const bl_batch* b, uint64_t first, uint64_t n
                         const uint64_t* d_offsets, uint32_t mode, bl_read_counts* d_records, bl_result* result)
 {
     static_assert(sizeof(bl_read_counts) == sizeof(blrc::Record) && alignof(blrc::Record) == 16, "the kernel's record is the header's");
-    if (!table) return fail(BL_ERR_INVALID, "table is NULL");
-    if (c && table->ctx != c) return fail(BL_ERR_INVALID, "the table belongs to another context");
-    if (table->view.key_words == 1 && k > 32) return fail(BL_ERR_INVALID, "a table of one-word keys takes k <= 32");
-    if (k >= 1 && 2 * k > table->view.key_bits)
-        return fail(BL_ERR_INVALID, "2k = " + std::to_string(2 * k) + " exceeds the table's key_bits = " + std::to_string(table->view.key_bits));
+    int rc = table_answers(c, table, k);
+    if (rc != BL_OK) return rc;
     if (min_count == 0) return fail(BL_ERR_INVALID, "min_count must be at least 1");
     if (mode != BL_READ_COUNTS_INIT && mode != BL_READ_COUNTS_ACCUMULATE) return fail(BL_ERR_INVALID, "mode is BL_READ_COUNTS_INIT or BL_READ_COUNTS_ACCUMULATE");
     if (!d_records) return fail(BL_ERR_INVALID, "d_records is NULL");
-    if (reinterpret_cast<uintptr_t>(d_records) % 16 != 0) return fail(BL_ERR_INVALID, "d_records must be 16-byte aligned");
-    if (b && !d_offsets && b->n_seqs > 1 && b->read_len == 0)
-        return fail(BL_ERR_INVALID, "d_offsets is NULL: only a single-sequence or a fixed-read-length batch finds its sequences without the offsets");
+    if (blh::misaligned16(d_records)) return fail(BL_ERR_INVALID, "d_records must be 16-byte aligned");
+    if (b) BLH_OK(blh::offsets_needed(d_offsets, b->n_seqs, b->read_len));
     blrc::ReadCountParams p{};
     bool empty;
-    int rc = prepare_kmers128(c, b, first, n, k, 0, flags, nullptr, p.km, result, empty);
+    rc = prepare_kmers128(c, b, first, n, k, 0, flags, nullptr, p.km, result, empty);
     if (rc != BL_OK || empty) return rc;
     p.table = table->view;
     p.min_count = min_count;
@@ -1155,18 +1152,15 @@ int bl_scan_read_counts(bl_ctx* c, const bl_batch* b, uint64_t first, uint64_t n
     p.n_seqs = b->n_seqs;  // >= 1: the range is not empty
     p.read_len = d_offsets ? 0 : b->read_len;
     p.records = reinterpret_cast<blrc::Record*>(d_records);
-    rc = begin_scan(c);
-    if (rc != BL_OK) return rc;
-    p.km.shards = c->shards();
-    rc = kernel_event(c, true);
-    if (rc != BL_OK) return rc;
-    hipError_t e = mode == BL_READ_COUNTS_INIT ? blrc::launch_read_counts_init(p, c->stream) : hipSuccess;
-    if (e != hipSuccess) return fail(BL_ERR_HIP, std::string("read_counts_init_kernel: ") + hipGetErrorString(e));
-    e = blrc::launch_read_counts(p, c->stream);
-    if (e != hipSuccess) return fail(BL_ERR_HIP, std::string("read_counts_kernel: ") + hipGetErrorString(e));
-    rc = kernel_event(c, false);
-    if (rc != BL_OK) return rc;
-    return end_scan(c, /*add_mask: count, found, sum*/ (1u << 0) | (1u << 2) | (1u << 3), result, false, 0, flags);
+    const char* kernel = "read_counts_init_kernel";
+    const auto launch = [&] {
+        p.km.shards = c->shards();
+        const hipError_t e = mode == BL_READ_COUNTS_INIT ? blrc::launch_read_counts_init(p, c->stream) : hipSuccess;
+        if (e != hipSuccess) return e;
+        kernel = "read_counts_kernel";
+        return blrc::launch_read_counts(p, c->stream);
+    };
+    return scan_one_pass(c, launch, kernel, /*add_mask: count, found, sum*/ (1u << 0) | (1u << 2) | (1u << 3), flags, result);
 }
 
 int bl_scan_hash_sample128(bl_ctx* c, const bl_batch* b, uint64_t first, uint64_t n, uint32_t k, uint64_t seed, uint64_t threshold, uint32_t flags,
@@ -1234,7 +1228,7 @@ static int scan_windows(int mode, bl_ctx* c, const bl_batch* b, uint64_t first, 
     if (unit < 1 || unit > bl::MAX_UNIT) return fail(BL_ERR_INVALID, "hashed unit length must be in [1, 32]");
     if (w < 1 || w > bl::MAX_W) return fail(BL_ERR_INVALID, "window must be in [1, 64]");
     uint64_t end;
-    int rc = check_range(b, first, n, end);
+    int rc = blh::range_end(b->n_bases, first, n, "a scan range", end);
     if (rc != BL_OK) return rc;
     if (end <= first) return zero_result(c, result, flags);
     p.bases = b->bases;

@@ -99,9 +99,9 @@ __global__ __launch_bounds__(CTPB) void write_kernel(const bllnk::Node* __restri
 
 namespace {
 
+using blh::blocks_for;
 using blh::hip_rc;
 using blh::invalid;
-unsigned blocks_for(uint64_t threads) { return (unsigned)((threads + CTPB - 1) / CTPB); }
 
 template <int W>
 int remove_marked(bl_ctx* ctx, const bl_table* table, const bllnk::Node* nodes, const uint8_t* marks, uint64_t n_unitigs, bl_table** out, uint64_t* n_removed)
@@ -110,7 +110,7 @@ int remove_marked(bl_ctx* ctx, const bl_table* table, const bllnk::Node* nodes, 
     hipStream_t s = bl_ctx_stream(ctx);
     const uint64_t n = table->view.n;
     const uint64_t n_tiles = tiles_of<ROWS>(n);
-    ull n_out = 0;
+    uint64_t n_out = 0;
     uint64_t* totals = nullptr;
     uint64_t* bases = nullptr;
     if (n_tiles) {
@@ -119,20 +119,16 @@ int remove_marked(bl_ctx* ctx, const bl_table* table, const bllnk::Node* nodes, 
         if (!totals) return bl_set_error(BL_ERR_OOM, "scratch allocation failed");
         bases = totals + n_tiles + 1;
         BLH_TRY(hipMemsetAsync(totals + n_tiles, 0, sizeof(uint64_t), s));
-        hipLaunchKernelGGL(count_kernel<ROWS>, dim3(blocks_for(n_tiles * 64)), dim3(CTPB), 0, s, nodes, marks, n_unitigs, n, n_tiles, totals);
+        hipLaunchKernelGGL(count_kernel<ROWS>, dim3(blocks_for(n_tiles * 64, CTPB)), dim3(CTPB), 0, s, nodes, marks, n_unitigs, n, n_tiles, totals);
         BLH_TRY(hipGetLastError());
-        const int rc = blh::exclusive_sum(ctx, totals, bases, (size_t)(n_tiles + 1), s);
-        if (rc != BL_OK) return rc;
-        BLH_TRY(hipMemcpyAsync(&n_out, bases + n_tiles, sizeof(n_out), hipMemcpyDeviceToHost, s));
-        BLH_TRY(hipStreamSynchronize(s));
+        BLH_OK(blh::exclusive_sum_total(ctx, totals, bases, (size_t)(n_tiles + 1), s, &n_out));
         if (n_out > n) return bl_set_error(BL_ERR_INTERNAL, "the count pass kept more keys than the table holds");
     }
     bl_table* t = nullptr;
-    const int rc = bllk::new_table(ctx, table->view.key_words, table->view.key_bits, n_out, &t);
-    if (rc != BL_OK) return rc;
+    BLH_OK(bllk::new_table(ctx, table->view.key_words, table->view.key_bits, n_out, &t));
     hipError_t e = hipSuccess;
     if (n_out) {
-        hipLaunchKernelGGL((write_kernel<W, ROWS>), dim3(blocks_for(n_tiles * 64)), dim3(CTPB), 0, s, nodes, marks, n_unitigs, table->view.keys,
+        hipLaunchKernelGGL((write_kernel<W, ROWS>), dim3(blocks_for(n_tiles * 64, CTPB)), dim3(CTPB), 0, s, nodes, marks, n_unitigs, table->view.keys,
                            table->view.counts, n, n_tiles, bases, (uint64_t)n_out, const_cast<uint64_t*>(t->view.keys), const_cast<uint32_t*>(t->view.counts));
         e = hipGetLastError();
     }
@@ -176,7 +172,7 @@ extern "C" int bl_unitigs_mark(bl_ctx* ctx, const uint64_t* d_unitig_offsets, co
     Rule r{rule->flags, rule->k, rule->max_tip_keys, rule->max_isolated_keys, rule->max_isolated_mean, rule->max_bubble_keys, rule->max_bubble_diff, 0};
     ull stripes[STRIPES * STRIPE_WORDS] = {}, host[5] = {};
     BLH_TRY(hipMemsetAsync(d_counters, 0, sizeof(stripes), s));
-    hipLaunchKernelGGL(mark_kernel, dim3(blocks_for(n_unitigs)), dim3(CTPB), 0, s, g, r, d_marks, d_counters);
+    hipLaunchKernelGGL(mark_kernel, dim3(blocks_for(n_unitigs, CTPB)), dim3(CTPB), 0, s, g, r, d_marks, d_counters);
     BLH_TRY(hipGetLastError());
     BLH_TRY(hipMemcpyAsync(stripes, d_counters, sizeof(stripes), hipMemcpyDeviceToHost, s));
     BLH_TRY(hipStreamSynchronize(s));
@@ -200,7 +196,7 @@ extern "C" int bl_table_remove_unitigs(bl_ctx* ctx, const bl_table* table, const
     if (n_removed) *n_removed = 0;
     if (!ctx || !table) return invalid("ctx or table is NULL");
     if (!out) return invalid("out is NULL");
-    if (table->ctx != ctx) return invalid("the table belongs to another context");
+    BLH_OK(blh::table_owner(table->ctx, ctx));
     if (table->view.n && (!d_nodes || !d_marks)) return invalid("d_nodes or d_marks is NULL on a table that is not empty");
     const bllnk::Node* nodes = reinterpret_cast<const bllnk::Node*>(d_nodes);
     return table->view.key_words == 2 ? remove_marked<2>(ctx, table, nodes, d_marks, n_unitigs, out, n_removed)

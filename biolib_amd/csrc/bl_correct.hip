@@ -145,9 +145,9 @@ __global__ __launch_bounds__(CTPB) void apply_kernel(const Edit* edits, ull n_ed
 
 namespace {
 
-int invalid(const std::string& msg) { return bl_set_error(BL_ERR_INVALID, msg.c_str()); }
-unsigned blocks_for(ull threads) { return (unsigned)((threads + CTPB - 1) / CTPB); }
-size_t round16(size_t b) { return (b + 15) & ~(size_t)15; }
+using blh::blocks_for;
+using blh::invalid;
+using blh::round16;
 static_assert(sizeof(ull) == sizeof(uint64_t), "blh::exclusive_sum sums the unit's counters as the 8-byte words they are");
 
 }  // namespace
@@ -159,30 +159,25 @@ extern "C" int bl_scan_read_edits(bl_ctx* ctx, const bl_batch* batch, uint64_t f
 {
     using namespace blcr;
     if (!ctx || !batch || !table) return invalid("ctx, batch or table is NULL");
-    bl_ctx* owner = nullptr;
-    uint64_t n_bases = 0, unused[2];
-    bl_batch_describe(batch, &owner, &n_bases, &unused[0], &unused[1]);
-    if (owner != ctx) return invalid("the batch belongs to another context");
-    if (table->ctx != ctx) return invalid("the table belongs to another context");
+    blh::BatchView view;
+    BLH_OK(blh::batch_view(ctx, batch, view));
+    const uint64_t n_bases = view.n_bases;
+    BLH_OK(blh::table_owner(table->ctx, ctx));
     if (!d_edits && capacity != 0) return invalid("d_edits is NULL with a capacity: the counting call passes capacity 0");
-    if (reinterpret_cast<uintptr_t>(d_edits) & 15) return invalid("d_edits must be 16-byte aligned");
+    if (blh::misaligned16(d_edits)) return invalid("d_edits must be 16-byte aligned");
     if (k < 1 || k > (uint32_t)bl::MAX_UNIT128) return invalid("k must be in [1, 64]");
-    if (table->view.key_words == 1 && k > 32) return invalid("a table of one-word keys takes k <= 32");
-    if (2 * k > table->view.key_bits) return invalid("2k = " + std::to_string(2 * k) + " exceeds the table's key_bits = " + std::to_string(table->view.key_bits));
+    BLH_OK(blh::table_takes_k(table->view.key_words, table->view.key_bits, k));
     if (min_count == 0) return invalid("min_count must be at least 1");
     if (min_support < 1 || min_support > k) return invalid("min_support must be in [1, k]");
     if (flags & ~(uint32_t)(BL_FLAG_CANONICAL | BL_FLAG_SYNC)) return invalid("flags: BL_FLAG_CANONICAL only (BL_FLAG_SYNC is accepted)");
-    if (first > n_bases) return invalid("range starts beyond the batch");
-    const uint64_t end = (n == 0 || n > n_bases - first) ? n_bases : first + n;
-    if (end - first > (1ull << 31)) return invalid("a scan range may hold at most 2^31 positions; split it");
+    uint64_t end = 0;
+    BLH_OK(blh::range_end(n_bases, first, n, "a scan range", end));
     if (stats) *stats = bl_edit_stats{};
-    int rc = bl_ctx_sync(ctx);  // the context's scans in flight
-    if (rc != BL_OK) return rc;
+    BLH_OK(bl_ctx_sync(ctx));  // the context's scans in flight
     if (end <= first) return BL_OK;
 
     const uint32_t* start_bits = nullptr;
-    rc = bl_batch_scan_view(ctx, batch, 1, &start_bits);
-    if (rc != BL_OK) return rc;
+    BLH_OK(bl_batch_scan_view(ctx, batch, 1, &start_bits));
     BLH_TRY(hipSetDevice(bl_ctx_device(ctx)));
     hipStream_t s = bl_ctx_stream(ctx);
 
@@ -198,7 +193,7 @@ extern "C" int bl_scan_read_edits(bl_ctx* ctx, const bl_batch* batch, uint64_t f
     ull* block_base = block_counts + (n_blocks + 1);
 
     StateParams sp{};
-    sp.km.bases = static_cast<const uint8_t*>(bl_batch_device_bases(batch));
+    sp.km.bases = view.bases;
     sp.km.n_bases = (int64_t)n_bases;
     sp.km.start_bits = start_bits;
     bl::plan_kmers128(s0, s1, sp.km);
@@ -221,11 +216,8 @@ extern "C" int bl_scan_read_edits(bl_ctx* ctx, const bl_batch* batch, uint64_t f
     rp.min_support = min_support;
     hipLaunchKernelGGL(run_kernel<false>, dim3((unsigned)n_blocks), dim3(CTPB), 0, s, rp, block_counts, (const ull*)nullptr, (Candidate*)nullptr, (ull)0, d_stats);
     BLH_TRY(hipGetLastError());
-    rc = blh::exclusive_sum(ctx, reinterpret_cast<const uint64_t*>(block_counts), reinterpret_cast<uint64_t*>(block_base), (size_t)(n_blocks + 1), s);
-    if (rc != BL_OK) return rc;
-    ull n_cand = 0;
-    BLH_TRY(hipMemcpyAsync(&n_cand, block_base + n_blocks, sizeof(n_cand), hipMemcpyDeviceToHost, s));
-    BLH_TRY(hipStreamSynchronize(s));
+    uint64_t n_cand = 0;
+    BLH_OK(blh::exclusive_sum_total(ctx, reinterpret_cast<const uint64_t*>(block_counts), reinterpret_cast<uint64_t*>(block_base), (size_t)(n_blocks + 1), s, &n_cand));
 
     if (n_cand) {
         // slot 0: candidates | their edits | edit flags | the flags' exclusive sum | verdicts
@@ -254,9 +246,8 @@ extern "C" int bl_scan_read_edits(bl_ctx* ctx, const bl_batch* batch, uint64_t f
         BLH_TRY(hipMemsetAsync(edit_flag + n_cand, 0, sizeof(ull), s));
         hipLaunchKernelGGL(test_kernel, dim3((unsigned)((n_cand + TEST_WAVES - 1) / TEST_WAVES)), dim3(CTPB), 0, s, tp);
         BLH_TRY(hipGetLastError());
-        rc = blh::exclusive_sum(ctx, reinterpret_cast<const uint64_t*>(edit_flag), reinterpret_cast<uint64_t*>(edit_sum), (size_t)(n_cand + 1), s);
-        if (rc != BL_OK) return rc;
-        hipLaunchKernelGGL(compact_kernel, dim3(blocks_for(n_cand)), dim3(CTPB), 0, s, edits, verdicts, (const ull*)edit_sum, n_cand, reinterpret_cast<Edit*>(d_edits), (ull)capacity, d_stats);
+        BLH_OK(blh::exclusive_sum(ctx, reinterpret_cast<const uint64_t*>(edit_flag), reinterpret_cast<uint64_t*>(edit_sum), (size_t)(n_cand + 1), s));
+        hipLaunchKernelGGL(compact_kernel, dim3(blocks_for(n_cand, CTPB)), dim3(CTPB), 0, s, edits, verdicts, (const ull*)edit_sum, n_cand, reinterpret_cast<Edit*>(d_edits), (ull)capacity, d_stats);
         BLH_TRY(hipGetLastError());
     }
     ull host[STAT_WORDS] = {};
@@ -279,17 +270,14 @@ extern "C" int bl_batch_apply_edits(bl_ctx* ctx, const bl_batch* batch, const bl
     using namespace blcr;
     if (!ctx || !batch || !out) return invalid("ctx, batch or out is NULL");
     *out = nullptr;
-    bl_ctx* owner = nullptr;
-    uint64_t n_bases = 0, unused[2];
-    bl_batch_describe(batch, &owner, &n_bases, &unused[0], &unused[1]);
-    if (owner != ctx) return invalid("the batch belongs to another context");
+    blh::BatchView view;
+    BLH_OK(blh::batch_view(ctx, batch, view));
+    const uint64_t n_bases = view.n_bases;
     if (n_edits && !d_edits) return invalid("d_edits is NULL");
-    if (reinterpret_cast<uintptr_t>(d_edits) & 15) return invalid("d_edits must be 16-byte aligned");
-    int rc = bl_ctx_sync(ctx);
-    if (rc != BL_OK) return rc;
+    if (blh::misaligned16(d_edits)) return invalid("d_edits must be 16-byte aligned");
+    BLH_OK(bl_ctx_sync(ctx));
     const uint32_t* start_bits = nullptr;  // (NULL on a fixed-length batch that has not needed them: the copy builds its own on demand)
-    rc = bl_batch_scan_view(ctx, batch, 0, &start_bits);
-    if (rc != BL_OK) return rc;
+    BLH_OK(bl_batch_scan_view(ctx, batch, 0, &start_bits));
     BLH_TRY(hipSetDevice(bl_ctx_device(ctx)));
     hipStream_t s = bl_ctx_stream(ctx);
 
@@ -298,16 +286,15 @@ extern "C" int bl_batch_apply_edits(bl_ctx* ctx, const bl_batch* batch, const bl
     blh::Pooled<uint32_t> d_bits;
     if (start_bits) d_bits = blh::Pooled<uint32_t>(ctx, bit_words * sizeof(uint32_t));
     if (!d_bases || (start_bits && !d_bits)) return bl_set_error(BL_ERR_OOM, "device allocation failed (batch)");
-    const uint8_t* src = static_cast<const uint8_t*>(bl_batch_device_bases(batch));
-    hipLaunchKernelGGL(copy_kernel, dim3(blocks_for(n_bases / 16 + 80)), dim3(CTPB), 0, s, src, d_bases.get(), (ull)n_bases, (ull)64);  // 64 bytes of zeros behind the bases
+    hipLaunchKernelGGL(copy_kernel, dim3(blocks_for(n_bases / 16 + 80, CTPB)), dim3(CTPB), 0, s, view.bases, d_bases.get(), (ull)n_bases, (ull)64);  // 64 bytes of zeros behind the bases
     BLH_TRY(hipGetLastError());
     if (d_bits) {
-        hipLaunchKernelGGL(copy_kernel, dim3(blocks_for(bit_words * 4 / 16 + 16)), dim3(CTPB), 0, s, reinterpret_cast<const uint8_t*>(start_bits),
+        hipLaunchKernelGGL(copy_kernel, dim3(blocks_for(bit_words * 4 / 16 + 16, CTPB)), dim3(CTPB), 0, s, reinterpret_cast<const uint8_t*>(start_bits),
                            reinterpret_cast<uint8_t*>(d_bits.get()), (ull)(bit_words * 4), (ull)0);
         BLH_TRY(hipGetLastError());
     }
     if (n_edits) {
-        hipLaunchKernelGGL(apply_kernel, dim3(blocks_for(n_edits)), dim3(CTPB), 0, s, reinterpret_cast<const Edit*>(d_edits), (ull)n_edits, d_bases.get(), (ull)n_bases);
+        hipLaunchKernelGGL(apply_kernel, dim3(blocks_for(n_edits, CTPB)), dim3(CTPB), 0, s, reinterpret_cast<const Edit*>(d_edits), (ull)n_edits, d_bases.get(), (ull)n_bases);
         BLH_TRY(hipGetLastError());
     }
     BLH_TRY(hipStreamSynchronize(s));

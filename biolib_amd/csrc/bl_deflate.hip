@@ -131,8 +131,7 @@ int enqueue(bl_ctx* ctx, hipStream_t s, const Arena& a, uint32_t group, const ui
         const uint32_t count = n_members - first < group ? (uint32_t)(n_members - first) : group;
         hipLaunchKernelGGL(deflate_members_kernel, dim3(count), dim3(64), 0, s, d_text, n_bytes, first, count, a);
         BLH_TRY(hipGetLastError());
-        const int rc = blh::exclusive_sum(ctx, a.sizes, a.starts, (size_t)count + 1, s);
-        if (rc != BL_OK) return rc;
+        BLH_OK(blh::exclusive_sum(ctx, a.sizes, a.starts, (size_t)count + 1, s));
         hipLaunchKernelGGL(gather_members_kernel, dim3(count), dim3(GATHER_THREADS), 0, s, n_bytes, first, count, a, d_out, d_members);
         hipLaunchKernelGGL(advance_kernel, dim3(1), dim3(1), 0, s, count, a);
         BLH_TRY(hipGetLastError());
@@ -172,7 +171,7 @@ extern "C" int bl_bgzf_deflate(bl_ctx* ctx, const uint8_t* d_text, uint64_t n_by
     if (!d_text && n_bytes) return invalid("bl_bgzf_deflate: d_text is NULL");
     if (!d_out || !n_out_bytes) return invalid("bl_bgzf_deflate: d_out or n_out_bytes is NULL");
     if (flags & ~(uint32_t)BL_BGZF_NO_EOF) return invalid("bl_bgzf_deflate: unknown flag bits");
-    if (reinterpret_cast<uintptr_t>(d_out) & 15) return invalid("bl_bgzf_deflate: d_out must be 16-byte aligned");
+    if (blh::misaligned16(d_out)) return invalid("bl_bgzf_deflate: d_out must be 16-byte aligned");
     const uint64_t bound = bl_bgzf_bound(n_bytes, flags), total_members = members_of(n_bytes);
     if (n_members) *n_members = total_members;
     if (capacity < bound) {
@@ -206,7 +205,7 @@ extern "C" int bl_bgzf_deflate(bl_ctx* ctx, const uint8_t* d_text, uint64_t n_by
 extern "C" int bl_text_write_bgzf(bl_ctx* ctx, const uint8_t* d_text, uint64_t n_bytes, const char* path, int append, uint32_t flags)
 {
     using namespace bl_deflate;
-    if (!ctx || !path || (n_bytes && !d_text)) return bl_set_error(BL_ERR_INVALID, "NULL argument");
+    if (!ctx || !path || (n_bytes && !d_text)) return invalid("NULL argument");
     if (flags & ~(uint32_t)BL_BGZF_NO_EOF) return invalid("bl_text_write_bgzf: unknown flag bits");
     BLH_TRY(hipSetDevice(bl_ctx_device(ctx)));
     FILE* f = std::fopen(path, append ? "ab" : "wb");

@@ -116,23 +116,12 @@ __global__ __launch_bounds__(TPB) void format_kernel(const FormatParams p)
 
 namespace {
 
+using blh::blocks_for;
 using blh::exclusive_sum;
 using blh::hip_rc;
 using blh::invalid;
-unsigned blocks_for(uint64_t threads) { return (unsigned)((threads + TPB - 1) / TPB); }
-
-// a NUL inside the 16 bytes: the length; none: -1
-int terminated_length(const char* s)
-{
-    for (int i = 0; i < 16; ++i)
-        if (!s[i]) return i;
-    return -1;
-}
-void pack16(const char* s, int n, uint64_t w[2])
-{
-    w[0] = w[1] = 0;
-    for (int i = 0; i < n; ++i) w[i >> 3] |= (uint64_t)(uint8_t)s[i] << (8 * (i & 7));
-}
+using blh::pack_prefix;
+using blh::terminated_length;
 
 void free_index(bl_text_index* ix)
 {
@@ -169,7 +158,7 @@ int index_device_text(bl_ctx* ctx, bl_text_index* ix, char first_byte, const cha
     if (li.n_lines) {
         e = hipMemsetAsync(d_err, 0, sizeof(unsigned int), s);
         if (e != hipSuccess) return fail(hip_rc(e));
-        hipLaunchKernelGGL(index_kernel, dim3(blocks_for(li.n_lines)), dim3(TPB), 0, s, ix->d_text, li, ix->d_records, ix->d_offsets, d_err);
+        hipLaunchKernelGGL(index_kernel, dim3(blocks_for(li.n_lines, TPB)), dim3(TPB), 0, s, ix->d_text, li, ix->d_records, ix->d_offsets, d_err);
         e = hipGetLastError();
         if (e == hipSuccess) e = hipMemcpyAsync(&err, d_err, sizeof(err), hipMemcpyDeviceToHost, s);
         if (e != hipSuccess) return fail(hip_rc(e));
@@ -189,7 +178,7 @@ int bl_text_index_from_device(bl_ctx* ctx, const uint8_t* d_text, uint64_t n_byt
                               bl_text_index** out_index, uint64_t* n_seqs, uint64_t* n_bases)
 {
     using namespace blfmt;
-    if (!ctx || !out_batch || !out_index || !d_text || n_bytes == 0) return bl_set_error(BL_ERR_INVALID, "NULL argument");
+    if (!ctx || !out_batch || !out_index || !d_text || n_bytes == 0) return blh::invalid("NULL argument");
     *out_batch = nullptr;
     *out_index = nullptr;
     if (hipSetDevice(bl_ctx_device(ctx)) != hipSuccess) return bl_set_error(BL_ERR_HIP, "hipSetDevice failed");
@@ -216,7 +205,7 @@ extern "C" int bl_text_index_build(bl_ctx* ctx, const char* text, uint64_t n_byt
                                    uint64_t* n_bases)
 {
     using namespace blfmt;
-    if (!ctx || !out_batch || !out_index || (n_bytes && !text)) return bl_set_error(BL_ERR_INVALID, "NULL argument");
+    if (!ctx || !out_batch || !out_index || (n_bytes && !text)) return blh::invalid("NULL argument");
     *out_batch = nullptr;
     *out_index = nullptr;
     if (n_seqs) *n_seqs = 0;
@@ -259,7 +248,7 @@ extern "C" int bl_text_index_build(bl_ctx* ctx, const char* text, uint64_t n_byt
 
 extern "C" int bl_text_index_info(const bl_text_index* ix, uint64_t* n_records, int* is_fastq, const uint8_t** d_text, uint64_t* n_bytes, const void** d_records)
 {
-    if (!ix) return bl_set_error(BL_ERR_INVALID, "NULL argument");
+    if (!ix) return blh::invalid("NULL argument");
     if (n_records) *n_records = ix->n_records;
     if (is_fastq) *is_fastq = ix->fastq;
     if (d_text) *d_text = ix->d_text;
@@ -296,21 +285,18 @@ extern "C" int bl_batch_format(bl_ctx* ctx, const bl_batch* batch, const uint64_
     const int prefix_len = terminated_length(rule->name_prefix), label_len = terminated_length(rule->tag_label);
     if (prefix_len < 0 || label_len < 0) return invalid("bl_format_rule: name_prefix and tag_label are NUL-terminated inside their 16 bytes");
     if (rule->reserved != 0) return invalid("bl_format_rule: reserved must be 0");
-    if (reinterpret_cast<uintptr_t>(d_spans) & 15) return invalid("d_spans must be 16-byte aligned");
-    if (reinterpret_cast<uintptr_t>(d_out) & 15) return invalid("d_out must be 16-byte aligned");
+    if (blh::misaligned16(d_spans)) return invalid("d_spans must be 16-byte aligned");
+    if (blh::misaligned16(d_out)) return invalid("d_out must be 16-byte aligned");
     if (index && index->ctx != ctx) return invalid("the index belongs to another context");
+    blh::BatchView view;
+    BLH_OK(blh::batch_view(ctx, batch, view));
+    BLH_OK(blh::offsets_needed(d_offsets, view.n_seqs, view.read_len));
     FormatParams p{};
-    {
-        bl_ctx* owner = nullptr;
-        uint64_t batch_read_len = 0;
-        bl_batch_describe(batch, &owner, &p.n_bases, &p.n_seqs, &batch_read_len);
-        if (owner != ctx) return invalid("the batch belongs to another context");
-        if (!d_offsets && p.n_seqs > 1 && batch_read_len == 0)
-            return invalid("d_offsets is NULL: only a single-sequence or a fixed-read-length batch finds its sequences without the offsets");
-        p.read_len = d_offsets ? 0 : (batch_read_len ? batch_read_len : (p.n_bases ? p.n_bases : 1));
-        p.full_reads = p.read_len ? p.n_bases / p.read_len : 0;
-    }
-    p.bases = static_cast<const uint8_t*>(bl_batch_device_bases(batch));
+    p.n_bases = view.n_bases;
+    p.n_seqs = view.n_seqs;
+    p.read_len = d_offsets ? 0 : (view.read_len ? view.read_len : (p.n_bases ? p.n_bases : 1));
+    p.full_reads = p.read_len ? p.n_bases / p.read_len : 0;
+    p.bases = view.bases;
     p.offsets = d_offsets;
     if (index && index->n_records) {
         p.text = index->d_text;
@@ -327,14 +313,13 @@ extern "C" int bl_batch_format(bl_ctx* ctx, const bl_batch* batch, const uint64_
     p.flags = rule->flags;
     p.line_width = rule->line_width;
     p.quality_fill = rule->quality_fill;
-    pack16(rule->name_prefix, prefix_len, p.prefix);
-    pack16(rule->tag_label, label_len, p.label);
+    pack_prefix(rule->name_prefix, prefix_len, p.prefix);
+    pack_prefix(rule->tag_label, label_len, p.label);
     p.prefix_len = (uint32_t)prefix_len;
     p.label_len = (uint32_t)label_len;
     p.first_number = rule->first_number;
 
-    hipError_t e = hipSetDevice(bl_ctx_device(ctx));
-    if (e != hipSuccess) return hip_rc(e);
+    BLH_TRY(hipSetDevice(bl_ctx_device(ctx)));
     hipStream_t s = bl_ctx_stream(ctx);  // behind the context's scans in flight
     const uint64_t n1 = p.n_seqs + 1;
     // slot 4: lengths, flags, their two sums and the descriptions (behind 32 * n1 bytes: 16-byte aligned)
@@ -347,17 +332,14 @@ extern "C" int bl_batch_format(bl_ctx* ctx, const bl_batch* batch, const uint64_
     p.rec_off = rec_off;
     p.desc = reinterpret_cast<Desc*>(arena + 4 * n1);
 
-    hipLaunchKernelGGL(record_length_kernel, dim3(blocks_for(n1)), dim3(TPB), 0, s, p);
-    e = hipGetLastError();
-    if (e != hipSuccess) return hip_rc(e);
-    int rc = exclusive_sum(ctx, p.rec_len, rec_off, (size_t)n1, s);
-    if (rc == BL_OK) rc = exclusive_sum(ctx, p.written, written_sum, (size_t)n1, s);  // (the first sum is done with slot 5: same stream)
-    if (rc != BL_OK) return rc;
+    hipLaunchKernelGGL(record_length_kernel, dim3(blocks_for(n1, TPB)), dim3(TPB), 0, s, p);
+    BLH_TRY(hipGetLastError());
+    BLH_OK(exclusive_sum(ctx, p.rec_len, rec_off, (size_t)n1, s));
+    BLH_OK(exclusive_sum(ctx, p.written, written_sum, (size_t)n1, s));  // (the first sum is done with slot 5: same stream)
     unsigned long long total = 0, n_written = 0;
-    e = hipMemcpyAsync(&total, rec_off + p.n_seqs, sizeof(total), hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess) e = hipMemcpyAsync(&n_written, written_sum + p.n_seqs, sizeof(n_written), hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess) e = hipStreamSynchronize(s);
-    if (e != hipSuccess) return hip_rc(e);
+    BLH_TRY(hipMemcpyAsync(&total, rec_off + p.n_seqs, sizeof(total), hipMemcpyDeviceToHost, s));
+    BLH_TRY(hipMemcpyAsync(&n_written, written_sum + p.n_seqs, sizeof(n_written), hipMemcpyDeviceToHost, s));
+    BLH_TRY(hipStreamSynchronize(s));
     if (n_bytes) *n_bytes = total;
     if (n_records) *n_records = n_written;
     if (!d_out) return BL_OK;  // sizing only
@@ -366,17 +348,17 @@ extern "C" int bl_batch_format(bl_ctx* ctx, const bl_batch* batch, const uint64_
     p.total = total;
     p.out = d_out;
     const uint64_t waves = (total + WAVE_BYTES - 1) / WAVE_BYTES;
-    hipLaunchKernelGGL(format_kernel, dim3(blocks_for(waves * 64)), dim3(TPB), 0, s, p);
-    e = hipGetLastError();
-    if (e == hipSuccess) e = hipStreamSynchronize(s);
-    return e == hipSuccess ? BL_OK : hip_rc(e);
+    hipLaunchKernelGGL(format_kernel, dim3(blocks_for(waves * 64, TPB)), dim3(TPB), 0, s, p);
+    BLH_TRY(hipGetLastError());
+    BLH_TRY(hipStreamSynchronize(s));
+    return BL_OK;
 }
 
 // Device text to a file: chunks of WRITE_CHUNK bytes through two pinned buffers, chunk c + 1 copying while chunk c is written.
 extern "C" int bl_text_write(bl_ctx* ctx, const uint8_t* d_text, uint64_t n_bytes, const char* path, int append)
 {
     constexpr size_t WRITE_CHUNK = (size_t)8 << 20;
-    if (!ctx || !path || (n_bytes && !d_text)) return bl_set_error(BL_ERR_INVALID, "NULL argument");
+    if (!ctx || !path || (n_bytes && !d_text)) return blh::invalid("NULL argument");
     hipError_t e = hipSetDevice(bl_ctx_device(ctx));
     if (e != hipSuccess) return blh::hip_rc(e);
     FILE* f = std::fopen(path, append ? "ab" : "wb");

@@ -165,16 +165,16 @@ __global__ __launch_bounds__(GTPB) void uniform_kernel(const uint64_t* offsets, 
 
 namespace {
 
+using blh::blocks_for;
 using blh::exclusive_sum;
 using blh::hip_rc;
 using blh::invalid;
-unsigned blocks_for(uint64_t threads) { return (unsigned)((threads + GTPB - 1) / GTPB); }
 
 // what both calls refuse before anything runs
 int check_arguments(bl_ctx* ctx, const bl_table* table, uint32_t k)
 {
     if (!ctx || !table) return invalid("ctx or table is NULL");
-    if (table->ctx != ctx) return invalid("the table belongs to another context");
+    BLH_OK(blh::table_owner(table->ctx, ctx));
     switch (refuse(k, table->view.key_words, table->view.key_bits, table->view.n)) {
     case 1: return invalid("k must be odd and 1 .. 63 (an even k has k-mers that are their own reverse complement)");
     case 2: return invalid("2k exceeds the table's key_bits");
@@ -211,21 +211,21 @@ int adjacency(const TableView& t, uint32_t k, const AdjBuffers& b, ull* d_counte
     uint32_t* d_words = reinterpret_cast<uint32_t*>(d_counters) + C_WORDS32;
     BLH_TRY(hipMemsetAsync(d_counters, 0, 8 * sizeof(ull), s));
     BLH_TRY(hipMemsetAsync(d_words, 0xFF, sizeof(uint32_t), s));
-    hipLaunchKernelGGL(check_kernel<W>, dim3(blocks_for(n)), dim3(GTPB), 0, s, t, k, d_words);
+    hipLaunchKernelGGL(check_kernel<W>, dim3(blocks_for(n, GTPB)), dim3(GTPB), 0, s, t, k, d_words);
     BLH_TRY(hipGetLastError());
     uint32_t first_bad = 0;
     BLH_TRY(hipMemcpyAsync(&first_bad, d_words, sizeof(first_bad), hipMemcpyDeviceToHost, s));
     BLH_TRY(hipStreamSynchronize(s));
     if (first_bad != LINK_NONE)
         return invalid(("the key at slot " + std::to_string(first_bad) + " has a bit at or above 2k or exceeds its own reverse complement: not a table of canonical k-mers of this k").c_str());
-    hipLaunchKernelGGL(mask_kernel<W>, dim3(blocks_for(n)), dim3(GTPB), 0, s, t, k, b.mask, reinterpret_cast<uint2*>(b.nbr));
+    hipLaunchKernelGGL(mask_kernel<W>, dim3(blocks_for(n, GTPB)), dim3(GTPB), 0, s, t, k, b.mask, reinterpret_cast<uint2*>(b.nbr));
     BLH_TRY(hipGetLastError());
     if (b.links) {
-        hipLaunchKernelGGL(link_kernel, dim3(blocks_for(2 * n)), dim3(GTPB), 0, s, b.mask, b.nbr, b.links, 2 * n);
+        hipLaunchKernelGGL(link_kernel, dim3(blocks_for(2 * n, GTPB)), dim3(GTPB), 0, s, b.mask, b.nbr, b.links, 2 * n);
         BLH_TRY(hipGetLastError());
     }
     if (stats) {
-        hipLaunchKernelGGL(stats_kernel, dim3(blocks_for(n)), dim3(GTPB), 0, s, b.mask, b.links, n, d_counters);
+        hipLaunchKernelGGL(stats_kernel, dim3(blocks_for(n, GTPB)), dim3(GTPB), 0, s, b.mask, b.links, n, d_counters);
         BLH_TRY(hipGetLastError());
         ull host[5] = {};
         BLH_TRY(hipMemcpyAsync(host, d_counters, sizeof(host), hipMemcpyDeviceToHost, s));
@@ -243,12 +243,12 @@ int adjacency(const TableView& t, uint32_t k, const AdjBuffers& b, ull* d_counte
 // pointer doubling until a round finds every state at its chain's end, at most `rounds` rounds; cur: the records of the last round
 int label(const uint32_t* links, Rec*& cur, Rec*& nxt, uint64_t n_states, uint32_t rounds, uint32_t* d_flag, bool& settled, hipStream_t s)
 {
-    hipLaunchKernelGGL(label_init_kernel, dim3(blocks_for(n_states)), dim3(GTPB), 0, s, links, cur, n_states);
+    hipLaunchKernelGGL(label_init_kernel, dim3(blocks_for(n_states, GTPB)), dim3(GTPB), 0, s, links, cur, n_states);
     BLH_TRY(hipGetLastError());
     settled = false;
     for (uint32_t r = 0; r < rounds && !settled; ++r) {
         BLH_TRY(hipMemsetAsync(d_flag, 0, sizeof(uint32_t), s));
-        hipLaunchKernelGGL(label_step_kernel, dim3(blocks_for(n_states)), dim3(GTPB), 0, s, cur, nxt, n_states, d_flag);
+        hipLaunchKernelGGL(label_step_kernel, dim3(blocks_for(n_states, GTPB)), dim3(GTPB), 0, s, cur, nxt, n_states, d_flag);
         BLH_TRY(hipGetLastError());
         uint32_t any = 0;
         BLH_TRY(hipMemcpyAsync(&any, d_flag, sizeof(any), hipMemcpyDeviceToHost, s));
@@ -312,41 +312,35 @@ int unitigs(bl_ctx* ctx, const bl_table* table, uint32_t k, bl_batch** out, uint
     if (!d_counters) return bl_set_error(BL_ERR_OOM, "scratch allocation failed");
     uint32_t* d_flag = reinterpret_cast<uint32_t*>(d_counters) + C_WORDS32 + 1;
 
-    int rc = adjacency<W>(t, k, b, d_counters, stats, s);
-    if (rc != BL_OK) return rc;
+    BLH_OK(adjacency<W>(t, k, b, d_counters, stats, s));
 
     // labelling; where states are still on their way after the bound they lie on cycles: cut each at its smallest slot and label again
     const uint32_t bound = max_rounds((uint32_t)n);
     bool settled = false;
     ull cuts = 0;
-    rc = label(b.links, cur, nxt, 2 * n, bound, d_flag, settled, s);
-    if (rc != BL_OK) return rc;
+    BLH_OK(label(b.links, cur, nxt, 2 * n, bound, d_flag, settled, s));
     if (!settled) {
-        hipLaunchKernelGGL(cut_kernel, dim3(blocks_for(n)), dim3(GTPB), 0, s, cur, b.links, n, d_counters);
+        hipLaunchKernelGGL(cut_kernel, dim3(blocks_for(n, GTPB)), dim3(GTPB), 0, s, cur, b.links, n, d_counters);
         BLH_TRY(hipGetLastError());
         BLH_TRY(hipMemcpyAsync(&cuts, d_counters + C_CUTS, sizeof(cuts), hipMemcpyDeviceToHost, s));
         BLH_TRY(hipStreamSynchronize(s));
         if (cuts) {
-            rc = label(b.links, cur, nxt, 2 * n, bound + 1, d_flag, settled, s);
-            if (rc != BL_OK) return rc;
+            BLH_OK(label(b.links, cur, nxt, 2 * n, bound + 1, d_flag, settled, s));
             if (!settled) return bl_set_error(BL_ERR_INTERNAL, "states are still on their way after every cycle was cut");
         }
     }
 
-    hipLaunchKernelGGL(place_kernel, dim3(blocks_for(n + 1)), dim3(GTPB), 0, s, cur, n, placed, is_start);
+    hipLaunchKernelGGL(place_kernel, dim3(blocks_for(n + 1, GTPB)), dim3(GTPB), 0, s, cur, n, placed, is_start);
     BLH_TRY(hipGetLastError());
-    rc = exclusive_sum(ctx, is_start, number, (size_t)(n + 1), s);
-    if (rc != BL_OK) return rc;
-    hipLaunchKernelGGL(number_kernel, dim3(blocks_for(n + 1)), dim3(GTPB), 0, s, placed, number, n, k, nodes, lengths, d_counters);
+    BLH_OK(exclusive_sum(ctx, is_start, number, (size_t)(n + 1), s));
+    hipLaunchKernelGGL(number_kernel, dim3(blocks_for(n + 1, GTPB)), dim3(GTPB), 0, s, placed, number, n, k, nodes, lengths, d_counters);
     BLH_TRY(hipGetLastError());
-    ull n_unitigs = 0, longest = 0, total = 0;
+    ull n_unitigs = 0, longest = 0;
     BLH_TRY(hipMemcpyAsync(&n_unitigs, number + n, sizeof(n_unitigs), hipMemcpyDeviceToHost, s));
     BLH_TRY(hipMemcpyAsync(&longest, d_counters + C_LONGEST, sizeof(longest), hipMemcpyDeviceToHost, s));
     BLH_TRY(hipStreamSynchronize(s));
-    rc = exclusive_sum(ctx, lengths, offsets, (size_t)(n_unitigs + 1), s);
-    if (rc != BL_OK) return rc;
-    BLH_TRY(hipMemcpyAsync(&total, offsets + n_unitigs, sizeof(total), hipMemcpyDeviceToHost, s));
-    BLH_TRY(hipStreamSynchronize(s));
+    uint64_t total = 0;
+    BLH_OK(blh::exclusive_sum_total(ctx, lengths, offsets, (size_t)(n_unitigs + 1), s, &total));
     if (stats) {
         stats->n_unitigs = n_unitigs;
         stats->n_cycles = cuts;
@@ -365,7 +359,7 @@ int unitigs(bl_ctx* ctx, const bl_table* table, uint32_t k, bl_batch** out, uint
     }
     if (d_count_sums) BLH_TRY(hipMemsetAsync(d_count_sums, 0, (size_t)n_unitigs * sizeof(uint64_t), s));
     if (out || d_count_sums) {
-        hipLaunchKernelGGL(emit_kernel<W>, dim3(blocks_for(n)), dim3(GTPB), 0, s, t, k, nodes, offsets, d_bases.get(), reinterpret_cast<ull*>(d_count_sums));
+        hipLaunchKernelGGL(emit_kernel<W>, dim3(blocks_for(n, GTPB)), dim3(GTPB), 0, s, t, k, nodes, offsets, d_bases.get(), reinterpret_cast<ull*>(d_count_sums));
         BLH_TRY(hipGetLastError());
     }
     // unitigs of one length make a fixed-length batch (the parser's rule), any other result carries start bits
@@ -373,15 +367,14 @@ int unitigs(bl_ctx* ctx, const bl_table* table, uint32_t k, bl_batch** out, uint
     uint32_t ragged = 0;
     if (fixed_len) {
         BLH_TRY(hipMemsetAsync(d_flag, 0, sizeof(uint32_t), s));
-        hipLaunchKernelGGL(uniform_kernel, dim3(blocks_for(n_unitigs)), dim3(GTPB), 0, s, offsets, (uint64_t)n_unitigs, fixed_len, d_flag);
+        hipLaunchKernelGGL(uniform_kernel, dim3(blocks_for(n_unitigs, GTPB)), dim3(GTPB), 0, s, offsets, (uint64_t)n_unitigs, fixed_len, d_flag);
         BLH_TRY(hipGetLastError());
         BLH_TRY(hipMemcpyAsync(&ragged, d_flag, sizeof(ragged), hipMemcpyDeviceToHost, s));
     }
     BLH_TRY(hipStreamSynchronize(s));
     if (ragged) fixed_len = 0;
     if (out) {
-        rc = bl_batch_adopt_device(ctx, d_bases.release(), total, d_offs.release(), n_unitigs, fixed_len, out);  // takes ownership of both
-        if (rc != BL_OK) return rc;
+        BLH_OK(bl_batch_adopt_device(ctx, d_bases.release(), total, d_offs.release(), n_unitigs, fixed_len, out));  // takes ownership of both
     }
     if (n_unitigs_out) *n_unitigs_out = n_unitigs;
     if (n_bases_out) *n_bases_out = total;
@@ -395,15 +388,13 @@ int unitigs(bl_ctx* ctx, const bl_table* table, uint32_t k, bl_batch** out, uint
 extern "C" int bl_table_adjacency(bl_ctx* ctx, const bl_table* table, uint32_t k, uint8_t* d_mask, uint32_t* d_links, bl_graph_stats* stats)
 {
     using namespace blgr;
-    int rc = check_arguments(ctx, table, k);
-    if (rc != BL_OK) return rc;
+    BLH_OK(check_arguments(ctx, table, k));
     if (stats) *stats = bl_graph_stats{};
     const TableView& t = table->view;
     const uint64_t n = t.n;
     if (n == 0) return BL_OK;
     if (!d_mask) return invalid("d_mask is NULL");
-    hipError_t e = hipSetDevice(bl_ctx_device(ctx));
-    if (e != hipSuccess) return hip_rc(e);
+    BLH_TRY(hipSetDevice(bl_ctx_device(ctx)));
     hipStream_t s = bl_ctx_stream(ctx);
     // slot 4: the one neighbour of every side of degree 1 and, where the caller takes no links but the statistics, the links
     const bool linking = d_links || stats;
@@ -423,10 +414,9 @@ extern "C" int bl_table_adjacency(bl_ctx* ctx, const bl_table* table, uint32_t k
     ull* d_counters = static_cast<ull*>(bl_ctx_scratch(ctx, 6, 128));
     if (!d_counters) return bl_set_error(BL_ERR_OOM, "scratch allocation failed");
     const AdjBuffers b{d_mask, nbr, links};
-    rc = t.key_words == 2 ? adjacency<2>(t, k, b, d_counters, stats, s) : adjacency<1>(t, k, b, d_counters, stats, s);
-    if (rc != BL_OK) return rc;
-    e = hipStreamSynchronize(s);
-    return e == hipSuccess ? BL_OK : hip_rc(e);
+    BLH_OK(t.key_words == 2 ? adjacency<2>(t, k, b, d_counters, stats, s) : adjacency<1>(t, k, b, d_counters, stats, s));
+    BLH_TRY(hipStreamSynchronize(s));
+    return BL_OK;
 }
 
 extern "C" int bl_table_unitigs(bl_ctx* ctx, const bl_table* table, uint32_t k, bl_batch** out, uint64_t* d_out_offsets, uint64_t* d_count_sums,
@@ -434,13 +424,11 @@ extern "C" int bl_table_unitigs(bl_ctx* ctx, const bl_table* table, uint32_t k, 
 {
     using namespace blgr;
     if (out) *out = nullptr;
-    int rc = check_arguments(ctx, table, k);
-    if (rc != BL_OK) return rc;
+    BLH_OK(check_arguments(ctx, table, k));
     if (stats) *stats = bl_graph_stats{};
     if (n_unitigs) *n_unitigs = 0;
     if (n_bases) *n_bases = 0;
-    hipError_t e = hipSetDevice(bl_ctx_device(ctx));
-    if (e != hipSuccess) return hip_rc(e);
+    BLH_TRY(hipSetDevice(bl_ctx_device(ctx)));
     hipStream_t s = bl_ctx_stream(ctx);
     if (table->view.n == 0) return empty_result(ctx, out, d_out_offsets, s);
     return table->view.key_words == 2 ? unitigs<2>(ctx, table, k, out, d_out_offsets, d_count_sums, d_nodes, n_unitigs, n_bases, stats, s)

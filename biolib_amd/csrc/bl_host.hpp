@@ -30,7 +30,7 @@ int bl_ctx_table_prefix_bits(bl_ctx* ctx);  // the "table_prefix_bits" option
 //   4      data; blpart::partition's histogram,        the set operations (bl_keylist.hpp), the owner splits, the table build and algebra, the
 //          offsets and bucket starts                   quantiles, select, format, the corrector, the graph (about 133 bytes per key in slot 4),
 //   5      library workspace (rocPRIM):                links, clean, the BGZF writer (slots, token areas and sizes of the members in flight)
-//          blh::exclusive_sum takes it                 and the steps (8 bytes per position; 88 per step for the GAF text): none of them calls
+//          blh::exclusive_sum(_total) take it          and the steps (8 bytes per position; 88 per step for the GAF text): none of them calls
 //                                                      another while it holds 4-6
 //   6      counters, flags, statistics
 void* bl_ctx_scratch(bl_ctx* ctx, int slot, size_t bytes);
@@ -107,6 +107,38 @@ hipError_t with_workspace(bl_ctx* ctx, int slot, F&& call)
 // Exclusive sum of n 8-byte words on `stream` (rocPRIM; its workspace is scratch slot 5, which a second sum on the same stream may take
 // again at once).  Defined in bl_host.hip: the library's one instantiation of that scan.
 int exclusive_sum(bl_ctx* ctx, const uint64_t* in, uint64_t* out, size_t n, hipStream_t stream);
+// The same, then out[n - 1] copied to *total and the stream waited for (n >= 1; callers end `in` with a word of 0: the sum of the rest).
+int exclusive_sum_total(bl_ctx* ctx, const uint64_t* in, uint64_t* out, size_t n, hipStream_t stream, uint64_t* total);
+
+inline unsigned blocks_for(uint64_t threads, unsigned tpb) { return (unsigned)((threads + tpb - 1) / tpb); }
+inline size_t round16(size_t bytes) { return (bytes + 15) & ~(size_t)15; }
+inline bool misaligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) != 0; }
+// the 16 bytes of a rule's name: the length up to the NUL inside them, -1 without one; the first len bytes as two little-endian words
+inline int terminated_length(const char* s)
+{
+    for (int i = 0; i < 16; ++i)
+        if (!s[i]) return i;
+    return -1;
+}
+inline void pack_prefix(const char* s, int len, uint64_t w[2])
+{
+    w[0] = w[1] = 0;
+    for (int i = 0; i < len; ++i) w[i >> 3] |= (uint64_t)(uint8_t)s[i] << (8 * (i & 7));
+}
+
+// ---- The argument checks the entry points share: BL_OK, or BL_ERR_INVALID with the one text each has.  They stand between a caller's
+// mistake and a kernel that reads outside an array.  Separate functions, because the entry points differ in what they check in between,
+// and the order in which a call refuses is part of its behaviour.  (Defined in bl_host.hip.)
+struct BatchView {
+    const uint8_t* bases;
+    uint64_t n_bases, n_seqs, read_len;  // read_len: 0 unless the batch is one of fixed-length reads
+};
+int batch_view(bl_ctx* ctx, const bl_batch* batch, BatchView& v);  // "the batch belongs to another context"; neither pointer is NULL
+// end: n == 0 or a range past the batch ends with it.  Refuses first > n_bases, and more than 2^31 positions: "<noun> may hold at most ..."
+int range_end(uint64_t n_bases, uint64_t first, uint64_t n, const char* noun, uint64_t& end);
+int offsets_needed(const uint64_t* d_offsets, uint64_t n_seqs, uint64_t read_len);  // NULL offsets on a batch of ragged sequences
+int table_owner(const bl_ctx* owner, const bl_ctx* ctx);                           // "the table belongs to another context"
+int table_takes_k(uint32_t key_words, uint32_t key_bits, uint32_t k);             // one-word keys hold k <= 32; 2k <= key_bits
 
 }  // namespace blh
 
@@ -114,4 +146,10 @@ int exclusive_sum(bl_ctx* ctx, const uint64_t* in, uint64_t* out, size_t n, hipS
     do {                                              \
         hipError_t e_ = (call);                       \
         if (e_ != hipSuccess) return blh::hip_rc(e_); \
+    } while (0)
+// the same for a call that answers a status of the library (the error text is set)
+#define BLH_OK(call)                    \
+    do {                                \
+        const int rc_ = (call);         \
+        if (rc_ != BL_OK) return rc_;   \
     } while (0)

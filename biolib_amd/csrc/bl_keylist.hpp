@@ -37,7 +37,6 @@ struct Width<__uint128_t> {
 };
 
 inline int scratch_failed() { return bl_set_error(BL_ERR_OOM, "scratch allocation failed"); }
-inline bool misaligned(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) != 0; }
 inline int bad_alignment() { return bl_set_error(BL_ERR_INVALID, "arrays of 16-byte keys must be 16-byte aligned"); }
 
 // the word a kernel or a primitive left at d_word, once the stream has drained
@@ -122,7 +121,7 @@ int read_file(bl_ctx* ctx, const char* path, int with_count, K* d_out, uint64_t 
     if (cnt > capacity) return bl_set_error(BL_ERR_CAPACITY, "device array too small for the file");
     if (cnt == 0) return BL_OK;
     if (!d_out) return bl_set_error(BL_ERR_INVALID, "NULL argument");
-    if (sizeof(K) == 16 && misaligned(d_out)) return bad_alignment();
+    if (sizeof(K) == 16 && blh::misaligned16(d_out)) return bad_alignment();
     std::vector<K> host(cnt);
     rc = Width<K>::read_host(path, with_count, host.data(), cnt);
     if (rc != BL_OK) return rc;
@@ -149,7 +148,7 @@ int merge_runs(bl_ctx* ctx, const char* const* paths, uint32_t n_paths, K* d_out
     if (total > capacity) return bl_set_error(BL_ERR_CAPACITY, "device array too small for the merged runs");
     if (total == 0) return BL_OK;
     if (!d_out) return bl_set_error(BL_ERR_INVALID, "NULL argument");
-    if (sizeof(K) == 16 && misaligned(d_out)) return bad_alignment();
+    if (sizeof(K) == 16 && blh::misaligned16(d_out)) return bad_alignment();
     for (uint32_t i = 0; i < n_paths; ++i) {
         const int rc = read_file<K>(ctx, paths[i], 0, d_out + off[i], len[i], nullptr);
         if (rc != BL_OK) return rc;

@@ -74,9 +74,9 @@ __global__ __launch_bounds__(LTPB) void link_emit_kernel(const uint64_t* __restr
 
 namespace {
 
+using blh::blocks_for;
 using blh::exclusive_sum;
 using blh::invalid;
-unsigned blocks_for(uint64_t threads) { return (unsigned)((threads + LTPB - 1) / LTPB); }
 
 size_t aligned(size_t bytes) { return (bytes + 255) & ~(size_t)255; }
 
@@ -90,7 +90,7 @@ extern "C" int bl_unitig_links(bl_ctx* ctx, const bl_table* table, uint32_t k, c
     using namespace bllnk;
     if (n_links) *n_links = 0;
     if (!ctx || !table) return invalid("ctx or table is NULL");
-    if (table->ctx != ctx) return invalid("the table belongs to another context");
+    BLH_OK(blh::table_owner(table->ctx, ctx));
     const TableView& t = table->view;
     const uint64_t n = t.n;
     switch (blgr::refuse(k, t.key_words, t.key_bits, n)) {
@@ -130,15 +130,14 @@ extern "C" int bl_unitig_links(bl_ctx* ctx, const bl_table* table, uint32_t k, c
 
     BLH_TRY(hipMemsetAsync(end_key, 0xFF, n_ends * sizeof(uint32_t), s));
     BLH_TRY(hipMemsetAsync(d_counters, 0, 4 * sizeof(ull), s));
-    hipLaunchKernelGGL(end_key_kernel, dim3(blocks_for(n)), dim3(LTPB), 0, s, nodes, d_unitig_offsets, n_unitigs, k, n, end_key);
+    hipLaunchKernelGGL(end_key_kernel, dim3(blocks_for(n, LTPB)), dim3(LTPB), 0, s, nodes, d_unitig_offsets, n_unitigs, k, n, end_key);
     BLH_TRY(hipGetLastError());
     if (t.key_words == 2)
-        hipLaunchKernelGGL(end_search_kernel<2>, dim3(blocks_for(n_ends + 1)), dim3(LTPB), 0, s, t, k, nodes, n_unitigs, end_key, flags, degree, parked, d_counters);
+        hipLaunchKernelGGL(end_search_kernel<2>, dim3(blocks_for(n_ends + 1, LTPB)), dim3(LTPB), 0, s, t, k, nodes, n_unitigs, end_key, flags, degree, parked, d_counters);
     else
-        hipLaunchKernelGGL(end_search_kernel<1>, dim3(blocks_for(n_ends + 1)), dim3(LTPB), 0, s, t, k, nodes, n_unitigs, end_key, flags, degree, parked, d_counters);
+        hipLaunchKernelGGL(end_search_kernel<1>, dim3(blocks_for(n_ends + 1, LTPB)), dim3(LTPB), 0, s, t, k, nodes, n_unitigs, end_key, flags, degree, parked, d_counters);
     BLH_TRY(hipGetLastError());
-    int rc = exclusive_sum(ctx, degree, offsets, (size_t)(n_ends + 1), s);
-    if (rc != BL_OK) return rc;
+    BLH_OK(exclusive_sum(ctx, degree, offsets, (size_t)(n_ends + 1), s));
     ull total = 0, host[4] = {};
     BLH_TRY(hipMemcpyAsync(&total, offsets + n_ends, sizeof(total), hipMemcpyDeviceToHost, s));
     BLH_TRY(hipMemcpyAsync(host, d_counters, sizeof(host), hipMemcpyDeviceToHost, s));
@@ -154,7 +153,7 @@ extern "C" int bl_unitig_links(bl_ctx* ctx, const bl_table* table, uint32_t k, c
     if (!d_links) return BL_OK;  // sizing only
     if (capacity < total) return bl_set_error(BL_ERR_CAPACITY, "bl_unitig_links: d_links is smaller than the records (*n_links says how many there are)");
     if (total == 0) return BL_OK;
-    hipLaunchKernelGGL(link_emit_kernel, dim3(blocks_for(n_ends)), dim3(LTPB), 0, s, offsets, parked, n_ends, (uint64_t)total, reinterpret_cast<Link*>(d_links));
+    hipLaunchKernelGGL(link_emit_kernel, dim3(blocks_for(n_ends, LTPB)), dim3(LTPB), 0, s, offsets, parked, n_ends, (uint64_t)total, reinterpret_cast<Link*>(d_links));
     BLH_TRY(hipGetLastError());
     BLH_TRY(hipStreamSynchronize(s));
     return BL_OK;
@@ -231,17 +230,9 @@ __global__ __launch_bounds__(TPB) void gfa_kernel(const GfaParams p)
 
 namespace {
 
-using blh::hip_rc;
+using blh::blocks_for;
 using blh::invalid;
-unsigned blocks_for(uint64_t threads) { return (unsigned)((threads + TPB - 1) / TPB); }
-
-// a NUL inside the 16 bytes: the length; none: -1
-int terminated_length(const char* s)
-{
-    for (int i = 0; i < 16; ++i)
-        if (!s[i]) return i;
-    return -1;
-}
+using blh::terminated_length;
 
 }  // namespace
 
@@ -261,17 +252,14 @@ extern "C" int bl_unitigs_format_gfa(bl_ctx* ctx, const bl_batch* unitigs, const
     case 4: return invalid("bl_gfa_rule: reserved must be 0");
     default: break;
     }
-    if (reinterpret_cast<uintptr_t>(d_out) & 15) return invalid("d_out must be 16-byte aligned");
+    if (blh::misaligned16(d_out)) return invalid("d_out must be 16-byte aligned");
     if (n_unitigs && !d_unitig_offsets) return invalid("d_unitig_offsets is NULL");
     if (n_links && !d_links) return invalid("d_links is NULL with n_links > 0");
+    blh::BatchView view;
+    BLH_OK(blh::batch_view(ctx, unitigs, view));
     GfaParams p{};
-    {
-        bl_ctx* owner = nullptr;
-        uint64_t n_seqs = 0, read_len = 0;
-        bl_batch_describe(unitigs, &owner, &p.n_bases, &n_seqs, &read_len);
-        if (owner != ctx) return invalid("the batch belongs to another context");
-    }
-    p.bases = static_cast<const uint8_t*>(bl_batch_device_bases(unitigs));
+    p.n_bases = view.n_bases;
+    p.bases = view.bases;
     p.offsets = d_unitig_offsets;
     p.n_unitigs = n_unitigs;
     p.sums = d_count_sums;
@@ -280,14 +268,13 @@ extern "C" int bl_unitigs_format_gfa(bl_ctx* ctx, const bl_batch* unitigs, const
     p.n_head = (rule->flags & BL_GFA_NO_HEADER) ? 0u : 1u;
     p.overlap = rule->k - 1;
     p.overlap_digits = p.overlap >= 10 ? 2u : 1u;
-    for (int i = 0; i < prefix_len; ++i) p.prefix[i >> 3] |= (uint64_t)(uint8_t)rule->name_prefix[i] << (8 * (i & 7));
+    blh::pack_prefix(rule->name_prefix, prefix_len, p.prefix);
     p.prefix_len = (uint32_t)prefix_len;
     p.first_number = rule->first_number;
     p.n_lines = p.n_head + n_unitigs + n_links;
     if (p.n_lines == 0) return BL_OK;
 
-    hipError_t e = hipSetDevice(bl_ctx_device(ctx));
-    if (e != hipSuccess) return hip_rc(e);
+    BLH_TRY(hipSetDevice(bl_ctx_device(ctx)));
     hipStream_t s = bl_ctx_stream(ctx);
     const uint64_t n1 = p.n_lines + 1;
     uint64_t* arena = static_cast<uint64_t*>(bl_ctx_scratch(ctx, 4, (size_t)(2 * n1) * sizeof(uint64_t)));  // lengths and their sums
@@ -295,23 +282,18 @@ extern "C" int bl_unitigs_format_gfa(bl_ctx* ctx, const bl_batch* unitigs, const
     p.line_len = arena;
     uint64_t* line_off = arena + n1;
     p.line_off = line_off;
-    hipLaunchKernelGGL(line_length_kernel, dim3(blocks_for(n1)), dim3(TPB), 0, s, p);
-    e = hipGetLastError();
-    if (e != hipSuccess) return hip_rc(e);
-    const int rc = blh::exclusive_sum(ctx, p.line_len, line_off, (size_t)n1, s);
-    if (rc != BL_OK) return rc;
-    unsigned long long total = 0;
-    e = hipMemcpyAsync(&total, line_off + p.n_lines, sizeof(total), hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess) e = hipStreamSynchronize(s);
-    if (e != hipSuccess) return hip_rc(e);
+    hipLaunchKernelGGL(line_length_kernel, dim3(blocks_for(n1, TPB)), dim3(TPB), 0, s, p);
+    BLH_TRY(hipGetLastError());
+    uint64_t total = 0;
+    BLH_OK(blh::exclusive_sum_total(ctx, p.line_len, line_off, (size_t)n1, s, &total));
     if (n_bytes) *n_bytes = total;
     if (!d_out) return BL_OK;  // sizing only
     if (capacity < total) return bl_set_error(BL_ERR_CAPACITY, "bl_unitigs_format_gfa: d_out is smaller than the text (*n_bytes says how large it is)");
     p.total = total;
     p.out = d_out;
     const uint64_t waves = (total + WAVE_BYTES - 1) / WAVE_BYTES;
-    hipLaunchKernelGGL(gfa_kernel, dim3(blocks_for(waves * 64)), dim3(TPB), 0, s, p);
-    e = hipGetLastError();
-    if (e == hipSuccess) e = hipStreamSynchronize(s);
-    return e == hipSuccess ? BL_OK : hip_rc(e);
+    hipLaunchKernelGGL(gfa_kernel, dim3(blocks_for(waves * 64, TPB)), dim3(TPB), 0, s, p);
+    BLH_TRY(hipGetLastError());
+    BLH_TRY(hipStreamSynchronize(s));
+    return BL_OK;
 }

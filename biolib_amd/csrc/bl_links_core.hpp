@@ -18,6 +18,7 @@
 // below n or END_NONE.  Nothing outside [0, n) of the nodes, [0, n_unitigs] of the offsets and the table's own arrays is read.
 #pragma once
 #include "bl_graph_core.hpp"
+#include "bl_unitig_records.hpp"
 
 namespace bllnk {
 
@@ -29,12 +30,8 @@ constexpr uint32_t ONCE = 1u;             // include/biolib_amd.h: BL_LINKS_ONCE
 constexpr uint32_t END_NONE = 0xFFFFFFFFu;
 constexpr uint32_t MIN_K = 3;
 
-struct Node {  // bl_unitig_node
-    uint32_t unitig, rank_flip;
-};
-struct Link {  // bl_unitig_link
-    uint32_t from, to;
-};
+using blrec::Node;
+using Link = blrec::LinkWords;
 struct alignas(16) Parked {
     uint32_t to[4];
 };

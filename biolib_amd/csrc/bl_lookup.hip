@@ -167,21 +167,22 @@ struct SatAdd {
 };
 
 using blh::hip_rc;
-bool misaligned(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) != 0; }
-size_t round16(size_t b) { return (b + 15) & ~(size_t)15; }
-unsigned blocks_for(ull n) { return (unsigned)((n + LTPB - 1) / LTPB < TABLE_GRID_MAX ? (n + LTPB - 1) / LTPB : TABLE_GRID_MAX); }
+using blh::invalid;
+using blh::misaligned16;
+using blh::round16;
+// the grid of the one-thread-per-key kernels, which stride: at most TABLE_GRID_MAX workgroups
+unsigned capped_blocks_for(ull n) { return n > (ull)TABLE_GRID_MAX * LTPB ? (unsigned)TABLE_GRID_MAX : blh::blocks_for(n, LTPB); }
 
 // KeyT: unsigned long long or __uint128_t — what rocPRIM sorts; the bytes are the table's
 template <typename KeyT>
 int build(bl_ctx* ctx, const uint64_t* d_keys, const uint32_t* d_counts, uint64_t n, uint32_t key_bits, bl_table** out)
 {
     constexpr uint32_t W = sizeof(KeyT) / 8;
-    if (!ctx || !out || (n && !d_keys) || key_bits < 1 || key_bits > 64 * W) return bl_set_error(BL_ERR_INVALID, W == 2 ? "bad argument (1 <= key_bits <= 128)" : "bad argument (1 <= key_bits <= 64)");
+    if (!ctx || !out || (n && !d_keys) || key_bits < 1 || key_bits > 64 * W) return invalid(W == 2 ? "bad argument (1 <= key_bits <= 128)" : "bad argument (1 <= key_bits <= 64)");
     *out = nullptr;
-    if (W == 2 && n && misaligned(d_keys)) return bl_set_error(BL_ERR_INVALID, "arrays of 16-byte keys must be 16-byte aligned");
-    if (n >= (1ull << 32)) return bl_set_error(BL_ERR_INVALID, "a count table takes fewer than 2^32 entries");
-    hipError_t e = hipSetDevice(bl_ctx_device(ctx));
-    if (e != hipSuccess) return hip_rc(e);
+    if (W == 2 && n && misaligned16(d_keys)) return invalid("arrays of 16-byte keys must be 16-byte aligned");
+    if (n >= (1ull << 32)) return invalid("a count table takes fewer than 2^32 entries");
+    BLH_TRY(hipSetDevice(bl_ctx_device(ctx)));
     hipStream_t s = bl_ctx_stream(ctx);
 
     ull distinct = 0;
@@ -192,15 +193,12 @@ int build(bl_ctx* ctx, const uint64_t* d_keys, const uint32_t* d_counts, uint64_
         if (!d_words) return bl_set_error(BL_ERR_OOM, "scratch allocation failed");
         // the key_bits promise, before the sort that relies on it
         ull host[3] = {0, 0, 0};
-        e = hipMemsetAsync(d_words, 0, 3 * sizeof(ull), s);
-        if (e == hipSuccess) {
-            hipLaunchKernelGGL(or_reduce_kernel, dim3(blocks_for(n)), dim3(LTPB), 0, s, d_keys, (ull)n, W, d_words);
-            e = hipGetLastError();
-        }
-        if (e == hipSuccess) e = hipMemcpyAsync(host, d_words, 2 * sizeof(ull), hipMemcpyDeviceToHost, s);
-        if (e == hipSuccess) e = hipStreamSynchronize(s);
-        if (e != hipSuccess) return hip_rc(e);
-        if (above_key_bits(host[0], host[1], key_bits)) return bl_set_error(BL_ERR_INVALID, "a key has a bit set at or above key_bits");
+        BLH_TRY(hipMemsetAsync(d_words, 0, 3 * sizeof(ull), s));
+        hipLaunchKernelGGL(or_reduce_kernel, dim3(capped_blocks_for(n)), dim3(LTPB), 0, s, d_keys, (ull)n, W, d_words);
+        BLH_TRY(hipGetLastError());
+        BLH_TRY(hipMemcpyAsync(host, d_words, 2 * sizeof(ull), hipMemcpyDeviceToHost, s));
+        BLH_TRY(hipStreamSynchronize(s));
+        if (above_key_bits(host[0], host[1], key_bits)) return invalid("a key has a bit set at or above key_bits");
 
         // slot 4: sorted keys | merged keys | sorted counts | merged counts
         const size_t kb = round16((size_t)n * sizeof(KeyT)), cb = round16((size_t)n * sizeof(uint32_t));
@@ -213,22 +211,21 @@ int build(bl_ctx* ctx, const uint64_t* d_keys, const uint32_t* d_counts, uint64_
         const KeyT* in = reinterpret_cast<const KeyT*>(d_keys);
         const rocprim::constant_iterator<uint32_t> ones(1u);
         // slot 5 for both, one after the other: the stream orders them
-        e = blh::with_workspace(ctx, 5, [&](void* ws, size_t& bytes) {
+        BLH_TRY(blh::with_workspace(ctx, 5, [&](void* ws, size_t& bytes) {
             if (d_counts) return rocprim::radix_sort_pairs(ws, bytes, in, sorted, d_counts, sorted_c, (size_t)n, 0u, key_bits, s);
             return rocprim::radix_sort_pairs(ws, bytes, in, sorted, ones, sorted_c, (size_t)n, 0u, key_bits, s);
-        });
-        if (e == hipSuccess)
-            e = blh::with_workspace(ctx, 5, [&](void* ws, size_t& bytes) {
-                return rocprim::reduce_by_key(ws, bytes, sorted, sorted_c, (size_t)n, merged, merged_c, d_words + 2, SatAdd(), rocprim::equal_to<KeyT>(), s);
-            });
-        if (e == hipSuccess) e = hipMemcpyAsync(&distinct, d_words + 2, sizeof(ull), hipMemcpyDeviceToHost, s);
-        if (e == hipSuccess) e = hipStreamSynchronize(s);
-        if (e != hipSuccess) return hip_rc(e);
+        }));
+        BLH_TRY(blh::with_workspace(ctx, 5, [&](void* ws, size_t& bytes) {
+            return rocprim::reduce_by_key(ws, bytes, sorted, sorted_c, (size_t)n, merged, merged_c, d_words + 2, SatAdd(), rocprim::equal_to<KeyT>(), s);
+        }));
+        BLH_TRY(hipMemcpyAsync(&distinct, d_words + 2, sizeof(ull), hipMemcpyDeviceToHost, s));
+        BLH_TRY(hipStreamSynchronize(s));
         if (distinct == 0 || distinct > n) return bl_set_error(BL_ERR_INTERNAL, "reduce_by_key returned an impossible number of keys");
     }
     bl_table* t = nullptr;
     const int rc = new_table(ctx, W, key_bits, distinct, &t);
     if (rc != BL_OK) return rc;
+    hipError_t e = hipSuccess;
     if (distinct) {
         e = hipMemcpyAsync(const_cast<uint64_t*>(t->view.keys), merged, (size_t)distinct * sizeof(KeyT), hipMemcpyDeviceToDevice, s);
         if (e == hipSuccess) e = hipMemcpyAsync(const_cast<uint32_t*>(t->view.counts), merged_c, (size_t)distinct * sizeof(uint32_t), hipMemcpyDeviceToDevice, s);
@@ -242,19 +239,18 @@ int build(bl_ctx* ctx, const uint64_t* d_keys, const uint32_t* d_counts, uint64_
 
 int lookup(bl_ctx* ctx, const bl_table* t, const uint64_t* d_queries, uint64_t n, uint32_t* d_out, uint32_t key_words)
 {
-    if (!ctx || !t || (n && (!d_queries || !d_out))) return bl_set_error(BL_ERR_INVALID, "NULL argument");
-    if (t->ctx != ctx) return bl_set_error(BL_ERR_INVALID, "the table belongs to another context");
-    if (t->view.key_words != key_words) return bl_set_error(BL_ERR_INVALID, key_words == 2 ? "bl_table_lookup_u128 takes a table of two-word keys" : "bl_table_lookup_u64 takes a table of one-word keys");
+    if (!ctx || !t || (n && (!d_queries || !d_out))) return invalid("NULL argument");
+    BLH_OK(blh::table_owner(t->ctx, ctx));
+    if (t->view.key_words != key_words) return invalid(key_words == 2 ? "bl_table_lookup_u128 takes a table of two-word keys" : "bl_table_lookup_u64 takes a table of one-word keys");
     if (n == 0) return BL_OK;
-    if (key_words == 2 && misaligned(d_queries)) return bl_set_error(BL_ERR_INVALID, "arrays of 16-byte keys must be 16-byte aligned");
-    hipError_t e = hipSetDevice(bl_ctx_device(ctx));
-    if (e != hipSuccess) return hip_rc(e);
+    if (key_words == 2 && misaligned16(d_queries)) return invalid("arrays of 16-byte keys must be 16-byte aligned");
+    BLH_TRY(hipSetDevice(bl_ctx_device(ctx)));
     hipStream_t s = bl_ctx_stream(ctx);
     const ull groups = (n + (ull)LTPB * G - 1) / ((ull)LTPB * G);
     hipLaunchKernelGGL(lookup_kernel, dim3((unsigned)(groups < LOOKUP_GRID_MAX ? groups : LOOKUP_GRID_MAX)), dim3(LTPB), 0, s, t->view, d_queries, (ull)n, d_out);
-    e = hipGetLastError();
-    if (e == hipSuccess) e = hipStreamSynchronize(s);
-    return e == hipSuccess ? BL_OK : hip_rc(e);
+    BLH_TRY(hipGetLastError());
+    BLH_TRY(hipStreamSynchronize(s));
+    return BL_OK;
 }
 
 }  // namespace
@@ -283,7 +279,7 @@ int bl_table_destroy(bl_table* t)
 
 int bl_table_info(const bl_table* t, uint64_t* n_distinct, uint32_t* key_words, uint32_t* key_bits, uint32_t* prefix_bits)
 {
-    if (!t) return bl_set_error(BL_ERR_INVALID, "table is NULL");
+    if (!t) return blh::invalid("table is NULL");
     if (n_distinct) *n_distinct = t->view.n;
     if (key_words) *key_words = t->view.key_words;
     if (key_bits) *key_bits = t->view.key_bits;
@@ -293,7 +289,7 @@ int bl_table_info(const bl_table* t, uint64_t* n_distinct, uint32_t* key_words, 
 
 int bl_table_arrays(const bl_table* t, const uint64_t** d_keys, const uint32_t** d_counts)
 {
-    if (!t) return bl_set_error(BL_ERR_INVALID, "table is NULL");
+    if (!t) return blh::invalid("table is NULL");
     if (d_keys) *d_keys = t->view.keys;
     if (d_counts) *d_counts = t->view.counts;
     return BL_OK;
@@ -312,32 +308,29 @@ int bl_table_lookup_u128(bl_ctx* ctx, const bl_table* t, const uint64_t* d_queri
 int bl_table_histogram(bl_ctx* ctx, const bl_table* t, uint64_t* hist, uint32_t n_bins)
 {
     using namespace bllk;
-    if (!ctx || !t || !hist || n_bins < 1 || n_bins > 65536) return bl_set_error(BL_ERR_INVALID, "bad argument (1 <= n_bins <= 65536)");
-    if (t->ctx != ctx) return bl_set_error(BL_ERR_INVALID, "the table belongs to another context");
+    if (!ctx || !t || !hist || n_bins < 1 || n_bins > 65536) return invalid("bad argument (1 <= n_bins <= 65536)");
+    BLH_OK(blh::table_owner(t->ctx, ctx));
     for (uint32_t b = 0; b < n_bins; ++b) hist[b] = 0;
     const uint32_t n = t->view.n;
     if (n == 0) return BL_OK;
-    hipError_t e = hipSetDevice(bl_ctx_device(ctx));
-    if (e != hipSuccess) return hip_rc(e);
+    BLH_TRY(hipSetDevice(bl_ctx_device(ctx)));
     hipStream_t s = bl_ctx_stream(ctx);
     ull* d_hist = static_cast<ull*>(bl_ctx_scratch(ctx, 6, (size_t)n_bins * sizeof(ull)));
     if (!d_hist) return bl_set_error(BL_ERR_OOM, "scratch allocation failed");
-    e = hipMemsetAsync(d_hist, 0, (size_t)n_bins * sizeof(ull), s);
-    if (e == hipSuccess) {
-        if (n_bins <= (uint32_t)HIST_LDS_BINS) {
-            // a workgroup clears and flushes n_bins words: give it at least that many keys
-            const ull per = n_bins > HIST_LDS_KEYS_MIN ? n_bins : HIST_LDS_KEYS_MIN;
-            const ull wg = (n + per - 1) / per;
-            hipLaunchKernelGGL(histogram_lds_kernel, dim3((unsigned)(wg < HIST_LDS_GRID_MAX ? wg : HIST_LDS_GRID_MAX)), dim3(LTPB), 0, s, t->view.counts, n, n_bins, d_hist);
-        } else {
-            hipLaunchKernelGGL(histogram_global_kernel, dim3(blocks_for(n)), dim3(LTPB), 0, s, t->view.counts, n, n_bins, d_hist);
-        }
-        e = hipGetLastError();
+    BLH_TRY(hipMemsetAsync(d_hist, 0, (size_t)n_bins * sizeof(ull), s));
+    if (n_bins <= (uint32_t)HIST_LDS_BINS) {
+        // a workgroup clears and flushes n_bins words: give it at least that many keys
+        const ull per = n_bins > HIST_LDS_KEYS_MIN ? n_bins : HIST_LDS_KEYS_MIN;
+        const ull wg = (n + per - 1) / per;
+        hipLaunchKernelGGL(histogram_lds_kernel, dim3((unsigned)(wg < HIST_LDS_GRID_MAX ? wg : HIST_LDS_GRID_MAX)), dim3(LTPB), 0, s, t->view.counts, n, n_bins, d_hist);
+    } else {
+        hipLaunchKernelGGL(histogram_global_kernel, dim3(capped_blocks_for(n)), dim3(LTPB), 0, s, t->view.counts, n, n_bins, d_hist);
     }
+    BLH_TRY(hipGetLastError());
     static_assert(sizeof(ull) == sizeof(uint64_t), "the device bins are the caller's words");
-    if (e == hipSuccess) e = hipMemcpyAsync(hist, d_hist, (size_t)n_bins * sizeof(ull), hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess) e = hipStreamSynchronize(s);
-    return e == hipSuccess ? BL_OK : hip_rc(e);
+    BLH_TRY(hipMemcpyAsync(hist, d_hist, (size_t)n_bins * sizeof(ull), hipMemcpyDeviceToHost, s));
+    BLH_TRY(hipStreamSynchronize(s));
+    return BL_OK;
 }
 
 }  // extern "C"

@@ -28,7 +28,7 @@ constexpr int HIST_LDS_BINS = 8192;          // bins a workgroup keeps in LDS (3
 constexpr int HIST_LDS_KEYS_MIN = 16 * LTPB; // keys a workgroup of the LDS histogram gets at least (and at least n_bins)
 constexpr int LOOKUP_GRID_MAX = 256 * 32;    // workgroups of lookup_kernel at most, LTPB * G queries each per step
 constexpr int HIST_LDS_GRID_MAX = 256 * 8;   // workgroups of histogram_lds_kernel at most
-constexpr int TABLE_GRID_MAX = 256 * 16;     // workgroups of the one-thread-per-key kernels at most (blocks_for): OR reduction, global histogram
+constexpr int TABLE_GRID_MAX = 256 * 16;     // workgroups of the one-thread-per-key kernels at most (capped_blocks_for): OR reduction, global histogram
 
 struct alignas(16) Key2 {
     uint64_t lo, hi;

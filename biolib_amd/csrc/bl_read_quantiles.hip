@@ -231,7 +231,6 @@ __global__ __launch_bounds__(WG_TPB) void select_wg_kernel(const SelectParams p)
 
 namespace {
 
-using blh::hip_rc;
 using blh::invalid;
 
 }  // namespace
@@ -244,10 +243,9 @@ extern "C" int bl_select_read_counts(bl_ctx* ctx, const bl_batch* batch, uint64_
 {
     using namespace blrq;
     if (!ctx || !batch) return invalid("ctx or batch is NULL");
-    bl_ctx* owner = nullptr;
-    uint64_t n_bases = 0, n_seqs = 0, read_len = 0;
-    bl_batch_describe(batch, &owner, &n_bases, &n_seqs, &read_len);
-    if (owner != ctx) return invalid("the batch belongs to another context");
+    blh::BatchView view;
+    BLH_OK(blh::batch_view(ctx, batch, view));
+    const uint64_t n_bases = view.n_bases, n_seqs = view.n_seqs, read_len = view.read_len;
     if (!d_counts || !d_valid) return invalid("d_counts and d_valid are both required: what bl_scan_kmer_counts wrote for the range");
     if (!d_quantiles) return invalid("d_quantiles is NULL");
     if (!q_num || !q_den) return invalid("q_num or q_den is NULL");
@@ -256,11 +254,9 @@ extern "C" int bl_select_read_counts(bl_ctx* ctx, const bl_batch* batch, uint64_
         if (q_den[j] == 0) return invalid("a quantile's q_den is 0");
         if (q_num[j] > q_den[j]) return invalid("a quantile's q_num exceeds its q_den");
     }
-    if (first > n_bases) return invalid("range starts beyond the batch");
-    const uint64_t end = (n == 0 || n > n_bases - first) ? n_bases : first + n;
-    if (end - first > (1ull << 31)) return invalid("a range may hold at most 2^31 positions; split it");
-    if (!d_offsets && n_seqs > 1 && read_len == 0)
-        return invalid("d_offsets is NULL: only a single-sequence or a fixed-read-length batch finds its sequences without the offsets");
+    uint64_t end = 0;
+    BLH_OK(blh::range_end(n_bases, first, n, "a range", end));
+    BLH_OK(blh::offsets_needed(d_offsets, n_seqs, read_len));
     if (end <= first) return BL_OK;  // (n_seqs >= 1 from here on)
 
     SelectParams p{};
@@ -280,8 +276,7 @@ extern "C" int bl_select_read_counts(bl_ctx* ctx, const bl_batch* batch, uint64_
     p.quantiles = d_quantiles;
     p.n_kmers = d_n_kmers;
 
-    hipError_t e = hipSetDevice(bl_ctx_device(ctx));
-    if (e != hipSuccess) return hip_rc(e);
+    BLH_TRY(hipSetDevice(bl_ctx_device(ctx)));
     hipStream_t s = bl_ctx_stream(ctx);  // behind the context's scans in flight
     // the long sequences of a range are disjoint and each longer than WAVE_MAX
     const uint64_t by_length = (end - first) / ((uint64_t)WAVE_MAX + 1);
@@ -289,17 +284,16 @@ extern "C" int bl_select_read_counts(bl_ctx* ctx, const bl_batch* batch, uint64_
     p.long_count = static_cast<unsigned long long*>(bl_ctx_scratch(ctx, 6, 128));
     p.long_list = static_cast<uint64_t*>(bl_ctx_scratch(ctx, 4, (size_t)(p.long_cap + 1) * sizeof(uint64_t)));
     if (!p.long_count || !p.long_list) return bl_set_error(BL_ERR_OOM, "scratch allocation failed");
-    e = hipMemsetAsync(p.long_count, 0, sizeof(unsigned long long), s);
-    if (e != hipSuccess) return hip_rc(e);
+    BLH_TRY(hipMemsetAsync(p.long_count, 0, sizeof(unsigned long long), s));
     const uint64_t wave_wgs = (n_seqs + WG_TPB / 64 - 1) / (WG_TPB / 64);
     hipLaunchKernelGGL(select_wave_kernel, dim3((unsigned)(wave_wgs < (uint64_t)WAVE_GRID_MAX ? wave_wgs : (uint64_t)WAVE_GRID_MAX)), dim3(WG_TPB), 0, s, p);
-    e = hipGetLastError();
+    hipError_t e = hipGetLastError();
     if (e != hipSuccess) return bl_set_error(BL_ERR_HIP, (std::string("select_wave_kernel: ") + hipGetErrorString(e)).c_str());
     if (p.long_cap) {
         hipLaunchKernelGGL(select_wg_kernel, dim3((unsigned)(p.long_cap < (uint64_t)WG_GRID_MAX ? p.long_cap : (uint64_t)WG_GRID_MAX)), dim3(WG_TPB), 0, s, p);
         e = hipGetLastError();
         if (e != hipSuccess) return bl_set_error(BL_ERR_HIP, (std::string("select_wg_kernel: ") + hipGetErrorString(e)).c_str());
     }
-    e = hipStreamSynchronize(s);
-    return e == hipSuccess ? BL_OK : hip_rc(e);
+    BLH_TRY(hipStreamSynchronize(s));
+    return BL_OK;
 }

@@ -98,21 +98,19 @@ __global__ __launch_bounds__(TPB) void gather_kernel(const SelectParams p)
 
 namespace {
 
+using blh::blocks_for;
 using blh::exclusive_sum;
-using blh::hip_rc;
 using blh::invalid;
-unsigned blocks_for(uint64_t threads) { return (unsigned)((threads + TPB - 1) / TPB); }
 
 // what both calls check of (ctx, batch, d_offsets); fills the source's description
 int describe_source(bl_ctx* ctx, const bl_batch* batch, const uint64_t* d_offsets, uint64_t& n_bases, uint64_t& n_seqs, uint64_t& read_len)
 {
-    bl_ctx* owner = nullptr;
-    uint64_t batch_read_len = 0;
-    bl_batch_describe(batch, &owner, &n_bases, &n_seqs, &batch_read_len);
-    if (owner != ctx) return invalid("the batch belongs to another context");
-    if (!d_offsets && n_seqs > 1 && batch_read_len == 0)
-        return invalid("d_offsets is NULL: only a single-sequence or a fixed-read-length batch finds its sequences without the offsets");
-    read_len = d_offsets ? 0 : (batch_read_len ? batch_read_len : (n_bases ? n_bases : 1));
+    blh::BatchView v;
+    BLH_OK(blh::batch_view(ctx, batch, v));
+    BLH_OK(blh::offsets_needed(d_offsets, v.n_seqs, v.read_len));
+    n_bases = v.n_bases;
+    n_seqs = v.n_seqs;
+    read_len = d_offsets ? 0 : (v.read_len ? v.read_len : (n_bases ? n_bases : 1));
     return BL_OK;
 }
 
@@ -127,11 +125,10 @@ extern "C" int bl_batch_select(bl_ctx* ctx, const bl_batch* batch, const uint64_
     if (!ctx || !batch || !out) return invalid("ctx, batch or out is NULL");
     *out = nullptr;
     if (!d_spans) return invalid("d_spans is NULL");
-    if (reinterpret_cast<uintptr_t>(d_spans) & 15) return invalid("d_spans must be 16-byte aligned");
+    if (blh::misaligned16(d_spans)) return invalid("d_spans must be 16-byte aligned");
     if (flags & ~(uint32_t)BL_SELECT_KEEP_EMPTY) return invalid("unknown flag bits");
     SelectParams p{};
-    int rc = describe_source(ctx, batch, d_offsets, p.n_bases, p.n_seqs, p.read_len);
-    if (rc != BL_OK) return rc;
+    BLH_OK(describe_source(ctx, batch, d_offsets, p.n_bases, p.n_seqs, p.read_len));
     p.bases = static_cast<const uint8_t*>(bl_batch_device_bases(batch));
     p.offsets = d_offsets;
     p.spans = d_spans;
@@ -139,8 +136,7 @@ extern "C" int bl_batch_select(bl_ctx* ctx, const bl_batch* batch, const uint64_
     p.user_offsets = d_out_offsets;
     p.source_index = d_source_index;
 
-    hipError_t e = hipSetDevice(bl_ctx_device(ctx));
-    if (e != hipSuccess) return hip_rc(e);
+    BLH_TRY(hipSetDevice(bl_ctx_device(ctx)));
     hipStream_t s = bl_ctx_stream(ctx);  // behind the context's scans in flight
     const uint64_t n1 = p.n_seqs + 1;
     // slot 4: len, keep, start, their two sums and the result's source starts; slot 6: the fixed-length flag
@@ -156,11 +152,10 @@ extern "C" int bl_batch_select(bl_ctx* ctx, const bl_batch* batch, const uint64_
     p.keep_sum = keep_sum;
     p.src_start = arena + 5 * n1;
 
-    hipLaunchKernelGGL(span_lengths_kernel, dim3(blocks_for(n1)), dim3(TPB), 0, s, p);
+    hipLaunchKernelGGL(span_lengths_kernel, dim3(blocks_for(n1, TPB)), dim3(TPB), 0, s, p);
     BLH_TRY(hipGetLastError());
-    rc = exclusive_sum(ctx, p.len, len_sum, (size_t)n1, s);
-    if (rc == BL_OK) rc = exclusive_sum(ctx, p.keep, keep_sum, (size_t)n1, s);  // (the first sum is done with slot 5: same stream)
-    if (rc != BL_OK) return rc;
+    BLH_OK(exclusive_sum(ctx, p.len, len_sum, (size_t)n1, s));
+    BLH_OK(exclusive_sum(ctx, p.keep, keep_sum, (size_t)n1, s));  // (the first sum is done with slot 5: same stream)
     unsigned long long total = 0, n_out = 0;
     BLH_TRY(hipMemcpyAsync(&total, len_sum + p.n_seqs, sizeof(total), hipMemcpyDeviceToHost, s));
     BLH_TRY(hipMemcpyAsync(&n_out, keep_sum + p.n_seqs, sizeof(n_out), hipMemcpyDeviceToHost, s));
@@ -174,11 +169,11 @@ extern "C" int bl_batch_select(bl_ctx* ctx, const bl_batch* batch, const uint64_
     p.out = d_bases.get();
     p.out_offsets = d_offs.get();
     BLH_TRY(hipMemsetAsync(d_bases.get() + (total & ~15ull), 0, 64 + (total & 15ull), s));  // (the last chunk's store comes after it and repeats its zeros)
-    hipLaunchKernelGGL(place_kernel, dim3(blocks_for(n1)), dim3(TPB), 0, s, p);
+    hipLaunchKernelGGL(place_kernel, dim3(blocks_for(n1, TPB)), dim3(TPB), 0, s, p);
     BLH_TRY(hipGetLastError());
     if (total) {
         const uint64_t waves = (total + WAVE_BYTES - 1) / WAVE_BYTES;
-        hipLaunchKernelGGL(gather_kernel, dim3(blocks_for(waves * 64)), dim3(TPB), 0, s, p);
+        hipLaunchKernelGGL(gather_kernel, dim3(blocks_for(waves * 64, TPB)), dim3(TPB), 0, s, p);
         BLH_TRY(hipGetLastError());
     }
     // sequences of one length make a fixed-length batch (the parser's rule): the read-tiled scan kernels, no start-bit vector
@@ -186,14 +181,13 @@ extern "C" int bl_batch_select(bl_ctx* ctx, const bl_batch* batch, const uint64_
     unsigned int ragged = 0;
     if (fixed_len) {
         BLH_TRY(hipMemsetAsync(d_flag, 0, sizeof(unsigned int), s));
-        hipLaunchKernelGGL(uniform_kernel, dim3(blocks_for(n_out + 1)), dim3(TPB), 0, s, d_offs.get(), (uint64_t)n_out, fixed_len, d_flag);
+        hipLaunchKernelGGL(uniform_kernel, dim3(blocks_for(n_out + 1, TPB)), dim3(TPB), 0, s, d_offs.get(), (uint64_t)n_out, fixed_len, d_flag);
         BLH_TRY(hipGetLastError());
         BLH_TRY(hipMemcpyAsync(&ragged, d_flag, sizeof(ragged), hipMemcpyDeviceToHost, s));
     }
     BLH_TRY(hipStreamSynchronize(s));
     if (ragged) fixed_len = 0;
-    rc = bl_batch_adopt_device(ctx, d_bases.release(), total, d_offs.release(), n_out, fixed_len, out);  // takes ownership of both
-    if (rc != BL_OK) return rc;
+    BLH_OK(bl_batch_adopt_device(ctx, d_bases.release(), total, d_offs.release(), n_out, fixed_len, out));  // takes ownership of both
     if (n_seqs_out) *n_seqs_out = n_out;
     if (n_bases_out) *n_bases_out = total;
     return BL_OK;
@@ -205,22 +199,20 @@ extern "C" int bl_read_spans(bl_ctx* ctx, const bl_batch* batch, const uint64_t*
     using namespace blsel;
     if (!ctx || !batch) return invalid("ctx or batch is NULL");
     if (!d_records || !rule || !d_spans) return invalid("d_records, rule or d_spans is NULL");
-    if ((reinterpret_cast<uintptr_t>(d_records) & 15) || (reinterpret_cast<uintptr_t>(d_spans) & 15)) return invalid("d_records and d_spans must be 16-byte aligned");
+    if (blh::misaligned16(d_records) || blh::misaligned16(d_spans)) return invalid("d_records and d_spans must be 16-byte aligned");
     SpanParams p{};
     static_assert(sizeof(p.rule) == sizeof(*rule), "one layout");
     std::memcpy(&p.rule, rule, sizeof(p.rule));
     if (!rule_valid(p.rule)) return invalid("bl_span_rule: trim is 0 .. 3, k 1 .. 64, every fraction has den >= 1 and num <= den, reserved is 0");
-    int rc = describe_source(ctx, batch, d_offsets, p.n_bases, p.n_seqs, p.read_len);
-    if (rc != BL_OK) return rc;
+    BLH_OK(describe_source(ctx, batch, d_offsets, p.n_bases, p.n_seqs, p.read_len));
     p.offsets = d_offsets;
     p.records = reinterpret_cast<const Record*>(d_records);
     p.stat = d_stat;
     p.spans = d_spans;
     if (p.n_seqs == 0) return BL_OK;
-    hipError_t e = hipSetDevice(bl_ctx_device(ctx));
-    if (e != hipSuccess) return hip_rc(e);
+    BLH_TRY(hipSetDevice(bl_ctx_device(ctx)));
     hipStream_t s = bl_ctx_stream(ctx);  // behind the scan that writes the records
-    hipLaunchKernelGGL(read_spans_kernel, dim3(blocks_for(p.n_seqs)), dim3(TPB), 0, s, p);
-    e = hipGetLastError();
+    hipLaunchKernelGGL(read_spans_kernel, dim3(blocks_for(p.n_seqs, TPB)), dim3(TPB), 0, s, p);
+    const hipError_t e = hipGetLastError();
     return e == hipSuccess ? BL_OK : bl_set_error(BL_ERR_HIP, (std::string("read_spans_kernel: ") + hipGetErrorString(e)).c_str());
 }

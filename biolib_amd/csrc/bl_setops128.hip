@@ -80,7 +80,7 @@ struct Key128HashOwner {
 
 using blh::hip_rc;
 using blkeys::bad_alignment;
-using blkeys::misaligned;
+using blh::misaligned16;
 
 int bad_key_bits() { return bl_set_error(BL_ERR_INVALID, "bad argument (1 <= key_bits <= 128)"); }
 __uint128_t* as_keys(uint64_t* p) { return reinterpret_cast<__uint128_t*>(p); }
@@ -94,7 +94,7 @@ int bl_sort_u128(bl_ctx* ctx, uint64_t* d_keys, uint64_t n, uint32_t key_bits)
 {
     if (!ctx || (n && !d_keys) || key_bits < 1 || key_bits > 128) return bad_key_bits();
     if (n == 0) return BL_OK;
-    if (misaligned(d_keys)) return bad_alignment();
+    if (misaligned16(d_keys)) return bad_alignment();
     return blkeys::sort_keys(ctx, as_keys(d_keys), n, key_bits);
 }
 
@@ -103,7 +103,7 @@ int bl_sort_unique_u128(bl_ctx* ctx, uint64_t* d_keys, uint64_t n, uint32_t key_
     if (!ctx || !n_unique || (n && !d_keys) || key_bits < 1 || key_bits > 128) return bad_key_bits();
     *n_unique = 0;
     if (n == 0) return BL_OK;
-    if (misaligned(d_keys)) return bad_alignment();
+    if (misaligned16(d_keys)) return bad_alignment();
     return blkeys::sort_unique(ctx, as_keys(d_keys), n, key_bits, n_unique);
 }
 
@@ -112,14 +112,14 @@ int bl_count_sorted_u128(bl_ctx* ctx, const uint64_t* d_sorted, uint64_t n, uint
     if (!ctx || !n_unique || (n && (!d_sorted || !d_unique || !d_counts))) return bl_set_error(BL_ERR_INVALID, "NULL argument");
     *n_unique = 0;
     if (n == 0) return BL_OK;
-    if (misaligned(d_sorted) || misaligned(d_unique)) return bad_alignment();
+    if (misaligned16(d_sorted) || misaligned16(d_unique)) return bad_alignment();
     return blkeys::count_sorted(ctx, as_keys(d_sorted), n, as_keys(d_unique), d_counts, n_unique);
 }
 
 int bl_jaccard_sorted_u128(bl_ctx* ctx, const uint64_t* d_a, uint64_t na, const uint64_t* d_b, uint64_t nb, uint64_t* intersection, uint64_t* union_size)
 {
     if (!ctx || !intersection || !union_size || (na && !d_a) || (nb && !d_b)) return bl_set_error(BL_ERR_INVALID, "NULL argument");
-    if ((na && misaligned(d_a)) || (nb && misaligned(d_b))) return bad_alignment();
+    if ((na && misaligned16(d_a)) || (nb && misaligned16(d_b))) return bad_alignment();
     if (na >= (1ull << 40) || nb >= (1ull << 40)) return bl_set_error(BL_ERR_INVALID, "bl_jaccard_sorted_u128 takes fewer than 2^40 keys per set");
     if (na == 0 || nb == 0) {
         *intersection = 0;
@@ -164,7 +164,7 @@ int bl_jaccard_sorted_u128(bl_ctx* ctx, const uint64_t* d_a, uint64_t na, const 
 int bl_partition_u128(bl_ctx* ctx, const uint64_t* d_keys, uint64_t n, uint32_t parts, uint64_t seed, uint64_t* d_out, uint64_t* counts)
 {
     if (!ctx || !counts || parts == 0 || parts > blpart::MAX_PARTS || (n && (!d_keys || !d_out))) return bl_set_error(BL_ERR_INVALID, "bad argument (1 <= parts <= 64)");
-    if (n && (misaligned(d_keys) || misaligned(d_out))) return bad_alignment();
+    if (n && (misaligned16(d_keys) || misaligned16(d_out))) return bad_alignment();
     const Key* keys = reinterpret_cast<const Key*>(d_keys);
     return blkeys::partition_keys(ctx, keys, n, parts, Key128HashOwner{keys, (uint32_t)seed}, reinterpret_cast<Key*>(d_out), counts);
 }

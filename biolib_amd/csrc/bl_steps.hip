@@ -126,24 +126,12 @@ __global__ __launch_bounds__(STPB) void gaf_write_kernel(const GafParams p) { wr
 
 namespace {
 
-int invalid(const std::string& msg) { return bl_set_error(BL_ERR_INVALID, msg.c_str()); }
-unsigned blocks_for(ull threads) { return (unsigned)((threads + STPB - 1) / STPB); }
-size_t round16(size_t b) { return (b + 15) & ~(size_t)15; }
+using blh::blocks_for;
+using blh::invalid;
+using blh::pack_prefix;
+using blh::round16;
+using blh::terminated_length;
 static_assert(sizeof(ull) == sizeof(uint64_t), "blh::exclusive_sum sums the unit's counters as the 8-byte words they are");
-
-// a NUL inside the 16 bytes: the length; none: -1
-int terminated_length(const char* s)
-{
-    for (int i = 0; i < 16; ++i)
-        if (!s[i]) return i;
-    return -1;
-}
-
-void pack_prefix(const char* s, int len, uint64_t w[2])
-{
-    w[0] = w[1] = 0;
-    for (int i = 0; i < len; ++i) w[i >> 3] |= (uint64_t)(uint8_t)s[i] << (8 * (i & 7));
-}
 
 }  // namespace
 
@@ -155,15 +143,14 @@ extern "C" int bl_scan_read_steps(bl_ctx* ctx, const bl_batch* batch, uint64_t f
 {
     using namespace blst;
     if (!ctx || !batch || !table) return invalid("ctx, batch or table is NULL");
-    bl_ctx* owner = nullptr;
-    uint64_t n_bases = 0, n_seqs = 0, read_len = 0;
-    bl_batch_describe(batch, &owner, &n_bases, &n_seqs, &read_len);
-    if (owner != ctx) return invalid("the batch belongs to another context");
-    if (table->ctx != ctx) return invalid("the table belongs to another context");
+    blh::BatchView view;
+    BLH_OK(blh::batch_view(ctx, batch, view));
+    const uint64_t n_bases = view.n_bases, n_seqs = view.n_seqs, read_len = view.read_len;
+    BLH_OK(blh::table_owner(table->ctx, ctx));
     const bllk::TableView& t = table->view;
     switch (blgr::refuse(k, t.key_words, t.key_bits, t.n)) {
     case 1: return invalid("k must be odd and 3 .. 63");
-    case 2: return invalid("2k = " + std::to_string(2 * k) + " exceeds the table's key_bits = " + std::to_string(t.key_bits));
+    case 2: return invalid(("2k = " + std::to_string(2 * k) + " exceeds the table's key_bits = " + std::to_string(t.key_bits)).c_str());
     case 3: return invalid("a table of one-word keys takes k <= 31");
     case 4: return invalid("the table has 2^31 keys or more: a step's end holds a unitig and an orientation");
     default: break;
@@ -174,22 +161,18 @@ extern "C" int bl_scan_read_steps(bl_ctx* ctx, const bl_batch* batch, uint64_t f
     default: break;
     }
     if (t.n && (!d_nodes || !d_unitig_offsets)) return invalid("d_nodes or d_unitig_offsets is NULL on a table that is not empty");
-    if (!d_offsets && n_seqs > 1 && read_len == 0)
-        return invalid("d_offsets is NULL: only a single-sequence or a fixed-read-length batch finds its sequences without the offsets");
+    BLH_OK(blh::offsets_needed(d_offsets, n_seqs, read_len));
     if (!d_steps && capacity != 0) return invalid("d_steps is NULL with a capacity: the sizing call passes capacity 0");
-    if (reinterpret_cast<uintptr_t>(d_steps) & 15) return invalid("d_steps must be 16-byte aligned");
+    if (blh::misaligned16(d_steps)) return invalid("d_steps must be 16-byte aligned");
     if (flags & ~(uint32_t)(BL_FLAG_CANONICAL | BL_FLAG_SYNC)) return invalid("flags: BL_FLAG_CANONICAL and BL_FLAG_SYNC only (the canonical form is always used)");
-    if (first > n_bases) return invalid("range starts beyond the batch");
-    const uint64_t end = (n == 0 || n > n_bases - first) ? n_bases : first + n;
-    if (end - first > (1ull << 31)) return invalid("a scan range may hold at most 2^31 positions; split it");
+    uint64_t end = 0;
+    BLH_OK(blh::range_end(n_bases, first, n, "a scan range", end));
     if (stats) *stats = bl_step_stats{};
-    int rc = bl_ctx_sync(ctx);  // the context's scans in flight
-    if (rc != BL_OK) return rc;
+    BLH_OK(bl_ctx_sync(ctx));  // the context's scans in flight
     if (end <= first) return BL_OK;
 
     const uint32_t* start_bits = nullptr;
-    rc = bl_batch_scan_view(ctx, batch, 1, &start_bits);
-    if (rc != BL_OK) return rc;
+    BLH_OK(bl_batch_scan_view(ctx, batch, 1, &start_bits));
     BLH_TRY(hipSetDevice(bl_ctx_device(ctx)));
     hipStream_t s = bl_ctx_stream(ctx);
 
@@ -204,7 +187,7 @@ extern "C" int bl_scan_read_steps(bl_ctx* ctx, const bl_batch* batch, uint64_t f
     ull* block_base = block_counts + (n_blocks + 1);
 
     NodeParams np{};
-    np.km.bases = static_cast<const uint8_t*>(bl_batch_device_bases(batch));
+    np.km.bases = view.bases;
     np.km.n_bases = (int64_t)n_bases;
     np.km.start_bits = start_bits;
     bl::plan_kmers128(s0, (int64_t)end, np.km);
@@ -218,12 +201,10 @@ extern "C" int bl_scan_read_steps(bl_ctx* ctx, const bl_batch* batch, uint64_t f
     np.words = reinterpret_cast<uint64_t*>(arena);
     BLH_TRY(hipMemsetAsync(d_stats, 0, STAT_WORDS * sizeof(ull), s));
     BLH_TRY(hipMemsetAsync(block_counts + n_blocks, 0, sizeof(ull), s));
-    rc = bl_ctx_kernel_event(ctx, s, 1);  // (bl_ctx_kernel_timing: the node pass alone)
-    if (rc != BL_OK) return rc;
+    BLH_OK(bl_ctx_kernel_event(ctx, s, 1));  // (bl_ctx_kernel_timing: the node pass alone)
     hipLaunchKernelGGL(node_kernel, dim3(bl::grid_for(np.km.n_tiles)), dim3(bl::TPB), 0, s, np, d_stats);
     BLH_TRY(hipGetLastError());
-    rc = bl_ctx_kernel_event(ctx, s, 0);
-    if (rc != BL_OK) return rc;
+    BLH_OK(bl_ctx_kernel_event(ctx, s, 0));
 
     StepParams sp{};
     sp.words = np.words;
@@ -233,11 +214,8 @@ extern "C" int bl_scan_read_steps(bl_ctx* ctx, const bl_batch* batch, uint64_t f
     sp.end = (int64_t)end;
     hipLaunchKernelGGL(ends_kernel<false>, dim3((unsigned)n_blocks), dim3(STPB), 0, s, sp, block_counts, (const ull*)nullptr, (ull)0, (uint32_t*)nullptr, (uint32_t*)nullptr);
     BLH_TRY(hipGetLastError());
-    rc = blh::exclusive_sum(ctx, reinterpret_cast<const uint64_t*>(block_counts), reinterpret_cast<uint64_t*>(block_base), (size_t)(n_blocks + 1), s);
-    if (rc != BL_OK) return rc;
-    ull n_steps = 0;
-    BLH_TRY(hipMemcpyAsync(&n_steps, block_base + n_blocks, sizeof(n_steps), hipMemcpyDeviceToHost, s));
-    BLH_TRY(hipStreamSynchronize(s));
+    uint64_t n_steps = 0;
+    BLH_OK(blh::exclusive_sum_total(ctx, reinterpret_cast<const uint64_t*>(block_counts), reinterpret_cast<uint64_t*>(block_base), (size_t)(n_blocks + 1), s, &n_steps));
 
     const bool store = d_steps && n_steps <= capacity;  // BL_ERR_CAPACITY leaves d_steps untouched
     if (n_steps) {
@@ -256,7 +234,7 @@ extern "C" int bl_scan_read_steps(bl_ctx* ctx, const bl_batch* batch, uint64_t f
         hipLaunchKernelGGL(ends_kernel<true>, dim3((unsigned)n_blocks), dim3(STPB), 0, s, sp, (ull*)nullptr, (const ull*)block_base, n_steps,
                            reinterpret_cast<uint32_t*>(ends), reinterpret_cast<uint32_t*>(ends + b_ends));
         BLH_TRY(hipGetLastError());
-        hipLaunchKernelGGL(step_kernel, dim3(blocks_for(n_steps)), dim3(STPB), 0, s, fp, store ? reinterpret_cast<Step*>(d_steps) : (Step*)nullptr, d_stats);
+        hipLaunchKernelGGL(step_kernel, dim3(blocks_for(n_steps, STPB)), dim3(STPB), 0, s, fp, store ? reinterpret_cast<Step*>(d_steps) : (Step*)nullptr, d_stats);
         BLH_TRY(hipGetLastError());
     }
     ull host[STAT_WORDS] = {};
@@ -280,7 +258,7 @@ extern "C" int bl_link_support(bl_ctx* ctx, const bl_read_step* d_steps, uint64_
     using namespace blst;
     if (!ctx) return invalid("ctx is NULL");
     if (n_steps && !d_steps) return invalid("d_steps is NULL with n_steps > 0");
-    if (reinterpret_cast<uintptr_t>(d_steps) & 15) return invalid("d_steps must be 16-byte aligned");
+    if (blh::misaligned16(d_steps)) return invalid("d_steps must be 16-byte aligned");
     if (n_unitigs >= (1ull << 31)) return invalid("n_unitigs must be below 2^31");
     if (n_unitigs && !d_link_offsets) return invalid("d_link_offsets is NULL with n_unitigs > 0");
     if (n_links && (!d_links || !d_support)) return invalid("d_links or d_support is NULL with n_links > 0");
@@ -300,7 +278,7 @@ extern "C" int bl_link_support(bl_ctx* ctx, const bl_read_step* d_steps, uint64_
         p.n_links = n_links;
         p.n_unitigs = n_unitigs;
         p.support = d_support;
-        hipLaunchKernelGGL(support_kernel, dim3(blocks_for(n_steps - 1)), dim3(STPB), 0, s, p, d_counters);
+        hipLaunchKernelGGL(support_kernel, dim3(blocks_for(n_steps - 1, STPB)), dim3(STPB), 0, s, p, d_counters);
         BLH_TRY(hipGetLastError());
     }
     ull host[2] = {};
@@ -328,17 +306,18 @@ extern "C" int bl_steps_format_gaf(bl_ctx* ctx, const bl_batch* batch, const uin
     case 4: return invalid("bl_gaf_rule: reserved must be 0");
     default: break;
     }
-    bl_ctx* owner = nullptr;
-    GafParams p{};
-    bl_batch_describe(batch, &owner, &p.n_bases, &p.n_seqs, &p.read_len);
-    if (owner != ctx) return invalid("the batch belongs to another context");
-    if (!d_offsets && p.n_seqs > 1 && p.read_len == 0)
-        return invalid("d_offsets is NULL: only a single-sequence or a fixed-read-length batch finds its sequences without the offsets");
-    if (reinterpret_cast<uintptr_t>(d_out) & 15) return invalid("d_out must be 16-byte aligned");
-    if (reinterpret_cast<uintptr_t>(d_steps) & 15) return invalid("d_steps must be 16-byte aligned");
+    blh::BatchView view;
+    BLH_OK(blh::batch_view(ctx, batch, view));
+    BLH_OK(blh::offsets_needed(d_offsets, view.n_seqs, view.read_len));
+    if (blh::misaligned16(d_out)) return invalid("d_out must be 16-byte aligned");
+    if (blh::misaligned16(d_steps)) return invalid("d_steps must be 16-byte aligned");
     if (n_steps && !d_steps) return invalid("d_steps is NULL with n_steps > 0");
     if (n_unitigs && !d_unitig_offsets) return invalid("d_unitig_offsets is NULL with n_unitigs > 0");
     if (n_steps == 0) return BL_OK;
+    GafParams p{};
+    p.n_bases = view.n_bases;
+    p.n_seqs = view.n_seqs;
+    p.read_len = view.read_len;
     p.steps = reinterpret_cast<const Step*>(d_steps);
     p.n_steps = n_steps;
     p.unitig_offsets = d_unitig_offsets;
@@ -374,33 +353,27 @@ extern "C" int bl_steps_format_gaf(bl_ctx* ctx, const bl_batch* batch, const uin
     uint64_t* line_off = arena + 10 * n1;
     p.line_off = line_off;
     BLH_TRY(hipMemsetAsync(d_counters, 0, sizeof(ull), s));
-    hipLaunchKernelGGL(gaf_measure_kernel, dim3(blocks_for(n1)), dim3(STPB), 0, s, p, d_counters);
+    hipLaunchKernelGGL(gaf_measure_kernel, dim3(blocks_for(n1, STPB)), dim3(STPB), 0, s, p, d_counters);
     BLH_TRY(hipGetLastError());
-    for (int j = 0; j < 4; ++j) {
-        const int rc = blh::exclusive_sum(ctx, arena + j * n1, sums + j * n1, (size_t)n1, s);
-        if (rc != BL_OK) return rc;
-    }
+    for (int j = 0; j < 4; ++j) BLH_OK(blh::exclusive_sum(ctx, arena + j * n1, sums + j * n1, (size_t)n1, s));
     ull continued = 0, n_chains = 0;
     BLH_TRY(hipMemcpyAsync(&continued, d_counters, sizeof(ull), hipMemcpyDeviceToHost, s));
     BLH_TRY(hipMemcpyAsync(&n_chains, p.head_sum + n_steps, sizeof(ull), hipMemcpyDeviceToHost, s));
     BLH_TRY(hipStreamSynchronize(s));
     if (continued) return invalid("a step carries BL_STEP_CONTINUED: fold the records of consecutive ranges first");
     p.n_chains = n_chains;
-    hipLaunchKernelGGL(gaf_chain_kernel, dim3(blocks_for(n1)), dim3(STPB), 0, s, p);
+    hipLaunchKernelGGL(gaf_chain_kernel, dim3(blocks_for(n1, STPB)), dim3(STPB), 0, s, p);
     BLH_TRY(hipGetLastError());
-    hipLaunchKernelGGL(gaf_length_kernel, dim3(blocks_for(n_chains + 1)), dim3(STPB), 0, s, p);
+    hipLaunchKernelGGL(gaf_length_kernel, dim3(blocks_for(n_chains + 1, STPB)), dim3(STPB), 0, s, p);
     BLH_TRY(hipGetLastError());
-    const int rc = blh::exclusive_sum(ctx, p.line_len, line_off, (size_t)(n_chains + 1), s);
-    if (rc != BL_OK) return rc;
-    ull total = 0;
-    BLH_TRY(hipMemcpyAsync(&total, line_off + n_chains, sizeof(total), hipMemcpyDeviceToHost, s));
-    BLH_TRY(hipStreamSynchronize(s));
+    uint64_t total = 0;
+    BLH_OK(blh::exclusive_sum_total(ctx, p.line_len, line_off, (size_t)(n_chains + 1), s, &total));
     if (n_bytes) *n_bytes = total;
     if (!d_out) return BL_OK;  // sizing only
     if (capacity < total) return bl_set_error(BL_ERR_CAPACITY, "bl_steps_format_gaf: d_out is smaller than the text (*n_bytes says how large it is)");
     p.total = total;
     p.out = d_out;
-    hipLaunchKernelGGL(gaf_write_kernel, dim3(blocks_for(n_steps)), dim3(STPB), 0, s, p);
+    hipLaunchKernelGGL(gaf_write_kernel, dim3(blocks_for(n_steps, STPB)), dim3(STPB), 0, s, p);
     BLH_TRY(hipGetLastError());
     BLH_TRY(hipStreamSynchronize(s));
     return BL_OK;

@@ -24,6 +24,7 @@
 #pragma once
 #include "bl_format_core.hpp"
 #include "bl_lookup_core.hpp"
+#include "bl_unitig_records.hpp"
 
 namespace blst {
 
@@ -32,12 +33,8 @@ constexpr uint64_t NO_NODE = ~0ull;       // (an end is below 2^32 - 2: n_unitig
 constexpr uint32_t LINKED = 1u, CONTINUED = 2u;  // include/biolib_amd.h: BL_STEP_*
 constexpr uint32_t HEAD = 1u, TAIL = 2u;
 
-struct alignas(8) Node {  // bl_unitig_node
-    uint32_t unitig, rank_flip;
-};
-struct LinkWords {  // bl_unitig_link
-    uint32_t from, to;
-};
+using blrec::LinkWords;
+using blrec::Node;
 struct alignas(16) Step {  // bl_read_step
     uint64_t pos, seq;
     uint32_t end, offset, n_kmers, flags;

@@ -131,8 +131,7 @@ using blh::hip_rc;
 template <typename K>
 int combine(bl_ctx* ctx, const bl_table* ta, const bl_table* tb, const Rule& rule, bl_table** out, bl_table_stats* stats)
 {
-    hipError_t e = hipSetDevice(bl_ctx_device(ctx));
-    if (e != hipSuccess) return hip_rc(e);
+    BLH_TRY(hipSetDevice(bl_ctx_device(ctx)));
     hipStream_t s = bl_ctx_stream(ctx);
     Tables in{};
     in.a = ta->view.keys;
@@ -157,15 +156,12 @@ int combine(bl_ctx* ctx, const bl_table* ta, const bl_table* tb, const Rule& rul
         if (!d_counters || !splits) return bl_set_error(BL_ERR_OOM, "scratch allocation failed");
         totals = splits + n_tiles + 1;
         bases = totals + n_tiles;
-        e = hipMemsetAsync(d_counters, 0, (WRITTEN + 1) * sizeof(ull), s);
-        if (e == hipSuccess) {
-            hipLaunchKernelGGL(table_partition_kernel<K>, dim3((unsigned)((n_tiles + 1 + TPB - 1) / TPB)), dim3(TPB), 0, s, in, n_tiles, splits);
-            hipLaunchKernelGGL(table_count_kernel<K>, dim3((unsigned)n_tiles), dim3(TPB), 0, s, in, rule, splits, totals, d_counters);
-            e = hipGetLastError();
-        }
-        if (e == hipSuccess) e = hipMemcpyAsync(host, d_counters, N_STATS * sizeof(ull), hipMemcpyDeviceToHost, s);
-        if (e == hipSuccess) e = hipStreamSynchronize(s);
-        if (e != hipSuccess) return hip_rc(e);
+        BLH_TRY(hipMemsetAsync(d_counters, 0, (WRITTEN + 1) * sizeof(ull), s));
+        hipLaunchKernelGGL(table_partition_kernel<K>, dim3((unsigned)((n_tiles + 1 + TPB - 1) / TPB)), dim3(TPB), 0, s, in, n_tiles, splits);
+        hipLaunchKernelGGL(table_count_kernel<K>, dim3((unsigned)n_tiles), dim3(TPB), 0, s, in, rule, splits, totals, d_counters);
+        BLH_TRY(hipGetLastError());
+        BLH_TRY(hipMemcpyAsync(host, d_counters, N_STATS * sizeof(ull), hipMemcpyDeviceToHost, s));
+        BLH_TRY(hipStreamSynchronize(s));
     }
     const ull n_out = host[3];
     if (stats) {
@@ -190,13 +186,13 @@ int combine(bl_ctx* ctx, const bl_table* ta, const bl_table* tb, const Rule& rul
         if (rc != BL_OK) { bllk::free_table(t); return rc; }
         hipLaunchKernelGGL(table_write_kernel<K>, dim3((unsigned)n_tiles), dim3(TPB), 0, s, in, rule, splits, bases, n_out,
                            reinterpret_cast<K*>(const_cast<uint64_t*>(t->view.keys)), const_cast<uint32_t*>(t->view.counts), d_counters);
-        e = hipGetLastError();
+        hipError_t e = hipGetLastError();
         if (e == hipSuccess) e = hipMemcpyAsync(&host[WRITTEN], d_counters + WRITTEN, sizeof(ull), hipMemcpyDeviceToHost, s);
         if (e == hipSuccess) e = hipStreamSynchronize(s);
         if (e != hipSuccess) { bllk::free_table(t); return hip_rc(e); }
         if (host[WRITTEN] != n_out) { bllk::free_table(t); return bl_set_error(BL_ERR_INTERNAL, "the write pass emitted another number of keys than the count pass"); }
     }
-    e = bllk::finish_table(ctx, t, s);
+    const hipError_t e = bllk::finish_table(ctx, t, s);
     if (e != hipSuccess) { bllk::free_table(t); return hip_rc(e); }
     *out = t;
     return BL_OK;
@@ -210,21 +206,22 @@ int bl_table_combine(bl_ctx* ctx, const bl_table* a, const bl_table* b, uint32_t
                      bl_table_stats* stats)
 {
     if (out) *out = nullptr;
-    if (!ctx || !a) return bl_set_error(BL_ERR_INVALID, "ctx or table a is NULL");
-    if (a->ctx != ctx || (b && b->ctx != ctx)) return bl_set_error(BL_ERR_INVALID, "the table belongs to another context");
+    if (!ctx || !a) return blh::invalid("ctx or table a is NULL");
+    BLH_OK(blh::table_owner(a->ctx, ctx));
+    if (b) BLH_OK(blh::table_owner(b->ctx, ctx));
     if (b && (b->view.key_words != a->view.key_words || b->view.key_bits != a->view.key_bits))
-        return bl_set_error(BL_ERR_INVALID, "the two tables differ in key_words or key_bits");
-    if (op >= N_OPS) return bl_set_error(BL_ERR_INVALID, "unknown op (BL_TABLE_UNION .. BL_TABLE_COUNT_SUBTRACT)");
-    if (count_mode >= N_MODES) return bl_set_error(BL_ERR_INVALID, "unknown count mode (BL_COUNT_SUM .. BL_COUNT_RIGHT)");
-    if (!rule_ok(op, count_mode)) return bl_set_error(BL_ERR_INVALID, "BL_TABLE_SUBTRACT and BL_TABLE_COUNT_SUBTRACT take BL_COUNT_LEFT only");
-    if (count_lo > count_hi) return bl_set_error(BL_ERR_INVALID, "count_lo exceeds count_hi");
+        return blh::invalid("the two tables differ in key_words or key_bits");
+    if (op >= N_OPS) return blh::invalid("unknown op (BL_TABLE_UNION .. BL_TABLE_COUNT_SUBTRACT)");
+    if (count_mode >= N_MODES) return blh::invalid("unknown count mode (BL_COUNT_SUM .. BL_COUNT_RIGHT)");
+    if (!rule_ok(op, count_mode)) return blh::invalid("BL_TABLE_SUBTRACT and BL_TABLE_COUNT_SUBTRACT take BL_COUNT_LEFT only");
+    if (count_lo > count_hi) return blh::invalid("count_lo exceeds count_hi");
     const Rule rule{op, count_mode, count_lo, count_hi};
     return a->view.key_words == 2 ? combine<Key2>(ctx, a, b, rule, out, stats) : combine<Key1>(ctx, a, b, rule, out, stats);
 }
 
 int bl_table_filter(bl_ctx* ctx, const bl_table* a, uint32_t count_lo, uint32_t count_hi, bl_table** out)
 {
-    if (!out) return bl_set_error(BL_ERR_INVALID, "out is NULL");
+    if (!out) return blh::invalid("out is NULL");
     return bl_table_combine(ctx, a, nullptr, BL_TABLE_UNION, BL_COUNT_LEFT, count_lo, count_hi, out, nullptr);
 }
 
