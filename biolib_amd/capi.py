@@ -32,6 +32,7 @@ SYMBOLS = [
     "bl_text_index_build", "bl_text_index_info", "bl_text_index_offsets", "bl_text_index_destroy", "bl_reader_next_batch_device_indexed", "bl_batch_format",
     "bl_text_write", "bl_bgzf_bound", "bl_bgzf_deflate", "bl_text_write_bgzf",
     "bl_scan_read_steps", "bl_link_support", "bl_steps_format_gaf",
+    "bl_scan_read_quality", "bl_spans_intersect",
 ]
 
 
@@ -113,6 +114,29 @@ class FormatRule(C.Structure):
     """bl_format_rule (64 bytes)"""
     _fields_ = [("format", C.c_uint32), ("flags", C.c_uint32), ("line_width", C.c_uint32), ("quality_fill", C.c_uint32), ("name_prefix", C.c_char * 16),
                 ("first_number", C.c_uint64), ("tag_label", C.c_char * 16), ("reserved", C.c_uint64)]
+
+
+QFAIL_MIN_LEN, QFAIL_MAX_LEN, QFAIL_AMBIGUOUS, QFAIL_LOW, QFAIL_MEAN, QFAIL_EE = 1, 2, 4, 8, 16, 32
+SPANS_PAIRED = 1
+# bl_read_quality as a numpy record (48 bytes)
+READ_QUALITY_DTYPE = [("begin", "<u8"), ("end", "<u8"), ("sum", "<u8"), ("ee", "<u8"), ("n_low", "<u4"), ("n_ambiguous", "<u4"), ("q_min", "u1"),
+                      ("q_max", "u1"), ("failed", "<u2"), ("reserved", "<u4")]
+
+
+class QualityRule(C.Structure):
+    """bl_quality_rule (80 bytes)"""
+    _fields_ = [(name, C.c_uint32) for name in ("phred_base", "quality_fill", "front_q", "back_q", "maxsum_front_q", "maxsum_back_q", "window_len",
+                                                "window_q", "low_q", "low_max_num", "low_max_den", "mean_q", "max_ambiguous", "reserved")] + \
+               [(name, C.c_uint64) for name in ("min_len", "max_len", "max_ee")]
+
+
+class QualityStats(C.Structure):
+    """bl_quality_stats"""
+    _fields_ = [(name, C.c_uint64) for name in ("n_reads", "n_reads_kept", "n_bases", "n_bases_kept", "n_too_short", "n_too_long", "n_ambiguous",
+                                                "n_low", "n_mean", "n_ee")] + [("reserved", C.c_uint64 * 2)]
+
+    def as_dict(self):
+        return {name: int(getattr(self, name)) for name, _ in self._fields_ if name != "reserved"}
 
 
 LINK_NONE = 0xFFFFFFFF
@@ -357,6 +381,9 @@ def lib():
         L.bl_scan_read_steps.argtypes = [vp, vp, u64, u64, u32, u32, vp, vp, vp, u64, vp, vp, u64, C.POINTER(StepStats)]
         L.bl_link_support.argtypes = [vp, vp, u64, vp, vp, u64, u64, vp, C.POINTER(SupportStats)]
         L.bl_steps_format_gaf.argtypes = [vp, vp, vp, vp, u64, vp, u64, C.POINTER(GafRule), vp, u64, C.POINTER(u64)]
+    if "BIOLIB_AMD_LIB" not in os.environ or hasattr(L, "bl_scan_read_quality"):
+        L.bl_scan_read_quality.argtypes = [vp, vp, vp, C.POINTER(QualityRule), vp, vp, C.POINTER(QualityStats)]
+        L.bl_spans_intersect.argtypes = [vp, vp, vp, vp, vp, u32, vp]
     _lib = L
     return L
 

@@ -34,6 +34,7 @@ struct bl_text_index {
     blfmt::TextRecord* d_records = nullptr;  // pool: max(n_records, 1)
     uint64_t* d_offsets = nullptr;           // pool: n_records + 1
     uint64_t n_records = 0;
+    uint64_t n_bases = 0;  // of the batch it was built with: d_offsets[n_records]
     int fastq = 0;
 };
 
@@ -146,6 +147,7 @@ int index_device_text(bl_ctx* ctx, bl_text_index* ix, char first_byte, const cha
         return code;
     };
     ix->n_records = li.n_records;
+    ix->n_bases = li.total;
     ix->fastq = first_byte == '@';
     ix->d_records = static_cast<TextRecord*>(bl_ctx_pool_alloc(ctx, (size_t)(li.n_records ? li.n_records : 1) * sizeof(TextRecord)));
     ix->d_offsets = static_cast<uint64_t*>(bl_ctx_pool_alloc(ctx, (size_t)(li.n_records + 1) * sizeof(uint64_t)));
@@ -258,6 +260,14 @@ extern "C" int bl_text_index_info(const bl_text_index* ix, uint64_t* n_records, 
 }
 
 extern "C" const uint64_t* bl_text_index_offsets(const bl_text_index* ix) { return ix ? ix->d_offsets : nullptr; }
+
+int bl_text_index_describe(const bl_text_index* ix, bl_ctx** ctx, uint64_t* n_bases)
+{
+    if (!ix) return blh::invalid("NULL argument");
+    *ctx = ix->ctx;
+    *n_bases = ix->n_bases;
+    return BL_OK;
+}
 
 extern "C" int bl_text_index_destroy(bl_text_index* ix)
 {

@@ -4,6 +4,7 @@ Device memory for outputs comes from torch (plumbing only): int64 CUDA tensors w
 kernels fill with uint64 records; `.view(np.uint64)` on the host copy restores the type.
 """
 import ctypes as C
+import math
 import weakref
 
 import numpy as np
@@ -1089,6 +1090,22 @@ class ReadCounts:
         return self.records[:self.n_seqs].cpu().numpy().view(dt).reshape(-1).copy()
 
 
+class ReadQuality:
+    """What bl_scan_read_quality wrote, one row per read: `records` is the raw device buffer, int64[n_seqs, 6] (capi.READ_QUALITY_DTYPE;
+    begin and end are the trimmed span before the filters), `spans` an int64 device tensor [n_seqs, 2] for select and format — (0, 0)
+    where a filter failed — and `stats` the call's totals as a dict, or None where they were not asked for."""
+
+    def __init__(self, n_seqs, records, spans, stats):
+        self.n_seqs = int(n_seqs)
+        self.records = records
+        self.spans = spans
+        self.stats = stats
+
+    def host(self):
+        """a numpy structured array of the records (capi.READ_QUALITY_DTYPE)"""
+        return self.records[:self.n_seqs].cpu().numpy().view(np.dtype(capi.READ_QUALITY_DTYPE)).reshape(-1).copy()
+
+
 class Batch:
     """Device-resident sequences (bl_batch)."""
 
@@ -1547,6 +1564,86 @@ class Batch:
         spans = self.read_spans(rc, k, trim, min_len, min_kmers, solid_min, solid_max, offsets=offsets)
         out, source_index = self.select(spans, keep_empty, offsets=offsets)
         return out, source_index, rc
+
+    # ---- quality trimming and filtering: spans from the quality bytes of the indexed text
+    def read_quality_raw(self, index, rule, records=None, spans=None, stats=None):
+        """bl_scan_read_quality: `index` the TextIndex this batch was built with, `rule` a capi.QualityRule, `records` (n_seqs rows of 48
+        bytes) and `spans` (n_seqs pairs of 64-bit words) 16-byte aligned device tensors or None, `stats` a capi.QualityStats or None.
+        Asynchronous on the context's stream without stats.  The library checks every argument."""
+        check(self._lib.bl_scan_read_quality(self.ctx._h, self._h, index._h if index is not None else None, C.byref(rule), _ptr(records), _ptr(spans),
+                                             C.byref(stats) if stats is not None else None))
+
+    @staticmethod
+    def quality_rule(phred=33, front_q=0, back_q=0, maxsum_q=(0, 0), window=None, low_q=0, max_low=None, mean_q=0, max_ambiguous=None, min_len=0,
+                     max_len=0, max_ee=None, quality_fill="I"):
+        r = capi.QualityRule()
+        r.phred_base = int(phred)
+        r.quality_fill = quality_fill if isinstance(quality_fill, int) else (quality_fill.encode("latin1") if isinstance(quality_fill, str) else bytes(quality_fill))[0]
+        r.front_q, r.back_q = int(front_q), int(back_q)
+        r.maxsum_front_q, r.maxsum_back_q = (int(maxsum_q), int(maxsum_q)) if isinstance(maxsum_q, int) else (int(maxsum_q[0]), int(maxsum_q[1]))
+        r.window_len, r.window_q = (0, 0) if window is None else (int(window[0]), int(window[1]))
+        r.low_q = int(low_q)
+        r.low_max_num, r.low_max_den = Batch._fraction(max_low, (1, 1))
+        r.mean_q = int(mean_q)
+        r.max_ambiguous = 2**32 - 1 if max_ambiguous is None else int(max_ambiguous)
+        r.min_len, r.max_len = int(min_len), int(max_len)
+        r.max_ee = 2**64 - 1 if max_ee is None else min(int(math.floor(max_ee * 2**31)), 2**64 - 1)
+        return r
+
+    def read_quality(self, index, phred=33, front_q=0, back_q=0, maxsum_q=(0, 0), window=None, low_q=0, max_low=None, mean_q=0, max_ambiguous=None,
+                     min_len=0, max_len=0, max_ee=None, quality_fill="I", stats=False):
+        """Trim and filter every read by its quality values (bl_scan_read_quality): a ReadQuality.  `index` is the TextIndex this batch
+        came with (from_text_indexed, device_batches(indexed=True)); a FASTA index gives quality_fill everywhere.  The Phred value of a
+        byte is min(max(byte - phred, 0), 93).  Trimming, in this order, each off at 0 / None:
+        front_q, back_q   cut the leading values below front_q and the trailing ones below back_q
+        maxsum_q          (front, back) or one number: the running-sum cut of BWA and cutadapt -q
+        window            (W, q): cut at the first window of W values whose mean is below q, and the values below q in front of it
+        Then the filters over the trimmed span: min_len, max_len (0: none), max_ambiguous bases that are not ACGTU, max_low = the
+        fraction ((num, den) or a number) of values below low_q allowed, mean_q, max_ee = the expected number of errors allowed.
+        stats=True makes the call synchronous and fills `.stats`."""
+        import torch
+
+        rule = self.quality_rule(phred, front_q, back_q, maxsum_q, window, low_q, max_low, mean_q, max_ambiguous, min_len, max_len, max_ee, quality_fill)
+        n = self.n_seqs
+        dev = self.ctx.torch_device
+        records = torch.zeros((max(n, 1), 6), dtype=torch.int64, device=dev)  # (torch allocations are 16-byte aligned)
+        spans = torch.zeros((max(n, 1), 2), dtype=torch.int64, device=dev)
+        st = capi.QualityStats() if stats else None
+        self.ctx._inputs_ready()
+        self.read_quality_raw(index, rule, records, spans, st)
+        return ReadQuality(n, records[:n], spans[:n], st.as_dict() if stats else None)
+
+    def intersect_spans_raw(self, a, b, flags, out, offsets=None):
+        """bl_spans_intersect: `a`, `b` (or None) and `out` hold n_seqs pairs of 64-bit words, 16-byte aligned; out may be a or b.
+        Asynchronous on the context's stream."""
+        check(self._lib.bl_spans_intersect(self.ctx._h, self._h, _ptr(offsets), _ptr(a), _ptr(b), int(flags), _ptr(out)))
+
+    def intersect_spans(self, a, b=None, paired=False, offsets=None):
+        """The spans of `a` and `b` joined read by read (bl_spans_intersect): an int64 device tensor [n_seqs, 2].  Both are clamped to
+        the read as select clamps them; the result is [max of the begins, min of the ends), (0, 0) where that is empty.  b=None: a
+        alone.  paired: reads 2j and 2j + 1 are mates, and where either span is empty both become (0, 0)."""
+        import torch
+
+        n = self.n_seqs
+        for name, t in (("a", a), ("b", b)):
+            if t is not None and not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.int64 and t.is_contiguous() and t.numel() == 2 * n):
+                raise ValueError(name + ": a contiguous int64 device tensor [n_seqs, 2]")
+        out = torch.zeros((max(n, 1), 2), dtype=torch.int64, device=self.ctx.torch_device)
+        if n == 0:
+            return out[:0]
+        self.ctx._inputs_ready()
+        self.intersect_spans_raw(a, b, capi.SPANS_PAIRED if paired else 0, out, self._device_offsets(offsets))
+        return out[:n]
+
+    def trim_by_quality(self, index, paired=False, keep_empty=None, **rule):
+        """Quality trimming and filtering in one chain on the device: read_quality(index, **rule), intersect_spans(paired) where the
+        reads are interleaved mates, select.  (Batch, source_index, spans, ReadQuality): the trimmed reads as a new batch, where each
+        came from, the spans that went into select (what format takes for the qualities) and the source's records.  keep_empty defaults
+        to `paired`, so that mates stay in step."""
+        rq = self.read_quality(index, **rule)
+        spans = self.intersect_spans(rq.spans, None, True) if paired else rq.spans
+        out, source_index = self.select(spans, paired if keep_empty is None else keep_empty)
+        return out, source_index, spans, rq
 
     # ---- threading: the reads' steps through the compacted graph
     def read_steps_raw(self, table, k, flags, nodes, unitig_offsets, n_unitigs, steps, capacity, first=0, n=0, offsets=None, stats=None):

@@ -996,6 +996,77 @@ int bl_batch_format(bl_ctx* ctx, const bl_batch* batch, const uint64_t* d_offset
                     const bl_format_rule* rule, uint8_t* d_out, uint64_t capacity, uint64_t* n_bytes, uint64_t* n_records);
 int bl_text_write(bl_ctx* ctx, const uint8_t* d_text, uint64_t n_bytes, const char* path, int append);
 
+/* Quality trimming and filtering on the device: the first step of a short-read pipeline (fastp, Trimmomatic, cutadapt -q) from the
+ * quality bytes the index keeps.  bl_scan_read_quality makes one span per read, in the form bl_batch_select and bl_batch_format take.
+ *
+ * `batch` is the batch `index` was built with (same context, n_seqs == n_records, same n_bases; the offsets are the index's own).  Read i
+ * has length L; its quality bytes are what bl_batch_format writes as the quality line of sequence i with this index, no d_source_index,
+ * no d_spans and the rule's quality_fill: a FASTA index gives the fill everywhere.  The Phred value is
+ * v[j] = min(max(byte - phred_base, 0), 93).
+ *
+ * Trimming.  The span starts as [b, e) = [0, L); three steps in this order, each off at its zero value:
+ *   A  edges (front_q, back_q)   b = the first j >= b with v[j] >= front_q, or e; then e = one past the last j in [b, e) with
+ *      v[j] >= back_q, or b
+ *   B  running sum (maxsum_front_q, maxsum_back_q), the rule of BWA and cutadapt -q; both ends are decided on step A's span.  Back, with
+ *      cutoff c: walk i = e - 1 down to b with s += c - v[i] and stop at the first s < 0; e' = the i of the first strict maximum of s
+ *      above 0, e where there is none.  Front is the mirror image, b' = i + 1.  The span becomes [b', max(b', e')).
+ *   C  window (window_len W = 1 .. 65535, window_q)   the smallest j in [b, e - W] whose W values from j on sum to less than
+ *      W * window_q; if there is one, e = j, then e moves left while e > b and v[e - 1] < window_q.  A span shorter than W is not tested.
+ * Statistics over the trimmed span, n = e - b: sum of the values; ee = the sum of BL_PHRED_ERR[v] = floor(2^31 * 10^(-v/10) + 1/2), the
+ * expected number of errors in units of 2^-31; q_min and q_max (255 and 0 for an empty span); n_low = #{v < low_q}; n_ambiguous = the
+ * bases of the span that the scans' encoder takes as invalid (anything but ACGTUacgtu).  The two counts saturate at UINT32_MAX.
+ * Filters; each sets its bit of `failed`, and all that fail are set:
+ *   BL_QFAIL_MIN_LEN   n < min_len                      BL_QFAIL_LOW    n_low * low_max_den > n * low_max_num
+ *   BL_QFAIL_MAX_LEN   max_len != 0 and n > max_len     BL_QFAIL_MEAN   sum < mean_q * n
+ *   BL_QFAIL_AMBIGUOUS n_ambiguous > max_ambiguous      BL_QFAIL_EE     ee > max_ee
+ * The neutral values are 0, 0, UINT32_MAX, (1, 1), 0 and UINT64_MAX.
+ * Outputs, each nullable: d_records[i] (48 bytes, 16-byte aligned; begin and end are the trimmed span BEFORE the filters);
+ * d_spans[2i], d_spans[2i+1] = (begin, end) where failed == 0, else (0, 0); *stats (host).  Without stats the call is asynchronous on
+ * the context's stream like the scans; with stats it is synchronous.  Results are bit-reproducible: the statistics are integer sums,
+ * and no atomic decides a value.  No byte outside the text's n_bytes, the batch's n_bases or the outputs is touched.
+ * BL_ERR_INVALID with a message, nothing launched: a NULL ctx, batch, index or rule; a batch or index of another context; a batch that is
+ * not the index's; phred_base other than 33 or 64; quality_fill outside 33 .. 126; a threshold above 94; window_len above 65535;
+ * low_max_den 0 or low_max_num > low_max_den; reserved != 0; d_records or d_spans not 16-byte aligned.
+ *
+ * bl_spans_intersect joins two span arrays of one batch (d_offsets as bl_batch_select takes them), one lane per read: both spans are
+ * clamped to the read as bl_batch_select clamps them, out = [max of the begins, min of the ends), or (0, 0) where that is empty.  d_b
+ * NULL: d_a alone.  BL_SPANS_PAIRED (n_seqs even; reads 2j and 2j + 1 are mates): where either result is empty both become (0, 0), so
+ * that a dropped read takes its mate along.  d_out may be d_a or d_b.  Asynchronous.  BL_ERR_INVALID: a NULL ctx, batch, d_a or d_out; a
+ * batch of another context; d_offsets NULL on a ragged batch; a misaligned array; unknown flag bits; an odd n_seqs with the flag. */
+enum { BL_QFAIL_MIN_LEN = 1, BL_QFAIL_MAX_LEN = 2, BL_QFAIL_AMBIGUOUS = 4, BL_QFAIL_LOW = 8, BL_QFAIL_MEAN = 16, BL_QFAIL_EE = 32 };
+typedef struct bl_quality_rule {
+    uint32_t phred_base;      /* 33 or 64 */
+    uint32_t quality_fill;    /* the byte of a position without a quality byte, 33..126 */
+    uint32_t front_q, back_q;                 /* step A; 0 = off */
+    uint32_t maxsum_front_q, maxsum_back_q;   /* step B; 0 = off */
+    uint32_t window_len, window_q;            /* step C; window_len 0 = off */
+    uint32_t low_q, low_max_num, low_max_den; /* fail where n_low * den > n * num; den >= 1, num <= den */
+    uint32_t mean_q;
+    uint32_t max_ambiguous;
+    uint32_t reserved;        /* 0 */
+    uint64_t min_len, max_len; /* max_len 0 = no limit */
+    uint64_t max_ee;          /* in units of 2^-31 */
+} bl_quality_rule;
+typedef struct bl_read_quality {
+    uint64_t begin, end;      /* the trimmed span, before the filters */
+    uint64_t sum, ee;
+    uint32_t n_low, n_ambiguous;
+    uint8_t  q_min, q_max;
+    uint16_t failed;          /* BL_QFAIL_* */
+    uint32_t reserved;
+} bl_read_quality;
+typedef struct bl_quality_stats {
+    uint64_t n_reads, n_reads_kept;  /* kept: failed == 0 and a span that is not empty */
+    uint64_t n_bases, n_bases_kept;
+    uint64_t n_too_short, n_too_long, n_ambiguous, n_low, n_mean, n_ee;  /* reads per filter bit */
+    uint64_t reserved[2];
+} bl_quality_stats;
+int bl_scan_read_quality(bl_ctx* ctx, const bl_batch* batch, const bl_text_index* index, const bl_quality_rule* rule,
+                         bl_read_quality* d_records /* nullable */, uint64_t* d_spans /* nullable */, bl_quality_stats* stats /* host, nullable */);
+enum { BL_SPANS_PAIRED = 1u << 0 };
+int bl_spans_intersect(bl_ctx* ctx, const bl_batch* batch, const uint64_t* d_offsets, const uint64_t* d_a, const uint64_t* d_b /* nullable */,
+                       uint32_t flags, uint64_t* d_out);
+
 /* Count reduction across the GPUs of one node: ctxs[g] is the context of device g (all distinct devices),
  * counters holds n_gpu rows of n 64-bit counters — row g = GPU g's local counts in, the column sums out (in every row).  One
  * ncclAllReduce(sum, uint64) per GPU over RCCL / xGMI, called on RCCL's C API directly (librccl.so.1 is loaded on first use);
