@@ -33,6 +33,7 @@ SYMBOLS = [
     "bl_text_write", "bl_bgzf_bound", "bl_bgzf_deflate", "bl_text_write_bgzf",
     "bl_scan_read_steps", "bl_link_support", "bl_steps_format_gaf",
     "bl_scan_read_quality", "bl_spans_intersect",
+    "bl_scan_read_adapters",
 ]
 
 
@@ -137,6 +138,35 @@ class QualityStats(C.Structure):
 
     def as_dict(self):
         return {name: int(getattr(self, name)) for name, _ in self._fields_ if name != "reserved"}
+
+
+ADAPT_POLY_BEFORE, ADAPT_PAIR, ADAPT_ADAPTER, ADAPT_POLY_AFTER, ADAPT_TOO_SHORT, ADAPT_PAIR_SKIPPED = 1, 2, 4, 8, 16, 32
+ADAPTERS_PAIRED = 1
+MAX_ADAPTERS, ADAPTER_MAX_LEN, ADAPTER_PAIR_MAX_LEN = 8, 64, 512
+# bl_read_adapters as a numpy record (32 bytes)
+READ_ADAPTERS_DTYPE = [("begin", "<u8"), ("end", "<u8"), ("match_pos", "<u4"), ("insert", "<u4"), ("adapter", "<u2"), ("overlap", "u1"), ("mismatches", "u1"),
+                       ("pair_mismatches", "<u2"), ("cut", "u1"), ("reserved", "u1")]
+
+
+class AdapterRule(C.Structure):
+    """bl_adapter_rule (616 bytes)"""
+    _fields_ = [("flags", C.c_uint32), ("n_adapters", C.c_uint32), ("adapter_len", C.c_uint32 * MAX_ADAPTERS),
+                ("adapters", (C.c_char * ADAPTER_MAX_LEN) * MAX_ADAPTERS)] + \
+               [(name, C.c_uint32) for name in ("min_overlap", "error_num", "error_den", "pair_min_overlap", "pair_error_num", "pair_error_den", "pair_max_diff",
+                                                "poly_before", "poly_after", "poly_min_len", "poly_per", "poly_max_mismatch", "reserved")] + \
+               [("min_len", C.c_uint64)]
+
+
+class AdapterStats(C.Structure):
+    """bl_adapter_stats"""
+    _fields_ = [(name, C.c_uint64) for name in ("n_reads", "n_reads_cut", "n_reads_kept", "n_bases", "n_bases_kept", "n_poly_before", "n_pair", "n_adapter",
+                                                "n_poly_after", "n_too_short", "n_pair_skipped")] + \
+               [("per_adapter", C.c_uint64 * MAX_ADAPTERS), ("reserved", C.c_uint64 * 5)]
+
+    def as_dict(self):
+        d = {name: int(getattr(self, name)) for name, _ in self._fields_ if name not in ("reserved", "per_adapter")}
+        d["per_adapter"] = [int(x) for x in self.per_adapter]
+        return d
 
 
 LINK_NONE = 0xFFFFFFFF
@@ -384,6 +414,8 @@ def lib():
     if "BIOLIB_AMD_LIB" not in os.environ or hasattr(L, "bl_scan_read_quality"):
         L.bl_scan_read_quality.argtypes = [vp, vp, vp, C.POINTER(QualityRule), vp, vp, C.POINTER(QualityStats)]
         L.bl_spans_intersect.argtypes = [vp, vp, vp, vp, vp, u32, vp]
+    if "BIOLIB_AMD_LIB" not in os.environ or hasattr(L, "bl_scan_read_adapters"):
+        L.bl_scan_read_adapters.argtypes = [vp, vp, vp, vp, C.POINTER(AdapterRule), vp, vp, C.POINTER(AdapterStats)]
     _lib = L
     return L
 

@@ -405,6 +405,16 @@ int bl_batch_scan_view(bl_ctx* c, const bl_batch* b, int ensure, const uint32_t*
     return BL_OK;
 }
 
+// what bl_adapters.hip needs of a batch: its packed copy (ScanParams::codes_packed, chunk_bad; chunk 0 of each), NULL for a batch without
+// one and under bl_ctx_set_option("packed_codes", 0)
+int bl_batch_packed_view(bl_ctx* c, const bl_batch* b, const uint32_t** codes, const uint32_t** chunk_bad)
+{
+    const bool have = c->packed_codes && b->codes;
+    *codes = have ? b->codes : nullptr;
+    *chunk_bad = have ? b->chunk_bad : nullptr;
+    return BL_OK;
+}
+
 // Device scratch that lives with the context (slot 0..7), grown on demand and never shrunk: the set operations and the
 // bucketed counter need gigabytes of temporary space per call, and hipMalloc / hipFree of that size costs more than their
 // kernels.  The caller has synchronised its previous use (these entry points are synchronous).  nullptr on failure.

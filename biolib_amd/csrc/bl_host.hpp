@@ -49,6 +49,8 @@ int bl_batch_adopt_like(bl_ctx* ctx, const bl_batch* like, void* d_bases, uint32
 int bl_batch_describe(const bl_batch* batch, bl_ctx** ctx, uint64_t* n_bases, uint64_t* n_seqs, uint64_t* read_len);
 // the start-bit vector the position-tiled scans read (NULL: one sequence).  ensure: build it where a fixed-length batch has not needed it yet
 int bl_batch_scan_view(bl_ctx* ctx, const bl_batch* batch, int ensure, const uint32_t** start_bits);
+// the batch's packed copy (bl_scan_core.hpp: ScanParams::codes_packed, chunk_bad), NULL where it has none or the context's "packed_codes" is 0
+int bl_batch_packed_view(bl_ctx* ctx, const bl_batch* batch, const uint32_t** codes, const uint32_t** chunk_bad);
 // (bl_batch_device_bases is public: include/biolib_amd.h)
 // what bl_text_index_info does not tell (bl_format.hip): the index's context and the n_bases of the batch it was built with
 int bl_text_index_describe(const bl_text_index* index, bl_ctx** ctx, uint64_t* n_bases);

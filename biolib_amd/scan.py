@@ -1106,6 +1106,31 @@ class ReadQuality:
         return self.records[:self.n_seqs].cpu().numpy().view(np.dtype(capi.READ_QUALITY_DTYPE)).reshape(-1).copy()
 
 
+# the public Illumina adapter sequences, as cutadapt's and fastp's documentation give them: what read-through leaves at a read's 3' end
+ADAPTERS = {
+    "truseq": "AGATCGGAAGAGC",            # TruSeq and most other Illumina kits, both reads
+    "nextera": "CTGTCTCTTATACACATCT",     # Nextera / transposase
+    "small_rna": "TGGAATTCTCGGGTGCCAAGG",  # small RNA 3' adapter
+}
+
+
+class ReadAdapters:
+    """What bl_scan_read_adapters wrote, one row per read: `records` is the raw device buffer, int64[n_seqs, 4] (capi.READ_ADAPTERS_DTYPE;
+    begin and end are the span after the four steps, before min_len), `spans` an int64 device tensor [n_seqs, 2] for intersect_spans,
+    select and format — (0, 0) where the result is empty or shorter than min_len — and `stats` the call's totals as a dict, or None
+    where they were not asked for."""
+
+    def __init__(self, n_seqs, records, spans, stats):
+        self.n_seqs = int(n_seqs)
+        self.records = records
+        self.spans = spans
+        self.stats = stats
+
+    def host(self):
+        """a numpy structured array of the records (capi.READ_ADAPTERS_DTYPE)"""
+        return self.records[:self.n_seqs].cpu().numpy().view(np.dtype(capi.READ_ADAPTERS_DTYPE)).reshape(-1).copy()
+
+
 class Batch:
     """Device-resident sequences (bl_batch)."""
 
@@ -1644,6 +1669,93 @@ class Batch:
         spans = self.intersect_spans(rq.spans, None, True) if paired else rq.spans
         out, source_index = self.select(spans, paired if keep_empty is None else keep_empty)
         return out, source_index, spans, rq
+
+    # ---- adapters, read-through between mates and poly tails: spans from the bases
+    def read_adapters_raw(self, rule, records=None, spans=None, stats=None, spans_in=None, offsets=None):
+        """bl_scan_read_adapters: `rule` a capi.AdapterRule, `spans_in` (n_seqs pairs of 64-bit words) or None, `records` (n_seqs rows of
+        32 bytes) and `spans` 16-byte aligned device tensors or None, `stats` a capi.AdapterStats or None, `offsets` as select.
+        Asynchronous on the context's stream without stats.  The library checks every argument."""
+        check(self._lib.bl_scan_read_adapters(self.ctx._h, self._h, _ptr(offsets), _ptr(spans_in), C.byref(rule), _ptr(records), _ptr(spans),
+                                              C.byref(stats) if stats is not None else None))
+
+    @staticmethod
+    def _poly_mask(letters):
+        mask = 0
+        for ch in (letters.decode("latin1") if isinstance(letters, (bytes, bytearray)) else letters):
+            code = "ACGT".find(ch.upper().replace("U", "T"))
+            if code < 0:
+                raise ValueError("a poly base is one of ACGT: %r" % (ch,))
+            mask |= 1 << code
+        return mask
+
+    @staticmethod
+    def adapter_rule(adapters=(), paired=False, min_overlap=3, max_error=0.1, pair_min_overlap=30, pair_max_error=0.2, pair_max_diff=5, poly_before="",
+                     poly_after="", poly_min_len=10, poly_per=8, poly_max_mismatch=5, min_len=0):
+        """The capi.AdapterRule (bl_adapter_rule) of read_adapters' arguments, for read_adapters_raw: `adapters` one sequence or up to 8 (str or
+        bytes, 1 .. 64 bases), max_error and pair_max_error a number or (num, den), the poly arguments strings of bases.  Raises ValueError
+        for what cannot be written into the struct; the library refuses everything else."""
+        r = capi.AdapterRule()
+        if isinstance(adapters, (str, bytes, bytearray)):
+            adapters = [adapters]
+        adapters = [a.encode("latin1") if isinstance(a, str) else bytes(a) for a in adapters]
+        if len(adapters) > capi.MAX_ADAPTERS:
+            raise ValueError("at most %d adapters" % capi.MAX_ADAPTERS)
+        r.flags = capi.ADAPTERS_PAIRED if paired else 0
+        r.n_adapters = len(adapters)
+        for a, text in enumerate(adapters):
+            if not 1 <= len(text) <= capi.ADAPTER_MAX_LEN:
+                raise ValueError("an adapter holds 1 .. %d bases" % capi.ADAPTER_MAX_LEN)
+            r.adapter_len[a] = len(text)
+            C.memmove(r.adapters[a], text, len(text))
+        r.min_overlap = int(min_overlap)
+        r.error_num, r.error_den = Batch._fraction(max_error, (1, 10))
+        r.pair_min_overlap = int(pair_min_overlap)
+        r.pair_error_num, r.pair_error_den = Batch._fraction(pair_max_error, (1, 5))
+        r.pair_max_diff = int(pair_max_diff)
+        r.poly_before, r.poly_after = Batch._poly_mask(poly_before), Batch._poly_mask(poly_after)
+        r.poly_min_len, r.poly_per, r.poly_max_mismatch = int(poly_min_len), int(poly_per), int(poly_max_mismatch)
+        r.min_len = int(min_len)
+        return r
+
+    def read_adapters(self, adapters=(), paired=False, spans=None, min_overlap=3, max_error=0.1, pair_min_overlap=30, pair_max_error=0.2, pair_max_diff=5,
+                      poly_before="", poly_after="", poly_min_len=10, poly_per=8, poly_max_mismatch=5, min_len=0, stats=False, offsets=None):
+        """Cut poly tails, read-through between mates and 3' adapters from every read (bl_scan_read_adapters; the header states the
+        rule): a ReadAdapters.  `spans`: the spans to start from (read_quality's), None for the whole reads.  Four steps, each off at
+        its empty value:
+        poly_before   bases such as "G" or "ACGT": a 3' tail of at least poly_min_len of one of them goes, with one mismatch allowed per
+                      poly_per bases (0: none) and poly_max_mismatch at most
+        paired        reads 2j and 2j + 1 are mates: where the first I bases of one are the reverse complement of the first I of the other
+                      (I >= pair_min_overlap, at most pair_max_error of them and pair_max_diff differing), both end at I
+        adapters      up to 8 sequences of up to 64 bases (biolib_amd.ADAPTERS has the Illumina ones): the best match without indels of
+                      at least min_overlap bases with at most max_error ((num, den) or a number) of them differing; the read ends there
+        poly_after    as poly_before, on what is left
+        A result shorter than min_len gets the span (0, 0).  stats=True makes the call synchronous and fills `.stats`."""
+        import torch
+
+        rule = self.adapter_rule(adapters, paired, min_overlap, max_error, pair_min_overlap, pair_max_error, pair_max_diff, poly_before, poly_after,
+                                 poly_min_len, poly_per, poly_max_mismatch, min_len)
+        n = self.n_seqs
+        dev = self.ctx.torch_device
+        if spans is not None and not (isinstance(spans, torch.Tensor) and spans.is_cuda and spans.dtype == torch.int64 and spans.is_contiguous() and
+                                      spans.numel() == 2 * n):
+            raise ValueError("spans: a contiguous int64 device tensor [n_seqs, 2]")
+        records = torch.zeros((max(n, 1), 4), dtype=torch.int64, device=dev)  # (torch allocations are 16-byte aligned)
+        out = torch.zeros((max(n, 1), 2), dtype=torch.int64, device=dev)
+        st = capi.AdapterStats() if stats else None
+        self.ctx._inputs_ready()
+        self.read_adapters_raw(rule, records, out, st, spans, self._device_offsets(offsets))
+        return ReadAdapters(n, records[:n], out[:n], st.as_dict() if stats else None)
+
+    def trim_adapters(self, adapters, paired=False, spans=None, keep_empty=None, **rule):
+        """Adapter trimming in one chain on the device: read_adapters(adapters, paired, spans, **rule), intersect_spans(paired) where the
+        reads are interleaved mates, select.  (Batch, source_index, spans, ReadAdapters): the trimmed reads as a new batch, where each
+        came from, the spans that went into select (what format takes for the qualities) and the source's records.  `spans` is where a
+        quality step's result goes in: b.trim_adapters(A, paired=True, spans=rq.spans) follows read_quality.  keep_empty defaults to
+        `paired`, so that mates stay in step."""
+        ra = self.read_adapters(adapters, paired, spans, **rule)
+        out_spans = self.intersect_spans(ra.spans, None, True) if paired else ra.spans
+        out, source_index = self.select(out_spans, paired if keep_empty is None else keep_empty)
+        return out, source_index, out_spans, ra
 
     # ---- threading: the reads' steps through the compacted graph
     def read_steps_raw(self, table, k, flags, nodes, unitig_offsets, n_unitigs, steps, capacity, first=0, n=0, offsets=None, stats=None):

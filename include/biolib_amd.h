@@ -1067,6 +1067,86 @@ enum { BL_SPANS_PAIRED = 1u << 0 };
 int bl_spans_intersect(bl_ctx* ctx, const bl_batch* batch, const uint64_t* d_offsets, const uint64_t* d_a, const uint64_t* d_b /* nullable */,
                        uint32_t flags, uint64_t* d_out);
 
+/* Adapter, read-through and poly-tail trimming on the device: the other half of what fastp, cutadapt and Trimmomatic do in front of a
+ * k-mer counter.  bl_scan_read_adapters makes one span per read, in the form bl_batch_select, bl_batch_format and bl_spans_intersect take.
+ *
+ * d_offsets as bl_batch_select takes them; read i has length L.  A base is VALID where the scans' encoder accepts it (ACGTUacgtu, U as T);
+ * an invalid base never matches anything, neither an adapter's base nor a poly base nor a mate's base.  The span starts as
+ * [b, e) = d_spans_in[i] clamped to the read as bl_batch_select clamps it, [0, L) without d_spans_in.  An empty input span gives the span
+ * (0, 0) and a record without a match and with cut == 0: no step runs.  Otherwise four steps in this order, each off at its zero value:
+ *   1  poly tail (poly_before: a mask of bases, bit c = code c, A C G T = 0 1 2 3).  For a base X of the mask walk t = 1, 2, ... from
+ *      the span's 3' end with x(t) = the number of the last t bases that are not X.  The walk stops at the first t with
+ *      x(t) > poly_max_mismatch, or with t >= poly_min_len and x(t) > floor(t / poly_per) (poly_per 0: x(t) > 0).  n = the bases walked
+ *      before the stop, e - b where nothing stops it.  Where n >= poly_min_len and one of those n bases is X, X proposes the position
+ *      of the leftmost X among them.  e becomes the smallest proposal (on a tie the lowest code, which gives the same e).
+ *   2  read-through between mates (BL_ADAPTERS_PAIRED only; reads 2j and 2j + 1 are mates r1 and r2 of lengths L1 and L2).  The WHOLE
+ *      reads are compared, whatever the input spans: for I in [pair_min_overlap, min(L1, L2)], d(I) = the number of i in [0, I) where
+ *      r1[i] or r2[I - 1 - i] is invalid or r1[i] != complement(r2[I - 1 - i]).  I qualifies where
+ *      d(I) <= min(pair_max_diff, floor(I * pair_error_num / pair_error_den)).  The LARGEST qualifying I is the insert: both mates get
+ *      insert = I, pair_mismatches = d(I) and e = max(b, min(e, I)); BL_ADAPT_PAIR is set on a mate whose end moved.  A pair with
+ *      min(L1, L2) > BL_ADAPTER_PAIR_MAX_LEN is not tested: BL_ADAPT_PAIR_SKIPPED on both mates.
+ *   3  3' adapters (cutadapt -a with --no-indels).  For adapter a of length A, O = min(min_overlap, A); for every p in [b, e - O],
+ *      o = min(A, e - p) and m = the number of j < o where read[p + j] is invalid or differs from a[j] (letter case ignored, U = T).
+ *      (a, p) is a candidate where m <= floor(o * error_num / error_den).  The match is the candidate with the most matching bases
+ *      o - m, then the smaller p, then the lower a.  Then e = p; the record keeps adapter = a, match_pos = p, overlap = o and
+ *      mismatches = m.  A match at p = b leaves an empty span.
+ *   4  poly tail (poly_after), as step 1, on the span that is left.
+ * Then n = e - b: d_spans[i] = (b, e) where n >= min_len and n > 0, else (0, 0); BL_ADAPT_TOO_SHORT where n < min_len.  The record's
+ * begin and end are (b, e) before min_len.  Mates are not dropped together here: bl_spans_intersect(..., BL_SPANS_PAIRED) does that.
+ * Statistics: n_reads_cut = reads with one of the four step bits; n_reads_kept, n_bases_kept = reads and bases of the spans that are
+ * not (0, 0); one count per bit of `cut`; per_adapter[a] = reads matched by adapter a.
+ * Outputs, each nullable: d_records[i] (32 bytes, 16-byte aligned), d_spans, *stats (host).  Without stats the call is asynchronous on
+ * the context's stream like the scans; with stats it is synchronous.  Results are bit-reproducible: no atomic and no shared memory
+ * decides a value or a place.  The bases come from the batch's packed 2-bit copy where it has one, from the ASCII bases where a
+ * 16-base chunk holds an invalid base and for a batch without a copy; no byte outside the batch's n_bases, the copy or the outputs is
+ * touched.  match_pos saturates at UINT32_MAX - 1 for a position beyond it.
+ * BL_ERR_INVALID with a message, nothing launched: a NULL ctx, batch or rule; a batch of another context; d_offsets NULL on a ragged
+ * batch; unknown flag bits; BL_ADAPTERS_PAIRED with an odd n_seqs; n_adapters > 8; an adapter length of 0 or above 64; an adapter byte
+ * outside ACGTUacgtu; min_overlap 0 with n_adapters > 0; a denominator of 0 or num > den; pair_min_overlap 0 under the flag; a poly mask
+ * above 15; poly_min_len 0 with a mask set; reserved != 0; d_records, d_spans or d_spans_in not 16-byte aligned.
+ * Knowingly different from cutadapt and fastp: no indels, no wildcards in adapters, 3' adapters only, one match per read, and no
+ * fall-back from step 2 to step 3 (both always run). */
+#define BL_MAX_ADAPTERS 8
+#define BL_ADAPTER_MAX_LEN 64
+#define BL_ADAPTER_PAIR_MAX_LEN 512
+enum { BL_ADAPT_POLY_BEFORE = 1, BL_ADAPT_PAIR = 2, BL_ADAPT_ADAPTER = 4, BL_ADAPT_POLY_AFTER = 8,
+       BL_ADAPT_TOO_SHORT = 16, BL_ADAPT_PAIR_SKIPPED = 32 };
+enum { BL_ADAPTERS_PAIRED = 1u << 0 };
+typedef struct bl_adapter_rule {
+    uint32_t flags;                      /* BL_ADAPTERS_PAIRED: reads 2j and 2j + 1 are mates, step 2 runs */
+    uint32_t n_adapters;                 /* 0 .. 8; 0 = step 3 off */
+    uint32_t adapter_len[BL_MAX_ADAPTERS];                  /* 1 .. 64 */
+    char     adapters[BL_MAX_ADAPTERS][BL_ADAPTER_MAX_LEN]; /* ACGTUacgtu only, no wildcard */
+    uint32_t min_overlap;                /* step 3, >= 1 (cutadapt -O) */
+    uint32_t error_num, error_den;       /* step 3: mismatches allowed in an overlap of o bases = floor(o * num / den); den >= 1, num <= den */
+    uint32_t pair_min_overlap;           /* step 2, >= 1 */
+    uint32_t pair_error_num, pair_error_den, pair_max_diff;
+    uint32_t poly_before, poly_after;    /* masks of bases, bit c = code c of the scans' encoder; 0 = off */
+    uint32_t poly_min_len, poly_per, poly_max_mismatch;   /* poly_per 0 = no mismatch allowed */
+    uint32_t reserved;
+    uint64_t min_len;                    /* span (0, 0) where the result is shorter */
+} bl_adapter_rule;
+typedef struct bl_read_adapters {        /* 32 bytes, 16-byte aligned */
+    uint64_t begin, end;                 /* the span after the four steps, before min_len */
+    uint32_t match_pos;                  /* read-relative start of step 3's match, UINT32_MAX: none */
+    uint32_t insert;                     /* step 2's I, 0: none */
+    uint16_t adapter;                    /* index of the matched adapter, 0xFFFF: none */
+    uint8_t  overlap, mismatches;        /* of step 3's match */
+    uint16_t pair_mismatches;
+    uint8_t  cut;                        /* BL_ADAPT_*: which steps moved an end, TOO_SHORT, PAIR_SKIPPED */
+    uint8_t  reserved;
+} bl_read_adapters;
+typedef struct bl_adapter_stats {
+    uint64_t n_reads, n_reads_cut, n_reads_kept, n_bases, n_bases_kept;
+    uint64_t n_poly_before, n_pair, n_adapter, n_poly_after, n_too_short, n_pair_skipped;
+    uint64_t per_adapter[BL_MAX_ADAPTERS];
+    uint64_t reserved[5];
+} bl_adapter_stats;
+int bl_scan_read_adapters(bl_ctx* ctx, const bl_batch* batch, const uint64_t* d_offsets /* as bl_batch_select */,
+                          const uint64_t* d_spans_in /* nullable */, const bl_adapter_rule* rule,
+                          bl_read_adapters* d_records /* nullable */, uint64_t* d_spans /* nullable */,
+                          bl_adapter_stats* stats /* host, nullable */);
+
 /* Count reduction across the GPUs of one node: ctxs[g] is the context of device g (all distinct devices),
  * counters holds n_gpu rows of n 64-bit counters — row g = GPU g's local counts in, the column sums out (in every row).  One
  * ncclAllReduce(sum, uint64) per GPU over RCCL / xGMI, called on RCCL's C API directly (librccl.so.1 is loaded on first use);
