@@ -34,6 +34,7 @@ SYMBOLS = [
     "bl_scan_read_steps", "bl_link_support", "bl_steps_format_gaf",
     "bl_scan_read_quality", "bl_spans_intersect",
     "bl_scan_read_adapters",
+    "bl_scan_read_duplicates",
 ]
 
 
@@ -166,6 +167,29 @@ class AdapterStats(C.Structure):
     def as_dict(self):
         d = {name: int(getattr(self, name)) for name, _ in self._fields_ if name not in ("reserved", "per_adapter")}
         d["per_adapter"] = [int(x) for x in self.per_adapter]
+        return d
+
+
+DEDUP_PAIRED, DEDUP_CANONICAL = 1, 2
+DUP_DUPLICATE, DUP_EMPTY, DUP_REVERSED = 1, 2, 4
+# bl_read_duplicate as a numpy record (16 bytes, one per unit)
+READ_DUPLICATE_DTYPE = [("first", "<u4"), ("kept", "<u4"), ("copies", "<u4"), ("flags", "<u4")]
+
+
+class DedupRule(C.Structure):
+    """bl_dedup_rule (32 bytes)"""
+    _fields_ = [("flags", C.c_uint32), ("hash_bits", C.c_uint32), ("prefix_len", C.c_uint64), ("seed", C.c_uint64), ("reserved", C.c_uint64)]
+
+
+class DedupStats(C.Structure):
+    """bl_dedup_stats"""
+    _fields_ = [(name, C.c_uint64) for name in ("n_units", "n_empty", "n_classes", "n_duplicates", "n_reversed", "largest_class", "n_reads_kept",
+                                                "n_bases_kept")] + \
+               [("class_hist", C.c_uint64 * 16), ("n_mixed_groups", C.c_uint64), ("rounds", C.c_uint64), ("reserved", C.c_uint64 * 6)]
+
+    def as_dict(self):
+        d = {name: int(getattr(self, name)) for name, _ in self._fields_ if name not in ("reserved", "class_hist")}
+        d["class_hist"] = [int(x) for x in self.class_hist]
         return d
 
 
@@ -416,6 +440,8 @@ def lib():
         L.bl_spans_intersect.argtypes = [vp, vp, vp, vp, vp, u32, vp]
     if "BIOLIB_AMD_LIB" not in os.environ or hasattr(L, "bl_scan_read_adapters"):
         L.bl_scan_read_adapters.argtypes = [vp, vp, vp, vp, C.POINTER(AdapterRule), vp, vp, C.POINTER(AdapterStats)]
+    if "BIOLIB_AMD_LIB" not in os.environ or hasattr(L, "bl_scan_read_duplicates"):
+        L.bl_scan_read_duplicates.argtypes = [vp, vp, vp, vp, vp, C.POINTER(DedupRule), vp, vp, C.POINTER(DedupStats)]
     _lib = L
     return L
 

@@ -380,6 +380,7 @@ hipStream_t bl_ctx_stream(bl_ctx* c)
     return c->lanes[0].own;
 }
 int bl_ctx_device(bl_ctx* c) { return c->device; }
+int bl_ctx_kernel_timing_on(bl_ctx* c) { return c->ktiming ? 1 : 0; }  // bl_dedup.hip
 int bl_ctx_count128_tables(bl_ctx* c) { return c->count128_tables ? 1 : 0; }  // bl_superkmer128.hip
 int bl_ctx_jaccard128_path(bl_ctx* c) { return c->jaccard128_path; }            // bl_setops128.hip
 int bl_ctx_table_prefix_bits(bl_ctx* c) { return c->table_prefix_bits; }        // bl_lookup.hip

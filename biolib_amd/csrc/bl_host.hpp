@@ -17,6 +17,7 @@ int bl_ctx_device(bl_ctx* ctx);
 // With bl_ctx_kernel_timing on: an event pair on `stream` around what the caller enqueues between start = 1 and start = 0, added to
 // bl_ctx_kernel_time's sum as one launch.  Nothing otherwise.
 int bl_ctx_kernel_event(bl_ctx* ctx, hipStream_t stream, int start);
+int bl_ctx_kernel_timing_on(bl_ctx* ctx);   // bl_ctx_kernel_timing is on: a call of several phases may set bl_ctx_mark markers between them
 int bl_ctx_count128_tables(bl_ctx* ctx);    // the "count128_tables" option
 int bl_ctx_jaccard128_path(bl_ctx* ctx);    // the "jaccard128_path" option
 int bl_ctx_table_prefix_bits(bl_ctx* ctx);  // the "table_prefix_bits" option
@@ -32,7 +33,7 @@ int bl_ctx_table_prefix_bits(bl_ctx* ctx);  // the "table_prefix_bits" option
 //   5      library workspace (rocPRIM):                links, clean, the BGZF writer (slots, token areas and sizes of the members in flight)
 //          blh::exclusive_sum(_total) take it          and the steps (8 bytes per position; 88 per step for the GAF text): none of them calls
 //                                                      another while it holds 4-6
-//   6      counters, flags, statistics
+//   6      counters, flags, statistics                 (bl_dedup.hip: 93 bytes per unit in slot 4, rocPRIM's workspace in 5, counters and flags in 6)
 void* bl_ctx_scratch(bl_ctx* ctx, int slot, size_t bytes);
 
 // Device memory of short-lived batch buffers, recycled between batches.  bl_ctx_pool_free takes NULL, and hipFree()s what is not the pool's.

@@ -1131,6 +1131,27 @@ class ReadAdapters:
         return self.records[:self.n_seqs].cpu().numpy().view(np.dtype(capi.READ_ADAPTERS_DTYPE)).reshape(-1).copy()
 
 
+class ReadDuplicates:
+    """What bl_scan_read_duplicates wrote: `records` is the raw device buffer, int64[n_units, 2] (capi.READ_DUPLICATE_DTYPE, one row per
+    UNIT: a read, or a pair of mates), `spans` an int64 device tensor [n_seqs, 2] for intersect_spans, select and format — (0, 0) for
+    the reads of a duplicate — and `stats` the call's totals as a dict, or None where they were not asked for."""
+
+    def __init__(self, n_units, records, spans, stats):
+        self.n_units = int(n_units)
+        self.records = records
+        self.spans = spans
+        self.stats = stats
+
+    def host(self):
+        """a numpy structured array of the records (capi.READ_DUPLICATE_DTYPE)"""
+        return self.records[:self.n_units].cpu().numpy().view(np.dtype(capi.READ_DUPLICATE_DTYPE)).reshape(-1).copy()
+
+    @property
+    def kept_mask(self):
+        """a bool device tensor [n_units]: the unit is no duplicate (empty units included)"""
+        return ((self.records[:self.n_units, 1] >> 32) & capi.DUP_DUPLICATE) == 0  # (a row: first | kept << 32, copies | flags << 32)
+
+
 class Batch:
     """Device-resident sequences (bl_batch)."""
 
@@ -1756,6 +1777,55 @@ class Batch:
         out_spans = self.intersect_spans(ra.spans, None, True) if paired else ra.spans
         out, source_index = self.select(out_spans, paired if keep_empty is None else keep_empty)
         return out, source_index, out_spans, ra
+
+    # ---- duplicates: exact copies of reads and pairs
+    def read_duplicates_raw(self, rule, records=None, spans=None, stats=None, spans_in=None, scores=None, offsets=None):
+        """bl_scan_read_duplicates: `rule` a capi.DedupRule, `spans_in` (n_seqs pairs of 64-bit words) and `scores` (n_seqs 64-bit words)
+        or None, `records` (n_units rows of 16 bytes) and `spans` 16-byte aligned device tensors or None, `stats` a capi.DedupStats or
+        None, `offsets` as select.  The library checks every argument."""
+        check(self._lib.bl_scan_read_duplicates(self.ctx._h, self._h, _ptr(offsets), _ptr(spans_in), _ptr(scores), C.byref(rule), _ptr(records),
+                                                _ptr(spans), C.byref(stats) if stats is not None else None))
+
+    def read_duplicates(self, paired=False, spans=None, canonical=False, prefix_len=0, scores=None, stats=False, offsets=None, hash_bits=0, seed=0):
+        """Find the exact duplicates among the reads, or among the pairs of interleaved mates (bl_scan_read_duplicates; the header
+        states the rule): a ReadDuplicates.  `spans`: the spans to compare (read_adapters'), None for the whole reads.
+        canonical    a read also equals its reverse complement, a pair the pair with its mates swapped
+        prefix_len   only the first prefix_len bases of every span count (0: all)
+        scores       an int64 device tensor, one value per READ (read_quality's records[:, 2], the sum of the Phred values): the member
+                     of a class with the largest score stays, the first on a tie; None: the first stays
+        hash_bits and seed change how the work is done, never a result.  stats=True fills `.stats`."""
+        import torch
+
+        n = self.n_seqs
+        dev = self.ctx.torch_device
+        if spans is not None and not (isinstance(spans, torch.Tensor) and spans.is_cuda and spans.dtype == torch.int64 and spans.is_contiguous() and
+                                      spans.numel() == 2 * n):
+            raise ValueError("spans: a contiguous int64 device tensor [n_seqs, 2]")
+        if scores is not None:
+            if not (isinstance(scores, torch.Tensor) and scores.is_cuda and scores.dtype == torch.int64 and scores.numel() == n):
+                raise ValueError("scores: an int64 device tensor [n_seqs]")
+            scores = scores.contiguous()
+        rule = capi.DedupRule()
+        rule.flags = (capi.DEDUP_PAIRED if paired else 0) | (capi.DEDUP_CANONICAL if canonical else 0)
+        rule.hash_bits, rule.prefix_len, rule.seed = int(hash_bits), int(prefix_len), int(seed) & (2**64 - 1)
+        n_units = n // 2 if paired else n
+        records = torch.zeros((max(n_units, 1), 2), dtype=torch.int64, device=dev)  # (torch allocations are 16-byte aligned)
+        out = torch.zeros((max(n, 1), 2), dtype=torch.int64, device=dev)
+        st = capi.DedupStats() if stats else None
+        self.ctx._inputs_ready()
+        self.read_duplicates_raw(rule, records, out, st, spans, scores, self._device_offsets(offsets))
+        return ReadDuplicates(n_units, records[:n_units], out[:n], st.as_dict() if stats else None)
+
+    def dedup(self, paired=False, spans=None, keep_empty=None, **rule):
+        """Duplicate removal in one chain on the device: read_duplicates(paired, spans, **rule), intersect_spans(paired) where the reads
+        are interleaved mates, select.  (Batch, source_index, spans, ReadDuplicates): the reads that stay as a new batch, where each
+        came from, the spans that went into select (what format takes for the qualities) and the source's records.  `spans` is where
+        the trimming steps' result goes in: b.dedup(paired=True, spans=ra.spans, scores=rq.records[:, 2]) follows read_quality and
+        read_adapters.  keep_empty defaults to False here: a duplicate pair goes as a whole."""
+        rd = self.read_duplicates(paired, spans, **rule)
+        out_spans = self.intersect_spans(rd.spans, None, True) if paired else rd.spans
+        out, source_index = self.select(out_spans, False if keep_empty is None else keep_empty)
+        return out, source_index, out_spans, rd
 
     # ---- threading: the reads' steps through the compacted graph
     def read_steps_raw(self, table, k, flags, nodes, unitig_offsets, n_unitigs, steps, capacity, first=0, n=0, offsets=None, stats=None):

@@ -1147,6 +1147,71 @@ int bl_scan_read_adapters(bl_ctx* ctx, const bl_batch* batch, const uint64_t* d_
                           bl_read_adapters* d_records /* nullable */, uint64_t* d_spans /* nullable */,
                           bl_adapter_stats* stats /* host, nullable */);
 
+/* Duplicate removal on the device: what fastp --dedup, clumpify dedupe and Picard MarkDuplicates (without coordinates) do in front of a
+ * k-mer counter, so that a duplicated fragment's errors do not pass a count filter.  bl_scan_read_duplicates finds the units of a batch
+ * that are EXACTLY equal and writes one record per unit and one span per read, in the form bl_batch_select, bl_batch_format and
+ * bl_spans_intersect take.
+ *
+ * Units.  A unit is a read; under BL_DEDUP_PAIRED it is the pair of reads 2u and 2u + 1, and n_seqs must be even.
+ * Letters.  A, C, G, T, with U read as T and letter case ignored; any byte the scans' encoder takes as invalid is one fifth letter N.
+ *   N equals N and never equals a base.
+ * Key of a read.  Its span: d_spans_in[i] clamped to the read as bl_batch_select clamps it, [0, L) without d_spans_in (d_offsets as
+ *   bl_batch_select takes them); cut to its first prefix_len bases where prefix_len > 0.  The key is that string of letters; length
+ *   counts: ACG is not ACGA.
+ * Key of a unit.  For a read its key s; for a pair the ordered pair (s1, s2).
+ * Equality.  Two units are equal where their keys are equal.  Under BL_DEDUP_CANONICAL they are also equal where a read's key is the
+ *   reverse complement of the other's (rc(N) = N), and where a pair's (s1, s2) is the other's (s2, s1): the same fragment sequenced
+ *   from its other strand swaps the mates without reverse-complementing them.
+ * Empty units.  A unit with an empty span in any of its reads is empty: BL_DUP_EMPTY, first = kept = itself, copies = 0.  It belongs to
+ *   no class, and its reads' clamped spans pass through, an empty one as (0, 0).
+ * Classes.  The other units fall into classes of equal units.  first is the lowest unit index of the class.  Without d_scores kept is
+ *   first.  With d_scores (one word per READ) a unit's score is the wrapping 64-bit sum of its reads' scores, and kept is the member
+ *   with the largest score, the lowest index on a tie (Picard's best sum of base qualities; bl_read_quality's sum is the intended
+ *   input).  copies is the class size, on every member.
+ * Flags.  BL_DUP_DUPLICATE on every member but kept.  BL_DUP_REVERSED where a member's forward key differs from the kept unit's.
+ * Spans.  d_spans of a duplicate's reads are (0, 0); those of a kept unit's reads are the clamped input spans (not cut to prefix_len).
+ * Statistics.  n_units; n_empty; n_classes; n_duplicates and n_reversed = the units with that flag; largest_class; n_reads_kept and
+ *   n_bases_kept = reads and bases of the spans written that are not (0, 0); class_hist[c - 1] = classes of size c, the last entry
+ *   those of 16 or more (fastp's duplication histogram).  n_mixed_groups and rounds describe the work done, not the result, and depend
+ *   on hash_bits and seed; nothing else does.
+ * Results are exact and bit-identical over reruns: no atomic decides a value or a place.  Outputs, each nullable: d_records[u] (16
+ * bytes, 16-byte aligned, one per UNIT), d_spans (one pair per READ), *stats (host).  The call waits for the device once per
+ * resolution round (one round unless hash_bits is small) and returns without waiting for its last kernels where stats is NULL; with
+ * stats it is synchronous.  No byte outside the batch's n_bases, its packed copy and the outputs is touched.  Temporaries come from
+ * the context's scratch, 93 bytes per unit.  With bl_ctx_kernel_timing on, the call sets five markers (bl_ctx_mark): in front of its
+ * first phase and behind each of its four phases (DESIGN.md §5.4u names them).
+ * BL_ERR_INVALID with a message, nothing launched: a NULL ctx, batch or rule; a batch of another context; d_offsets NULL on a ragged
+ * batch; unknown flag bits; BL_DEDUP_PAIRED with an odd n_seqs; hash_bits above 96; reserved != 0; 2^32 units or more; d_records,
+ * d_spans or d_spans_in not 16-byte aligned.
+ * Not done: duplicates across batches, near-duplicates with mismatches, UMIs, optical coordinates from names, merging of mates. */
+enum { BL_DEDUP_PAIRED = 1u << 0, BL_DEDUP_CANONICAL = 1u << 1 };
+enum { BL_DUP_DUPLICATE = 1, BL_DUP_EMPTY = 2, BL_DUP_REVERSED = 4 };
+typedef struct bl_dedup_rule {
+    uint32_t flags;         /* BL_DEDUP_* */
+    uint32_t hash_bits;     /* 0 = the default (96); 1 .. 96: how finely the units are grouped before they are compared.  Changes speed only */
+    uint64_t prefix_len;    /* 0 = the whole span; P > 0: only the first P bases of every read's span are its key */
+    uint64_t seed;          /* changes the grouping only, never a result */
+    uint64_t reserved;      /* 0 */
+} bl_dedup_rule;
+typedef struct bl_read_duplicate {   /* 16 bytes, 16-byte aligned; one per UNIT */
+    uint32_t first;   /* lowest unit index of the class */
+    uint32_t kept;    /* the unit of the class that stays */
+    uint32_t copies;  /* class size, on every member; 0 on an empty unit */
+    uint32_t flags;   /* BL_DUP_* */
+} bl_read_duplicate;
+typedef struct bl_dedup_stats {
+    uint64_t n_units, n_empty, n_classes, n_duplicates, n_reversed, largest_class;
+    uint64_t n_reads_kept, n_bases_kept;     /* reads and bases of the spans written that are not (0, 0) */
+    uint64_t class_hist[16];                 /* classes of size 1 .. 15, and 16 or more */
+    uint64_t n_mixed_groups;                 /* groups of units compared together that held more than one class: not part of the result */
+    uint64_t rounds;                         /* resolution rounds run: same remark */
+    uint64_t reserved[6];
+} bl_dedup_stats;
+int bl_scan_read_duplicates(bl_ctx* ctx, const bl_batch* batch, const uint64_t* d_offsets /* as bl_batch_select */,
+                            const uint64_t* d_spans_in /* nullable */, const uint64_t* d_scores /* one per READ, nullable */,
+                            const bl_dedup_rule* rule, bl_read_duplicate* d_records /* nullable */, uint64_t* d_spans /* nullable */,
+                            bl_dedup_stats* stats /* host, nullable */);
+
 /* Count reduction across the GPUs of one node: ctxs[g] is the context of device g (all distinct devices),
  * counters holds n_gpu rows of n 64-bit counters — row g = GPU g's local counts in, the column sums out (in every row).  One
  * ncclAllReduce(sum, uint64) per GPU over RCCL / xGMI, called on RCCL's C API directly (librccl.so.1 is loaded on first use);
